@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- frame-pairs/s of the EfficientLO-Net hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--batch B --height H --width W]
+    python bench.py [--gpus N --steps K --warmup W] [--batch B --height H --width W] [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): the full 4-level PWC pyramid -- Siamese set-conv
 pyramid, initial attentive cost volume, coarse pose, three warp-refinement levels
@@ -17,22 +17,28 @@ relays rank 0's line.  Frame pairs are independent, so ranks shard the stream wi
 step's pose is logged on the device and the logs are all-gathered (7 floats per pair) once per timed repeat, inside
 the timed region, so rank 0 can chain them (main.py:557-572): the only exchange inference has.  scaling = weak.
 
-Timing: W untimed warm-up steps (at least 2 per lane), then repeats of EXACTLY K steps, each bracketed by a barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks; repeats continue until 0.25 s have been
-measured (a 20-step run at batch 1 is 2.5 ms of signal otherwise) and `ms_per_step` / `value` come from the MEDIAN
-repeat (`repeats`, `ms_per_step_repeats` show them all).
+Timing: W untimed warm-up steps (at least 2 per lane), then ONE timed repeat of EXACTLY K steps, bracketed by a barrier +
+torch.cuda.synchronize() on both sides and reduced with MAX over ranks: `ms_per_step` / `value` come from it.  With
+--full, further repeats of K steps follow until 0.25 s have been measured (a 20-step run at batch 1 is 2.5 ms of signal
+otherwise); `repeats`, `ms_per_step_repeats` and `ms_per_step_median` show them (the headline stays the first repeat).
+
+--dump-outputs DIR: after the timed steps, the arrays the last timed step handed its caller (submit()'s outputs: the four
+levels' [q_norm, t] and l0_xyz_f1) go to DIR/<name>.npy as float32.  Inputs, weights and visiting orders are seeded, so the
+same arguments give the same inputs on every run: two builds can be compared output for output.
 
 Throughput design: the whole forward is one hipGraph; `--lanes` graphs (default 8), each with its own static
 buffers, dealt over one stream per hardware queue (model.distinct_queue_streams), keep independent forwards
 in flight (step i rides lane i % lanes).
 
-Besides the contract keys the line carries (rank 0):
+A plain run does only what the headline needs (set-up, warm-up, the K timed steps, the line).  With --full the line
+also carries (rank 0):
   roofline     -- SURVEY.md section 8(d): the dominant kernel of the timed path (fused cost-volume stage 1 at l0) timed
                   live with HIP events, its algorithmic bytes against the 8 TB/s HBM roofline and its executed
                   matrix-core flops against the peak of the dtype it issues; plus `cost_volume_*`: ALL cost-volume
                   kernels of a forward (four levels) at batch 8, fp32 and fp16 feature storage (configs[2])
   cpu_baseline -- the CPU oracle (oracle/, kind "port") on one core and on all host cores
   batch8, from_raw_clouds, dense_f32, train_dp -- see the functions below
+  rccl         -- N > 1 (or ELO_BENCH_FORCE_DIST=1): the collectives of the path under a clock of their own
 """
 import argparse
 import importlib
@@ -98,9 +104,15 @@ def parse():
                     help="every N-th replay of a lane runs the graph recorded on the range-checked kernels (the fp16 split's "
                          "production guard, PWCLONet.capture(check_every=N)); 0: off")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeats of the timed loop up to 0.25 s, the roofline / cpu_baseline / from_raw_clouds / "
+                         "batch8 / submit_ordering / sparse / hires / dense_f32 / train_dp legs and (N > 1) the rccl clocks; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true",
-                    help="only the timed loop: no roofline / cpu_baseline / from_raw_clouds / batch8 / dense_f32 / train_dp legs")
+                    help="with --full: only the timed loop, no roofline / cpu_baseline / from_raw_clouds / batch8 / dense_f32 / train_dp "
+                         "legs (a run without --full has none of them)")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from the committed counter passes instead of two rocprofv3 --pmc child runs (~30 s)")
     ap.add_argument("--cpu-pairs", type=int, default=24, help="pairs in the one-core CPU sample (all cores: 3 per core)")
@@ -777,6 +789,28 @@ def rccl_leg(dist, dev, backend, world, rank, pose_block, numa, iters=10):
     return out
 
 
+# ----------------------------------------------------------------------------- outputs of the last timed step
+OUTPUT_NAMES = ("l0_q_norm", "l0_t", "l1_q_norm", "l1_t", "l2_q_norm", "l2_t", "l3_q_norm", "l3_t", "l0_xyz_f1")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, outs):
+    """The arrays of one step's outputs as DIR/<name>.npy, float32 (get_model_from_projection's names; `out<i>` otherwise).
+    An array beyond its share of 64 MB is replaced by a fixed, seeded sample of its flattened elements (the same elements on
+    every run with the same arguments)."""
+    import numpy as np
+    import torch
+    outs = [t for t in outs if torch.is_tensor(t)]
+    names = OUTPUT_NAMES if len(outs) == len(OUTPUT_NAMES) else ["out%d" % i for i in range(len(outs))]
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(outs))
+    for name, t in zip(names, outs):
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # ----------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -834,12 +868,14 @@ def main():
     B, H, W = args.batch, args.height, args.width
     lanes = 1 if (args.no_graph or dry) else max(1, args.lanes)
     warmup = max(args.warmup, 2 * lanes)
+    last = {}                                            # the outputs the last timed step handed back (--dump-outputs)
     if dry:
         net = None
         pose_log = torch.zeros((max(args.steps, warmup), B, 7))
 
         def step(i):
             pose_log[i, :, 0] = 1.0
+            last["out"] = (pose_log[i],)
 
         def begin_repeat(reset=False):
             pass
@@ -874,13 +910,19 @@ def main():
 
         ready = False if args.submit_order == "caller" else None
 
-        def step(i):
+        def forward_step(i):
             pair = pool[i % len(pool)]
             if args.no_graph:                            # the l0 pose-head kernel writes the log row itself
                 return net.forward(pair[:B], pair[B:], pose_out=pose_log[i])
             if args.inputs == "in-place":                # the lane's buffer holds its pair (filled before the timed region)
                 return net.submit(i % lanes, ready=ready)
             return net.submit(i % lanes, pair, ready=ready)   # step i rides lane i % lanes: one copy in (the stacked pair), graph replay
+
+        def step(i):
+            out = forward_step(i)
+            if i == args.steps - 1:                      # (the warm-up runs first: the timed loop's last step writes it last)
+                last["out"] = out
+            return out
 
         def begin_repeat(reset=False):
             if not args.no_graph:
@@ -945,7 +987,7 @@ def main():
     if group:
         dist.all_gather(gathered, pose_log[:args.steps].contiguous())     # untimed: RCCL sets its channels up on first use
     repeats, total = [], 0.0
-    while total < MIN_TIMED_S and len(repeats) < 200:
+    while not repeats or (args.full and total < MIN_TIMED_S and len(repeats) < 200):
         sync()
         if group:
             dist.barrier()
@@ -968,7 +1010,9 @@ def main():
         if dry:
             break
     assert torch.isfinite(pose_log[:args.steps]).all()
-    elapsed = statistics.median(repeats)
+    elapsed = repeats[0]                                  # the K timed steps; --full's further repeats only add the median
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"])
 
     line = {
         "metric": "frame-pairs/sec (KITTI 64x1800 range image)" if (H, W) == (64, 1800)
@@ -979,6 +1023,7 @@ def main():
         "warmup_requested": args.warmup,                  # `warmup` = max(--warmup, 2 per lane): every lane's graph has replayed twice
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "repeats": len(repeats), "ms_per_step_repeats": [round(r / args.steps * 1e3, 4) for r in repeats[:16]],
+        "ms_per_step_median": round(statistics.median(repeats) / args.steps * 1e3, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": ("f32 (1x1 convolutions as 3 fp16-MFMA products of hi/lo-split fp32 operands, fp32 accumulate%s)"
                   % ("; true-fp32 MFMA comparison build" if os.environ.get("ELO_DENSE_F32") == "1" else ""))
@@ -1003,7 +1048,7 @@ def main():
         # the fp16 split's production guard: every N-th replay of a lane ran on the range-checked kernels INSIDE the timed loop
         line["range_check"] = {"every_nth_replay": args.check_every, "violations": net.range_violations()}
         assert line["range_check"]["violations"] == 0
-    legs = not args.no_legs and not dry
+    legs = args.full and not args.no_legs and not dry
     if legs and args.train_steps > 0 and (H, W) == (64, 1800):
         train = train_dp_leg(args, dev, rank, world, dist, group)          # every rank takes part (one collective per step)
         line["train_dp"] = train
@@ -1039,7 +1084,7 @@ def main():
             line["hires"] = hires_leg(dev, lanes)
             if os.environ.get("ELO_DENSE_F32") != "1":
                 line["dense_f32"] = dense_f32_leg(args)
-    if group:                                         # every rank takes part; rank 0 reports
+    if group and args.full:                           # every rank takes part; rank 0 reports
         line["rccl"] = rccl_leg(dist, dev, backend, world, rank, pose_log[:args.steps].contiguous(), numa)
     if rank == 0:
         print(json.dumps(line), flush=True)

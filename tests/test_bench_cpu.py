@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["ELO_BENCH_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dry-run", "--steps", "5",
                           "--warmup", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -32,7 +32,7 @@ def test_bench_dry_run_with_eight_ranks():
     global batch and the rccl object carry the world size, and `warmup` / `warmup_requested` explain the driver's warm-up."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["ELO_BENCH_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry-run", "--steps", "20",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--dry-run", "--steps", "20",
                           "--warmup", "5", "--batch", "8"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -61,13 +61,30 @@ def test_bench_one_rank_process_group_rehearsal():
     environment, the collectives run on the world of one, the line carries the `rccl` object, n_gpus stays 1."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ELO_BENCH_FORCE_DIST="1", ELO_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "4", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dry-run", "--steps", "4", "--warmup", "1"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["config"]["parallelism"] == "dp1" and "launching" not in out.stderr
     r = d["rccl"]
     assert r["world_size"] == 1 and r["backend"] == "gloo" and r["all_reduce_us"] > 0 and r["all_gather_bytes"] == 4 * 7 * 4
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_its_outputs(tmp_path):
+    """Without --full: ONE timed repeat of exactly --steps steps (no further repeats, no rccl clocks even in a process group), and
+    --dump-outputs writes the last timed step's outputs as float32 .npy files."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(ELO_BENCH_FORCE_DIST="1", ELO_BENCH_BACKEND="gloo")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "6", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "out")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 6 and d["repeats"] == 1 and "rccl" not in d and "ms_per_step" in d
+    import numpy as np
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["out0.npy"], files
+    a = np.load(tmp_path / "out" / "out0.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 7) and a[0, 0] == 1.0
 
 
 RING_LOG = """\

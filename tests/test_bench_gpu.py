@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,7 @@ def _line(out):
 
 
 def test_bench_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "8", "--cpu-pairs", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "40", "--warmup", "8", "--cpu-pairs", "2",
                           "--train-steps", "2"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     d = _line(out)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -66,11 +67,35 @@ def test_bench_line_contract():
     assert t["n_gpus"] == 1 and t["value"] > 0 and t["batch_per_gpu"] == 8
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full: the contract keys from ONE timed repeat of exactly --steps steps, none of the --full legs, and
+    --dump-outputs writes the nine outputs of the last timed step (float32); a second run with the same arguments computes
+    the same poses (seeded inputs, weights and visiting orders)."""
+    dumps = []
+    for run in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "8",
+                              "--dump-outputs", str(tmp_path / str(run))], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        d = _line(out)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 30 and d["repeats"] == 1 and d["value"] > 0
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-3                             # B = 1
+        for leg in ("roofline", "cpu_baseline", "batch8", "from_raw_clouds", "hires", "dense_f32", "train_dp", "rccl"):
+            assert leg not in d, leg
+        dumps.append({f[:-4]: np.load(tmp_path / str(run) / f) for f in os.listdir(tmp_path / str(run))})
+    a, b = dumps
+    assert set(a) == {"l0_q_norm", "l0_t", "l1_q_norm", "l1_t", "l2_q_norm", "l2_t", "l3_q_norm", "l3_t", "l0_xyz_f1"}
+    for name, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), name
+        assert v.shape == b[name].shape and np.allclose(v, b[name], rtol=1e-5, atol=1e-6), name
+    assert a["l0_q_norm"].size == 4 and abs(float(np.linalg.norm(a["l0_q_norm"])) - 1.0) < 1e-4                  # B = 1
+
+
 def test_bench_gpus_2_launches_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["ELO_BENCH_BACKEND"] = "gloo"                    # two ranks on ONE GPU: RCCL would refuse the duplicate device
     env["ELO_BENCH_SHARE_GPU"] = "1"                     # (without it bench.py refuses --gpus 2 on a 1-GPU box)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "8",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "8",
                           "--lanes", "4", "--train-steps", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _line(out)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["value"] > 0
@@ -89,7 +114,7 @@ def test_bench_runs_its_distributed_path_through_rccl_as_one_rank(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ELO_BENCH_FORCE_DIST="1", NCCL_DEBUG="INFO", NCCL_DEBUG_SUBSYS="INIT,GRAPH,TUNING,COLL", NCCL_DEBUG_FILE=str(log),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "8", "--train-steps", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "8", "--train-steps", "2"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _line(out)
     assert d["n_gpus"] == 1 and d["value"] > 0

@@ -169,13 +169,12 @@ def test_tf_bundle_reader_round_trip_and_crc(tmp_path):
         assert np.array_equal(v.cpu().numpy(), state[k])
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/pretrained_model/pretrained_model.ckpt.index"),
-                    reason="the reference checkout is only present in the authoring container")
 def test_tf_bundle_reader_parses_the_reference_index():
-    """The reference ships the INDEX of its checkpoint (no data shard): every table block passes its crc32c, the
-    entries tile the data shard without gaps, and names/shapes equal the committed fixture."""
+    """The reference ships the INDEX of its checkpoint (no data shard; a copy is stored as tests/golden/pretrained_model.ckpt.index):
+    every table block passes its crc32c, the entries tile the data shard without gaps, and names/shapes equal the committed fixture."""
     tc = load_pkg("tf_checkpoint")
-    header, entries = tc.read_index("/root/reference/pretrained_model/pretrained_model.ckpt", verify=True)
+    prefix = os.path.join(GOLDEN, "pretrained_model.ckpt")
+    header, entries = tc.read_index(prefix, verify=True)
     assert header["num_shards"] == 1 and len(entries) == 1327
     spans = sorted((e.offset, e.size) for e in entries.values())
     assert spans[0][0] == 0 and all(a[0] + a[1] == b[0] for a, b in zip(spans, spans[1:]))
@@ -186,7 +185,7 @@ def test_tf_bundle_reader_parses_the_reference_index():
     for e in entries.values():
         assert e.size == int(np.prod(e.shape, dtype=np.int64)) * np.dtype(tc.DTYPES[e.dtype]).itemsize
     with pytest.raises(FileNotFoundError, match="ships only the .index"):
-        tc.load_checkpoint("/root/reference/pretrained_model/pretrained_model.ckpt", ["w_x"])
+        tc.load_checkpoint(prefix, ["w_x"])
 
 
 def test_data_augmentation_is_a_clipped_rigid_transform():

@@ -1,19 +1,23 @@
-"""CPU, authoring container only: the C restatement against the reference's own
-kernel bodies built for the host (oracle/_ref, see oracle/build_ref.sh), on a
-seeded random sweep that includes heavy exact-tie inputs.  Skipped where
-oracle/_ref has not been built (it cannot be built without /root/reference)."""
+"""CPU: the C restatement against the reference's own kernel bodies built for the host (oracle/_ref, see
+oracle/build_ref.sh), on a seeded random sweep that includes heavy exact-tie inputs.  The sweep's reference outputs are
+stored in tests/golden/ref_sweep.npz (tests/golden/make_ref_sweep.py), so the restatement is checked against them
+everywhere, and against the live build too where oracle/_ref has been built (it cannot be built without the reference
+checkout).  The tests of the contracted build need oracle/_ref and are skipped without it."""
 import math
+import os
 
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
 from oracle import grouping as G
 
-pytestmark = pytest.mark.skipif(not G.have_ref(), reason="oracle/_ref not built")
+SWEEP = os.path.join(GOLDEN, "ref_sweep.npz")
+OPS = (("random", G.fused_conv_random_k), ("select", G.fused_conv_select_k))
 
 
-@pytest.mark.parametrize("seed", range(40))
-def test_restatement_equals_reference_build(seed):
+def sweep_case(seed):
+    """The arguments (after the op) of sweep case `seed`."""
     rng = np.random.default_rng(seed)
     B = int(rng.integers(1, 3))
     H, W = int(rng.integers(1, 12)), int(rng.integers(6, 40))
@@ -35,11 +39,21 @@ def test_restatement_equals_reference_build(seed):
     perm = rng.permutation(kH * kW).astype(np.int32)
     dist = float(rng.choice([0.5, 2.0, 5.0, 1000.0]))
     fc = int(rng.integers(0, 2))
-    for fn in (G.fused_conv_random_k, G.fused_conv_select_k):
-        a = fn(xyz1, xyz2, idx, perm, H, W, N, kH, kW, K, fc, dist, sh, sw, impl="oracle")
-        b = fn(xyz1, xyz2, idx, perm, H, W, N, kH, kW, K, fc, dist, sh, sw, impl="ref")
-        for x, y in zip(a, b):
-            assert np.array_equal(x, y)
+    return xyz1, xyz2, idx, perm, H, W, N, kH, kW, K, fc, dist, sh, sw
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_restatement_equals_reference_build(seed):
+    args = sweep_case(seed)
+    stored = np.load(SWEEP)
+    for op, fn in OPS:
+        a = fn(*args, impl="oracle")
+        for j, x in enumerate(a):
+            assert np.array_equal(x, stored["%d/%s/%d" % (seed, op, j)]), (op, j)
+        if G.have_ref():
+            b = fn(*args, impl="ref")
+            for x, y in zip(a, b):
+                assert np.array_equal(x, y)
 
 
 @pytest.mark.skipif(not G.have_ref_fma(), reason="oracle/_ref/libelo_ref_fma.so not built")

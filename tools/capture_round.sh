@@ -1,6 +1,6 @@
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/r02_final; mkdir -p $OUT
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_8lanes -o t -- python $REPO/bench.py --steps 200 --warmup 16 --no-legs > $OUT/trace_8lanes.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_1lane -o t -- python $REPO/bench.py --steps 200 --warmup 16 --no-legs --lanes 1 > $OUT/trace_1lane.log 2>&1

@@ -7,7 +7,7 @@
 #    kernel (tools/rr_clock.sh) and the MFMA / VALU co-execution microbenchmark (tools/micro/coexec.hip).
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/r03; mkdir -p $OUT
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 python tools/cv1_variants.py --levels l0,l1,l2,full725 --batches 1,8 2>/dev/null | grep "^{" > $OUT/cv1_variants.txt
 python tools/parity_flips.py > $OUT/parity_flips.txt 2>/dev/null
 cd /tmp; export TMPDIR=/tmp

@@ -4,7 +4,7 @@
 #   trace + counter passes, the SQ instruction budget of a batch-8 forward, the parity statistic with its ATTRIBUTED flips, training.
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/r05/final; mkdir -p $OUT
-python bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 python tools/parity_flips.py > $OUT/parity_flips.txt 2>/dev/null
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_8lanes -o t -- python $REPO/bench.py --steps 200 --warmup 16 --no-legs > $OUT/trace_8lanes.log 2>&1

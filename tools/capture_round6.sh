@@ -6,7 +6,7 @@
 #   the streaming ceiling of this box (tools/micro/hbm_probe); training step time + kernel histogram; the parity statistic.
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/r06/final; mkdir -p $OUT
-python bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 python tools/parity_flips.py > $OUT/parity_flips.txt 2>/dev/null
 for dt in "" "--half"; do python tools/cold_sweep.py $dt > $OUT/cold_sweep${dt:+_f16}.txt 2>&1; done
 python tools/cold_sweep.py --half --grid 16x225 > $OUT/cold_sweep_f16_16x225.txt 2>&1
