@@ -216,6 +216,9 @@ SYMBOLS = [
     ("elo_cv_stage1_setconv_chain_form", ctypes.c_int, [ctypes.POINTER(Cv1Args), ctypes.POINTER(SetconvArgs), ctypes.POINTER(SetconvArgs)]),
     ("elo_cv_stage1_setconv_chain", ctypes.c_int, [ctypes.POINTER(Cv1Args), ctypes.POINTER(SetconvArgs), ctypes.POINTER(SetconvArgs), _vp]),
     ("elo_cv_stage2_fused", ctypes.c_int, [ctypes.POINTER(Cv2Args), _vp]),
+    ("elo_debug_upconv_ride_launches", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]),
+    ("elo_cv_stage2_upconv_form", ctypes.c_int, [ctypes.POINTER(Cv2Args), ctypes.POINTER(MlpArgs), ctypes.POINTER(MlpArgs)]),
+    ("elo_cv_stage2_upconv_fused", ctypes.c_int, [ctypes.POINTER(Cv2Args), ctypes.POINTER(MlpArgs), ctypes.POINTER(MlpArgs), _vp]),
     ("elo_cv_stage1_setconv_fused", ctypes.c_int, [ctypes.POINTER(Cv1Args), ctypes.POINTER(SetconvArgs), ctypes.POINTER(SetconvArgs), _vp]),
 ]
 

@@ -2687,16 +2687,15 @@ __global__ __launch_bounds__(ELO_BLOCK, 2) void setconv_narrow_kernel(const elo_
 // LDS columns: [0,64) grouped cost, [64,128) xyz-encoding, [128,128+C) feat1, [192,208) xyz_cat;
 // sum_cost0 reads [0,128+C) and writes [64,192); sum_cost1 maps [64,192) -> [64,128).
 template <int TILE, int MODE>
-__global__ __launch_bounds__(FUSED_BLOCK, TILE == 32 ? ELO_TILE32_WAVES : ELO_TILE_WAVES) void cv2_kernel(const elo_cv2_args a, const int S)   // (32 rows at 6 waves: 4 VGPRs spilled to scratch)
+__device__ __forceinline__ void cv2_tile(const elo_cv2_args &a, const int S, float *lds, unsigned block, unsigned nblocks)
 {
-    extern __shared__ __align__(16) float lds[];
     float *act = lds;
     const TileMeta meta = tile_meta(lds, TILE, S);
     const int tid = threadIdx.x;
     const int K = a.K, P = TILE / K, C = a.C, f16 = a.feat_dtype == ELO_F16;
     unsigned bad = 0;
     const long total_points = (long)a.batch * a.npoints;
-    const long first_point = (long)xcd_tile(blockIdx.x, gridDim.x) * P;
+    const long first_point = (long)xcd_tile(block, nblocks) * P;
     if (first_point >= total_points) return;
     if (a.group.random_hw) {                          // random-k of the warped cloud on itself (:106-108)
         int *lds_off = reinterpret_cast<int *>(meta.cxyz + 128);
@@ -2731,6 +2730,43 @@ __global__ __launch_bounds__(FUSED_BLOCK, TILE == 32 ? ELO_TILE32_WAVES : ELO_TI
     dense_pf<TILE, 64, 0, MODE>(act, S, 64, to_pool(64), a.sum_cost1, p64, nullptr, nullptr, bad);       // -> 64 logits at [64,128)
     pool_masked_softmax(act, S, 64, 0, meta, P, K, first_point, total_points, a.out, f16);   // :137-146
     report_violations<MODE>(bad, a.range_counter);
+}
+
+template <int TILE, int MODE>
+__global__ __launch_bounds__(FUSED_BLOCK, TILE == 32 ? ELO_TILE32_WAVES : ELO_TILE_WAVES) void cv2_kernel(const elo_cv2_args a, const int S)   // (32 rows at 6 waves: 4 VGPRs spilled to scratch)
+{
+    extern __shared__ __align__(16) float lds[];
+    cv2_tile<TILE, MODE>(a, S, lds, blockIdx.x, gridDim.x);
+}
+
+// ---- heterogeneous launch: cost-volume stage 2 and the level's two set-upconv stage-2 MLPs in ONE grid ------------------
+// The set-upconvs' second stage ([pooled | points1] -> 128 -> 64, pointnet_util.py:300-310) reads only their stage-1 output,
+// which the launch in front of this one wrote; the flow predictors behind them are the first consumers of the cost.  So the
+// set-upconv MLPs ride here, next to the cost-volume tiles, and the predictor launch (mlp_sv_kernel) keeps only its own two
+// layers on the level's critical path.  The first n_cv workgroups run cost-volume tiles, the rest one MLP row tile of job
+// j each (stage 1 only: `out` goes to HBM from the accumulators, as the fused two-stage launch writes it).
+struct MlpSideJobs {
+    elo_mlp_args job[2];
+    int S, blocks_per_job;
+};
+
+template <int TILE_CV, int TILE_MLP, int MODE>
+__global__ __launch_bounds__(FUSED_BLOCK, TILE_CV == 32 || TILE_MLP == 32 ? ELO_TILE32_WAVES : ELO_TILE_WAVES)
+void cv2_upconv_kernel(const elo_cv2_args a, const int S, const unsigned n_cv, const MlpSideJobs side)
+{
+    extern __shared__ __align__(16) float lds[];
+    if (blockIdx.x < n_cv) {
+        cv2_tile<TILE_CV, MODE>(a, S, lds, blockIdx.x, n_cv);
+    } else {
+        const unsigned r = blockIdx.x - n_cv;
+        const unsigned j = r / (unsigned)side.blocks_per_job;         // uniform: one scalar index into the kernarg block
+        const elo_mlp_args &m = side.job[j];
+        const long first = (long)xcd_tile(r - j * (unsigned)side.blocks_per_job, (unsigned)side.blocks_per_job) * TILE_MLP;
+        if (first >= m.rows) return;
+        unsigned bad = 0;
+        mlp_tile<TILE_MLP, MODE>(m, lds, side.S, first, m.rows, false, bad);
+        report_violations<MODE>(bad, m.range_counter);
+    }
 }
 
 // A 16-row tile halves the serial work per workgroup and doubles their number: take it whenever the
@@ -2992,6 +3028,13 @@ extern "C" int elo_debug_chain_pair_launches(unsigned long long *count, int rese
     if (reset) g_chain_pair_launches.store(0);
     return ELO_OK;
 }
+static std::atomic<unsigned long long> g_upconv_ride_launches;  // cv2_upconv_kernel (elo_cv_stage2_upconv_fused)
+extern "C" int elo_debug_upconv_ride_launches(unsigned long long *count, int reset)
+{
+    if (count) *count = g_upconv_ride_launches.load();
+    if (reset) g_upconv_ride_launches.store(0);
+    return ELO_OK;
+}
 static std::atomic<unsigned long long> g_sv_ride_launches;    // mlp_sv_kernel (elo_mlp_args.sv_*)
 extern "C" int elo_debug_sv_ride_launches(unsigned long long *count, int reset)
 {
@@ -3168,6 +3211,18 @@ static int mlp_cols(const elo_mlp_args *a, int in_width)
     return cols;
 }
 
+// the regime (products mode, rows per launch) in which elo_mlp_fused2 takes the register-resident chain for the model's
+// two-stage shape; the other conditions are the shape's (plan_mlp)
+static bool mlp_chain_regime(long rows, bool pair, int batch_hint, int mode)
+{
+#ifdef ELO_DENSE_F32
+    (void)rows; (void)pair; (void)batch_hint; (void)mode;
+    return false;
+#else
+    return (mode == MODE_SPLIT || mode == MODE_HALF) && cv1_rr_on() && rows * (pair ? 2 : 1) >= mlp_rr_rows(batch_hint);
+#endif
+}
+
 // everything elo_mlp_fused2 decides before it launches
 struct MlpPlan { int S, mode, C; bool t16, chain; int sv_tiles; };     // sv_tiles: row tiles per batch element of the softmax_valid ride (0: none)
 
@@ -3202,16 +3257,15 @@ static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, co
     {   // the register-resident form (mlp2_rr_kernel) for the model's two-stage shape, from ELO_MLP_RR_ROWS rows per launch on
         // two regimes (fused._prepass_rows): batch >= 4 keeps the GPU full -- 24.0 k -> 25.5 k pairs/s at batch 8 with the chain at
         // every level; at batch 1 (7200 rows at l0) the tile kernel is faster: 10.2 k vs 9.8 k
-        const long min_rows = mlp_rr_rows(a->batch_hint);
         const int C = p->C;
         const bool aligned = ((uintptr_t)a->src[0] | (uintptr_t)a->src[1] | (uintptr_t)a->before | (uintptr_t)a->after | (uintptr_t)a->out |
                               (uintptr_t)a->out2) % 16 == 0 &&
                              (!b || ((uintptr_t)b->src[0] | (uintptr_t)b->src[1] | (uintptr_t)b->before | (uintptr_t)b->after | (uintptr_t)b->out |
                                      (uintptr_t)b->out2) % 16 == 0);
-        p->chain = (p->mode == MODE_SPLIT || p->mode == MODE_HALF) && cv1_rr_on() && a->n_sources == 2 && a->src_width[0] == 64 &&
+        p->chain = a->n_sources == 2 && a->src_width[0] == 64 &&
                    (C == 16 || C == 32 || C == 64) && a->n_layers == 2 && a->layers[0].N == 128 && a->layers[1].N == 64 && a->n_layers2 == 2 &&
                    a->layers2[0].N == 128 && a->layers2[1].N == 64 && a->w_before == C && a->w_after == 64 && aligned &&
-                   a->rows * (b ? 2 : 1) >= min_rows;
+                   mlp_chain_regime(a->rows, b != nullptr, a->batch_hint, p->mode);
     }
 #endif
     // the softmax_valid ride (elo_mlp_args.sv_*): tile kernel, 64-wide final output, whole tiles per batch element
@@ -3505,9 +3559,8 @@ extern "C" int elo_cv_stage1_setconv_chain(const elo_cv1_args *a, const elo_setc
 #endif
 }
 
-extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream)
+static int plan_cv2(const elo_cv2_args *a, TilePlan *p, const char *who)
 {
-    const char *who = "elo_cv_stage2_fused";
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->batch >= 0 && a->npoints > 0 && a->K > 0 && a->H > 0 && a->W > 0 && a->C > 0, who, "bad sizes");
     ELO_REQUIRE(a->npoints == a->H * a->W, who, "npoints must equal H*W (every pixel is a centre)");
@@ -3522,21 +3575,33 @@ extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream)
     if (int rc = check_dense(a->sum_cost1, 128, 64, who, "sum_cost_volume_1")) return rc;
     const long points = (long)a->batch * a->npoints;
     if (points >= 0x7fffffffL) return fail(ELO_ERR_LIMIT, "%s: batch * npoints beyond 2^31", who);
+    p->units = 0;
     if (points == 0) return ELO_OK;
-    const int S = row_stride(208);
+    p->S = row_stride(208);
     const int P32 = 32 / a->K, P16 = a->K <= 16 ? 16 / a->K : 1;
     const long u32 = (points + P32 - 1) / P32, u16 = (points + P16 - 1) / P16;
-    int mode = 0;
-    if (int rc = products_mode(who, &mode, a->xyz_enc, a->sum_cost0, a->sum_cost1)) return rc;
-    const bool t16 = small_tile(u32, a->K);
+    if (int rc = products_mode(who, &p->mode, a->xyz_enc, a->sum_cost0, a->sum_cost1)) return rc;
+    p->t16 = small_tile(u32, a->K);
+    p->units = p->t16 ? u16 : u32;
     const int KT = a->group.random_hw ? a->group.kernel_h * a->group.kernel_w : 0;
-    const size_t lds = tile_lds_bytes(t16 ? 16 : 32, S, KT, false);
-    if (int rc = check_group(a->group, a->H, a->W, lds, who)) return rc;
+    p->lds = tile_lds_bytes(p->t16 ? 16 : 32, p->S, KT, false);
+    return check_group(a->group, a->H, a->W, p->lds, who);
+}
+
+extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_cv_stage2_fused";
+    TilePlan plan;
+    if (int rc = plan_cv2(a, &plan, who)) return rc;
+    if (plan.units == 0) return ELO_OK;
+    const int S = plan.S, mode = plan.mode;
+    const bool t16 = plan.t16;
+    const size_t lds = plan.lds;
     hipStream_t s = (hipStream_t)stream;
 #ifndef ELO_DENSE_F32
     if (!a->group.random_hw && cv_chain(a->C, mode)) {
         const int P = RR_ROWS / a->K;                              // points per workgroup (128 rows)
-        const dim3 rgrid((unsigned)((points + P - 1) / P));
+        const dim3 rgrid((unsigned)(((long)a->batch * a->npoints + P - 1) / P));
         const bool f16 = a->feat_dtype == ELO_F16;
 #define RR(CC)                                                                                                           \
         do {                                                                                                             \
@@ -3553,9 +3618,69 @@ extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream)
         return check_launch(who);
     }
 #endif
-    const dim3 grid((unsigned)(t16 ? u16 : u32));
+    const dim3 grid((unsigned)plan.units);
 #define CALL(k) hipLaunchKernelGGL(k, grid, dim3(FUSED_BLOCK), lds, s, *a, S)
     ELO_PICK(cv2_kernel, t16, mode, CALL);
 #undef CALL
+    return check_launch(who);
+}
+
+// Cost-volume stage 2 (tile kernel) and the level's two set-upconv stage-2 MLPs (stage-1-only elo_mlp_args: n_layers2 = 0, no
+// clear_* / sv_* side jobs) in ONE launch (cv2_upconv_kernel): the bits of elo_cv_stage2_fused + elo_mlp_fused2(ja, jb).  Taken
+// only where both are tile kernels: the cost volume groups in the kernel (or its chain form is off) and the pair of two-stage
+// MLPs these jobs would otherwise begin is below the chain kernel's regime (the predictor launch behind them is then a tile
+// kernel too).  upconv_ride_plan: ELO_OK when the form applies, else the reason.
+static int upconv_ride_plan(const elo_cv2_args *a, const elo_mlp_args *ja, const elo_mlp_args *jb, TilePlan *pc, MlpPlan *pm,
+                            const char *who)
+{
+    if (int rc = plan_cv2(a, pc, who)) return rc;
+    ELO_REQUIRE(ja && jb, who, "two set-upconv jobs");
+    if (int rc = plan_mlp(ja, jb, pm, who)) return rc;
+    if (pc->units == 0 || ja->rows == 0) return fail(ELO_ERR_ARG, "%s: empty cost volume or jobs (call the separate entry points)", who);
+    for (const elo_mlp_args *j : {ja, jb})
+        if (j->n_layers2 != 0 || j->clear_scratch || j->sv_scratch)
+            return fail(ELO_ERR_ARG, "%s: the set-upconv jobs are one-stage MLPs without side jobs", who);
+    if (pm->mode != pc->mode) return fail(ELO_ERR_ARG, "%s: the cost volume and the MLP jobs must share one products mode", who);
+#ifndef ELO_DENSE_F32
+    if (!a->group.random_hw && cv_chain(a->C, pc->mode)) return fail(ELO_ERR_ARG, "%s: the cost volume takes its chain form", who);
+#endif
+    if (mlp_chain_regime(ja->rows, true, ja->batch_hint, pm->mode))
+        return fail(ELO_ERR_ARG, "%s: the set-upconv / predictor pair is in the chain kernel's regime", who);
+    return ELO_OK;
+}
+
+extern "C" int elo_cv_stage2_upconv_form(const elo_cv2_args *a, const elo_mlp_args *ja, const elo_mlp_args *jb)
+{
+    TilePlan pc;
+    MlpPlan pm;
+    return upconv_ride_plan(a, ja, jb, &pc, &pm, "elo_cv_stage2_upconv_form") == ELO_OK ? 1 : 0;
+}
+
+extern "C" int elo_cv_stage2_upconv_fused(const elo_cv2_args *a, const elo_mlp_args *ja, const elo_mlp_args *jb, elo_stream_t stream)
+{
+    const char *who = "elo_cv_stage2_upconv_fused";
+    TilePlan pc;
+    MlpPlan pm;
+    if (int rc = upconv_ride_plan(a, ja, jb, &pc, &pm, who)) return rc;
+    MlpSideJobs side;
+    side.job[0] = *ja;
+    side.job[1] = *jb;
+    side.S = pm.S;
+    const int tm = pm.t16 ? 16 : 32;
+    side.blocks_per_job = (int)((ja->rows + tm - 1) / tm);
+    const unsigned n_cv = (unsigned)pc.units;
+    const dim3 grid(n_cv + 2u * (unsigned)side.blocks_per_job);
+    const size_t lm = tile_lds_bytes(tm, pm.S), lds = pc.lds > lm ? pc.lds : lm;
+    const int S = pc.S;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL_T(M) do {                                                                                                  \
+        if (pc.t16 && pm.t16) hipLaunchKernelGGL((cv2_upconv_kernel<16, 16, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);      \
+        else if (pc.t16) hipLaunchKernelGGL((cv2_upconv_kernel<16, 32, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);           \
+        else if (pm.t16) hipLaunchKernelGGL((cv2_upconv_kernel<32, 16, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);           \
+        else hipLaunchKernelGGL((cv2_upconv_kernel<32, 32, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);                        \
+    } while (0)
+    ELO_PICK_MODE(pc.mode, CALL_T);
+#undef CALL_T
+    ++g_upconv_ride_launches;
     return check_launch(who);
 }

@@ -358,10 +358,13 @@ def mlp(sources, layers, clear=None, sv=None):
     return out.reshape(sources[0].shape[:-1] + (layers[-1].N,))
 
 
-def mlp_pair(sources_a, layers_a, sources_b, layers_b):
-    """Two row-wise MLPs of identical shape in ONE launch."""
+def mlp_pair(sources_a, layers_a, sources_b, layers_b, clear=None, sv=None):
+    """Two row-wise MLPs of identical shape in ONE launch.  `clear`, `sv`: as for mlp2_pair (out_a are the logits, out_b the
+    features)."""
     a, out_a, _ka = _mlp_args(sources_a, layers_a)
     b, out_b, _kb = _mlp_args(sources_b, layers_b)
+    if _ride_sv(a, b, sv, out_a.dtype) or sv is None:
+        _ride_clear(a, clear, out_a.dtype)
     L.call2("elo_mlp_fused2", a, b, out_a)
     lead = sources_a[0].shape[:-1]
     return out_a.reshape(lead + (layers_a[-1].N,)), out_b.reshape(lead + (layers_b[-1].N,))
@@ -560,10 +563,14 @@ def cv_stage1_alone(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2
         _RECORD = keep
 
 
-def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group=None, K=None):
+def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group=None, K=None, side=None):
+    """Cost-volume stage 2 in one launch.  `side`: the two set-upconv stage-2 MLPs of the level (dicts of mlp() arguments:
+    sources, layers; same shape) -- run INSIDE this launch where both are tile kernels (below THROUGHPUT_BATCH, in-kernel
+    grouping, the pair below the chain kernel's rows: elo_cv_stage2_upconv_fused); the call then returns (out, [out_a, out_b]),
+    or (out, None) where they cannot ride and the caller runs them itself."""
     L.require_gpu(xyz1_proj, feat1_proj, cost_proj, idx, mask)
     if _RECORD is not None:
-        _record(2, (xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1), dict(group=group, K=K))
+        _record(2, (xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1), dict(group=group, K=K, side=side))
     xyz1_proj = _f32c(xyz1_proj)
     (feat1_proj, cost_proj), dt, code = _features(feat1_proj, cost_proj)
     B, H, W, C = feat1_proj.shape
@@ -579,5 +586,13 @@ def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, s
     a = L.Cv2Args(B, N, K, H, W, C, xyz1_proj.data_ptr(), feat1_proj.data_ptr(), cost_proj.data_ptr(), ptr(idx),
                   ptr(mask), xyz_enc.struct(), sum_cost0.struct(), sum_cost1.struct(), out.data_ptr(),
                   group.struct(B, N, K, xyz1_proj.device) if group is not None else _NO_GROUP, code)
+    if side:
+        if B < THROUGHPUT_BATCH:
+            jobs = [_mlp_args(**job) for job in side]                   # (args, out, keep-alive)
+            if L.lib().elo_cv_stage2_upconv_form(ctypes.byref(a), ctypes.byref(jobs[0][0]), ctypes.byref(jobs[1][0])) == 1:
+                L.call3("elo_cv_stage2_upconv_fused", a, jobs[0][0], jobs[1][0], out)
+                return out, [j[1].reshape(job["sources"][0].shape[:-1] + (j[1].shape[-1],)) for j, job in zip(jobs, side)]
+        L.call("elo_cv_stage2_fused", a, out)
+        return out, None
     L.call("elo_cv_stage2_fused", a, out)
     return out

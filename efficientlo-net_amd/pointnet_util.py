@@ -146,11 +146,14 @@ def _split_conv(parts, num_output_channels, scope, is_training, bn_decay, bn=Tru
 @_storage_boundary("points1_proj", "points2_proj")
 def cost_volume(warped_xyz1_proj, xyz2_proj, points1_proj, points2_proj, kernel_size1, kernel_size2, nsample,
                 nsample_q, distance, mlp1, mlp2, is_training, bn_decay, scope, bn=True, pooling='max', knn=True,
-                corr_func='elementwise_product', side_jobs=None, side_chain=False):
+                corr_func='elementwise_product', side_jobs=None, side_chain=False, upconv=None):
     """Attentive cost volume, utils/pointnet_util.py:33-149.  Returns (B, H*W, mlp2[-1]).
     `side_jobs` (fused inference path only): one or two set-conv jobs (fused.setconv keyword dicts) that only share
     inputs with this cost volume; they run inside stage 1's launch and the call returns (cost, [(out, new_xyz), ...]).
-    `side_chain`: they ride only on the chain form of stage 1 (fused.cv_stage1); else the second element is None."""
+    `side_chain`: they ride only on the chain form of stage 1 (fused.cv_stage1); else the second element is None.
+    `upconv` (fused inference path only): a function of stage 1's side output (the list above, or None) that returns the two
+    set-upconv stage-2 MLP jobs of the level (up_conv_stage2_jobs) or None; they ride on stage 2's launch where they can
+    (fused.cv_stage2) and the call returns (cost, side output or None, [out_a, out_b] or None)."""
     with tf_util.variable_scope(scope):
         B, H, W, _ = warped_xyz1_proj.shape
         N = H * W
@@ -177,13 +180,17 @@ def cost_volume(warped_xyz1_proj, xyz2_proj, points1_proj, points2_proj, kernel_
             pi_feat1_new, side_out = stage1 if side_jobs else (stage1, None)
             pi_feat1_new = pi_feat1_new.reshape(B, H, W, -1)
             order = list(range(64 + C, 128 + C)) + list(range(64)) + list(range(64, 64 + C))   # [grouped | enc | feat1]
-            cost = fused.cv_stage2(warped_xyz1_proj, points1_proj, pi_feat1_new, None, None,
-                                   P('sum_xyz_encoding', 10, 64), P('sum_cost_volume_0', 128 + C, 128, row_order=order),
-                                   P('sum_cost_volume_1', 128, 64),
-                                   group=fused.Grouping(random_HW_p, kernel_size1, distance), K=nsample)   # :104-146
+            layers2 = (P('sum_xyz_encoding', 10, 64), P('sum_cost_volume_0', 128 + C, 128, row_order=order),
+                       P('sum_cost_volume_1', 128, 64))
+            up_jobs = upconv(side_out) if upconv is not None else None          # (its layers after this operator's)
+            cost = fused.cv_stage2(warped_xyz1_proj, points1_proj, pi_feat1_new, None, None, *layers2,
+                                   group=fused.Grouping(random_HW_p, kernel_size1, distance), K=nsample, side=up_jobs)   # :104-146
+            cost, up_out = cost if up_jobs else (cost, None)
+            if upconv is not None:
+                return cost, side_out, up_out
             return (cost, side_out) if side_jobs else cost
-        if side_jobs:
-            raise NotImplementedError("side_jobs ride on the fused cost-volume launch only")
+        if side_jobs or upconv is not None:
+            raise NotImplementedError("side_jobs / upconv ride on the fused cost-volume launches only")
 
         # ---- stage 1: point -> patch in frame 2 (:47-100)
         idx_hw = get_hw_idx(B, H, W, dev)
@@ -361,26 +368,61 @@ def up_conv_stage1_jobs(up_a, up_b):
     return jobs
 
 
-def up_conv_predict_finish(up_a, up_b, fp_a, fp_b, up_a_pooled, up_b_pooled, clear=None, sv=None):
+def _up_stage2(up):
+    """(points1 (B, H*W, C), the stage-2 layers) of a set-upconv (pointnet_util.py:300-310)."""
+    P = fused.packed_layer
+    with tf_util.variable_scope(up["scope"]):
+        feat1_proj, mlp, mlp2 = up["feat1_proj"], up["mlp"], up["mlp2"]
+        B, H, W, _ = up["xyz1_proj"].shape
+        points1 = feat1_proj.reshape(B, H * W, -1)
+        w2 = [mlp[-1] + points1.shape[-1]] + list(mlp2)
+        return points1, [P('up_2_%d' % i, w2[i], w2[i + 1]) for i in range(len(mlp2))]
+
+
+def _predictor(up, fp, w_after=None):
+    """(before, after, layers) of the flow predictor a set-upconv feeds: its first layer packed for the columns
+    [set-upconv output | before | after] (fused.stage2_row_order).  `w_after`: after's width where fp has no cost_volume yet."""
+    P = fused.packed_layer
+    with tf_util.variable_scope(fp["scope"]):
+        before, after = fp["points_f1"], fp.get("cost_volume")
+        w_before = before.shape[-1] if before is not None else 0
+        w_after = after.shape[-1] if after is not None else (w_after or 0)
+        wp = [w_before + w_after + up["mlp2"][-1]] + list(fp["mlp"])
+        return before, after, [P('conv_predictor%d' % i, wp[i], wp[i + 1], bn=fp.get("bn", True),
+                                 row_order=fused.stage2_row_order(w_before, up["mlp2"][-1], w_after) if i == 0 else None)
+                               for i in range(len(fp["mlp"]))]
+
+
+def up_conv_stage2_jobs(up_a, up_b, fp_a, fp_b, up_a_pooled, up_b_pooled, w_cost):
+    """Stage 2 of the two set-upconvs of a level ([pooled | points1] -> mlp2) as fused.mlp job dicts (sources, layers): for the
+    level's cost-volume stage 2 to carry (cost_volume(upconv=...)): they only read stage 1's output, so they leave the
+    predictors' critical path.  The predictors' layers (fp_x without cost_volume; w_cost: its width) are made here too, in
+    up_conv_predict_finish's order: a fresh store creates the same variables."""
+    jobs = []
+    for up, fp, pooled in ((up_a, fp_a, up_a_pooled), (up_b, fp_b, up_b_pooled)):
+        points1, layers = _up_stage2(up)
+        _predictor(up, fp, w_after=w_cost)
+        jobs.append(dict(sources=[pooled, points1], layers=layers))
+    return jobs
+
+
+def up_conv_predict_finish(up_a, up_b, fp_a, fp_b, up_a_pooled, up_b_pooled, clear=None, sv=None, up_out=None):
     """Stage 2 of both set-upconvs and the two flow predictors they feed, in ONE launch (see up_conv_predict_pair).
-    `sv`: an _ops.SvPartials: predictor a's output are softmax_valid's logits, predictor b's its features (fused.mlp2_pair)."""
+    `sv`: an _ops.SvPartials: predictor a's output are softmax_valid's logits, predictor b's its features (fused.mlp2_pair).
+    `up_out`: [out_a, out_b] when the set-upconvs' stage 2 already ran (on the cost volume's stage-2 launch,
+    up_conv_stage2_jobs): then the launch runs the predictors alone on [out | points_f1 | cost] (fused.mlp_pair) -- the same
+    columns, the same bits."""
+    if up_out is not None:
+        specs = []
+        for up, fp, out in ((up_a, fp_a, up_out[0]), (up_b, fp_b, up_out[1])):
+            before, after, layers2 = _predictor(up, fp)
+            specs.append(([p for p in (out, before, after) if p is not None], layers2))
+        pred_a, pred_b = fused.mlp_pair(specs[0][0], specs[0][1], specs[1][0], specs[1][1], clear=clear, sv=sv)
+        return up_out[0], pred_a, up_out[1], pred_b
     stage2 = []
     for up, fp, pooled in ((up_a, fp_a, up_a_pooled), (up_b, fp_b, up_b_pooled)):
-        P = fused.packed_layer
-        with tf_util.variable_scope(up["scope"]):
-            feat1_proj, mlp, mlp2 = up["feat1_proj"], up["mlp"], up["mlp2"]
-            B, H, W, _ = up["xyz1_proj"].shape
-            points1 = feat1_proj.reshape(B, H * W, -1)
-            w2 = [mlp[-1] + points1.shape[-1]] + list(mlp2)
-            layers = [P('up_2_%d' % i, w2[i], w2[i + 1]) for i in range(len(mlp2))]
-        with tf_util.variable_scope(fp["scope"]):
-            before, after = fp["points_f1"], fp["cost_volume"]
-            wp = [sum(p.shape[-1] for p in (before, after) if p is not None) + mlp2[-1]] + list(fp["mlp"])
-            w_before = before.shape[-1] if before is not None else 0
-            w_after = after.shape[-1] if after is not None else 0
-            layers2 = [P('conv_predictor%d' % i, wp[i], wp[i + 1], bn=fp.get("bn", True),
-                         row_order=fused.stage2_row_order(w_before, mlp2[-1], w_after) if i == 0 else None)
-                       for i in range(len(fp["mlp"]))]
+        points1, layers = _up_stage2(up)
+        before, after, layers2 = _predictor(up, fp)
         stage2.append(dict(sources=[pooled, points1], layers=layers, before=before, after=after, layers2=layers2))
     (out_a, pred_a), (out_b, pred_b) = fused.mlp2_pair(stage2[0], stage2[1], clear=clear, sv=sv)
     return out_a, pred_a, out_b, pred_b

@@ -30,6 +30,7 @@ _HOST = {
     "chain_pair": ("ELO_CHAIN_PAIR", lambda v: v != "0", True),               # cost-volume stage 1 + the level's set-upconv stage 1 as ONE chain-kernel launch where both are chain forms
     "native_submit": ("ELO_NATIVE_SUBMIT", lambda v: v != "0", True),         # a lane submit as ONE C call (copy + hipGraphLaunch on the raw exec handle) instead of torch's copy_ + replay()
     "sv_ride": ("ELO_SV_RIDE", lambda v: v != "0", True),                     # softmax_valid's partial sums ride on the launch that produces its inputs (one launch less per level)
+    "upconv_ride": ("ELO_UPCONV_RIDE", lambda v: v != "0", True),             # a level's set-upconv stage 2 rides on its cost-volume stage-2 launch; the predictor launch keeps its own layers only
     "train_kernels": ("ELO_TRAIN_KERNELS", lambda v: v != "0", True),
     "train_dense": ("ELO_TRAIN_DENSE", lambda v: v != "0", True),             # a training layer's two products (x W + b with the batch moments, dz W^T) on elo_dense_rows instead of the library GEMM ...
     "train_dense_rows": ("ELO_TRAIN_DENSE_ROWS", int, 25000),                 # ... from this many rows on for x W + b (below: one macro-block per wave, the library + elo_bn_stats are faster: tools/dense_rows_micro.py)

@@ -826,6 +826,7 @@ int elo_debug_rr_rows(long setconv_rows, long mlp_rows);
 int elo_debug_rr_launches(unsigned long long *counts4, int reset);
 int elo_debug_sv_ride_launches(unsigned long long *count, int reset);     /* ... and of mlp_sv_kernel (elo_mlp_args.sv_*) */
 int elo_debug_chain_pair_launches(unsigned long long *count, int reset);  /* ... and of cv1_setconv_rr_kernel (elo_cv_stage1_setconv_chain) */
+int elo_debug_upconv_ride_launches(unsigned long long *count, int reset); /* ... and of cv2_upconv_kernel (elo_cv_stage2_upconv_fused) */
 /* the two narrow set-conv layers of the pyramid (6 -> 8 -> 8 -> 16 and 19 -> 16 -> 16 -> 32, K = 32; elo_setconv_fused with
  * elo_dense.w_plain given): 1 = setconv_narrow_kernel, the MLP on the matrix cores, for the 19-channel layer (the default;
  * also ELO_SETCONV_NARROW_MFMA; the 6-channel layer stays on the VALU kernel: slower on the matrix cores, measured), 0 =
@@ -869,6 +870,14 @@ typedef struct elo_cv2_args {
                                           * elo_range_violations() */
 } elo_cv2_args;
 int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream);
+/* elo_cv_stage2_fused AND the two set-upconv stage-2 MLPs of the level (elo_mlp_fused2(ja, jb) semantics; one-stage jobs:
+ * n_layers2 = 0, no clear_* / sv_* side jobs) in ONE launch: the first workgroups run cost-volume tiles, the rest MLP row
+ * tiles of ja, then jb.  The set-upconvs read only the stage-1 output of the launch in front, so they leave the critical
+ * path of the predictors, which then run on [out | points_f1 | cost] alone.  Tile-kernel form only: the cost volume groups in
+ * the kernel and the two-stage pair these jobs would begin is below the chain kernel's rows (elo_mlp_fused2).
+ * elo_cv_stage2_upconv_form: 1 when the launch takes them (else the separate entry points).  Same results bit for bit. */
+int elo_cv_stage2_upconv_form(const elo_cv2_args *a, const elo_mlp_args *ja, const elo_mlp_args *jb);
+int elo_cv_stage2_upconv_fused(const elo_cv2_args *a, const elo_mlp_args *ja, const elo_mlp_args *jb, elo_stream_t stream);
 
 #ifdef __cplusplus
 }
