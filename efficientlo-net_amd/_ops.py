@@ -612,8 +612,9 @@ def _aligned16(*ts):
 
 
 def dense_rows_supported(x2, W):
-    """elo_dense_rows takes fp32 (rows, Cin) x (Cin, Cout) on the GPU with Cout <= 192 and W within 160 KB of LDS."""
-    return (x2.is_cuda and x2.dtype == torch.float32 and W.dtype == torch.float32 and x2.shape[0] > 0
+    """elo_dense_rows takes fp32 (rows, Cin) x (Cin, Cout) on the GPU with Cout <= 192, W within 160 KB of LDS and x 16-byte aligned
+    (a contiguous view at an offset is not: the library GEMM takes it)."""
+    return (x2.is_cuda and x2.dtype == torch.float32 and W.dtype == torch.float32 and x2.shape[0] > 0 and _aligned16(x2)
             and bool(L.lib().elo_dense_rows_supported(x2.shape[0], W.shape[0], W.shape[1]))
             and bool(L.lib().elo_dense_rows_supported(x2.shape[0], W.shape[1], W.shape[0])))
 
@@ -689,6 +690,8 @@ class _DenseBN(torch.autograd.Function):
     def backward(ctx, dy):
         x2, W, z, mean, invstd, g, bt = ctx.saved_tensors
         (dy,) = _f32(dy)
+        if not _aligned16(dy):                  # a contiguous view at an offset: elo_bn_backward (and the fused dx operand) read 16-byte vectors
+            dy = dy.clone(memory_format=torch.contiguous_format)
         M, C = z.shape
         G = ctx.groups
         dev = z.device

@@ -8,8 +8,8 @@ import pytest
 import torch
 
 import twins_torch as twin
+from backward_check import _boundary_safe_points, _check
 from conftest import load_pkg
-from oracle import ops_np as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -25,31 +25,6 @@ def _setup(seed=0, B=2, H=8, W=113, C=32, K=6):
     perm = t(rng.permutation(35).astype(np.int32))
     idx, _, _, m = elo.fused_conv_select_k(x1, x2, hw, perm, H, W, H * W, 5, 7, K, 0, 1000.0, 1, 1, want_valid=False)
     return rng, x1, x2, idx, m.reshape(B, H * W, K).contiguous()
-
-
-def _check(fn_hip, fn_twin, inputs, wrt, seed=0, tol=1e-4):
-    """inputs: list of fp32 tensors / non-tensors; wrt: indices of the tensors to differentiate.  The upstream gradient
-    is random; every gradient is compared against the float64 autograd of the twin, relative to its own scale."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    a32 = [x.clone().requires_grad_(True) if i in wrt else x for i, x in enumerate(inputs)]
-    a64 = [(x.double().clone().requires_grad_(True) if i in wrt else (x.double() if torch.is_tensor(x) and x.is_floating_point() else x))
-           for i, x in enumerate(inputs)]
-    out32, out64 = fn_hip(*a32), fn_twin(*a64)
-    outs32 = [o for o in (out32 if isinstance(out32, (tuple, list)) else [out32]) if o is not None]
-    outs64 = [o for o in (out64 if isinstance(out64, (tuple, list)) else [out64]) if o is not None]
-    ups = [torch.randn(o.shape, generator=g).to(DEV) for o in outs32]
-    for o32, o64 in zip(outs32, outs64):
-        assert torch.allclose(o32.double(), o64, atol=1e-4, rtol=1e-4)
-    g32 = torch.autograd.grad(outs32, [a32[i] for i in wrt], ups, allow_unused=True)
-    g64 = torch.autograd.grad(outs64, [a64[i] for i in wrt], [u.double() for u in ups], allow_unused=True)
-    for i, a, b in zip(wrt, g32, g64):
-        assert (a is None) == (b is None), i
-        if a is None:
-            continue
-        scale = float(b.abs().max()) + 1e-12
-        err = float((a.double() - b).abs().max()) / scale
-        assert err < tol, "input %d: max err %.3e of scale %.3e" % (i, err, scale)
-        assert float(a.abs().max()) > 0, i                       # a real gradient, not zeros against zeros
 
 
 def test_gather_kernels_backward():
@@ -85,14 +60,6 @@ def test_pooling_kernels_backward():
     gf, gw = torch.autograd.grad(out, a, torch.ones_like(out))
     assert float(gf[1].abs().max()) == 0 and float(gw[1].abs().max()) == 0 and float(gf[0].abs().max()) > 0
     _check(ops.softmax_valid, twin.softmax_valid, [f, w, x1.reshape(B, N, 3).contiguous()], wrt=[0, 1])
-
-
-def _boundary_safe_points(rng, B, N, H, W):
-    az_res, vres, voff = (float(x) for x in O.projection_constants(H, W))
-    col = rng.integers(0, W, (B, N)) + rng.uniform(0.3, 0.7, (B, N))
-    rowf = rng.integers(1, H, (B, N)) + rng.uniform(0.3, 0.7, (B, N))
-    az, beta, r = np.pi - col * az_res, (rowf - voff) * vres, rng.uniform(3, 30, (B, N))
-    return np.stack([r * np.cos(beta) * np.cos(az), r * np.cos(beta) * np.sin(az), r * np.sin(beta)], -1).astype(np.float32)
 
 
 def test_warp_project_backward():

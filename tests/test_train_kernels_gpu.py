@@ -34,12 +34,30 @@ def _reference(x, W, b, gamma, beta, rm, rv, momentum, eps, relu, gy, mask):
                                                 (777, 272, 256, True), (65536, 16, 16, True), (13, 19, 32, True), (1, 8, 8, True),
                                                 (120001, 67, 128, True), (150000, 128, 64, True), (100003, 8, 16, False)])
 def test_training_layer_matches_float64(rows, cin, cout, relu):
-    tf_util = load_pkg("tf_util")
     rng = np.random.default_rng(rows + cin)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-    store = tf_util.VariableStore(DEV, seed=3)
     x = t(rng.normal(0.3, 1.5, (1, rows, 1, cin))).requires_grad_(True)
     gy = t(rng.normal(0, 1, (rows, cout)))
+    _check_layer(rng, x, gy, rows, cin, cout, relu)
+
+
+def test_training_layer_takes_tensors_at_a_4_byte_offset():
+    """A layer with elo_dense_rows' row count (tuning train_dense_rows) whose input and upstream gradient are contiguous views 4 bytes
+    into their storage: elo_dense_rows and elo_bn_backward read 16-byte vectors, so the product goes to the library GEMM and batch
+    norm's backward gets an aligned copy of dy.  Same float64 checks as above."""
+    rows, cin, cout = 30000, 3, 64
+    rng = np.random.default_rng(7)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
+    x = t(rng.normal(0.3, 1.5, (rows * cin + 1,)))[1:].view(1, rows, 1, cin).requires_grad_(True)
+    gy = t(rng.normal(0, 1, (rows * cout + 1,)))[1:].view(rows, cout)
+    assert x.is_contiguous() and x.data_ptr() % 16 == 4 and gy.data_ptr() % 16 == 4
+    _check_layer(rng, x, gy, rows, cin, cout, True)
+
+
+def _check_layer(rng, x, gy, rows, cin, cout, relu):
+    tf_util = load_pkg("tf_util")
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
+    store = tf_util.VariableStore(DEV, seed=3)
     with tf_util.default_store(store):
         y = tf_util.conv2d(x, cout, [1, 1], scope="layer", bn=True, is_training=True, bn_decay=0.7,
                            activation_fn=tf_util.relu if relu else None)                       # creates the variables
@@ -54,7 +72,7 @@ def test_training_layer_matches_float64(rows, cin, cout, relu):
     leaves = [x, P["layer/weights"], P["layer/biases"], P["layer/bn/gamma"], P["layer/bn/beta"]]
     for l in leaves:
         l.grad = None
-    (y.reshape(rows, cout) * gy).sum().backward()
+    y.reshape(rows, cout).backward(gy)                          # (gy reaches the layer's backward as it is: a view stays a view)
     if rows > 1:
         want_y, want_rm, want_rv, want_g = _reference(x.reshape(rows, cin), leaves[1], leaves[2], leaves[3], leaves[4], rm0, rv0, 0.3,
                                                       tf_util.BN_EPS, relu, gy, (y.reshape(rows, cout) > 0).detach())
@@ -332,7 +350,7 @@ def test_the_layer_is_the_same_on_both_dense_paths():
         x = x0.clone().requires_grad_(True)
         with tuning.override(train_dense=own), tf_util.default_store(store):
             y = tf_util.conv2d(x, cout, [1, 1], scope="layer", bn=True, is_training=True, bn_decay=0.7, activation_fn=tf_util.relu)
-            (y.reshape(rows, cout) * gy).sum().backward()
+            y.reshape(rows, cout).backward(gy)                          # (gy reaches the layer's backward as it is: a view stays a view)
         P = store.params
         res.append([y.detach(), store.buffers["layer/bn/moving_mean"], store.buffers["layer/bn/moving_variance"], x.grad,
                     P["layer/weights"].grad, P["layer/biases"].grad, P["layer/bn/gamma"].grad, P["layer/bn/beta"].grad])

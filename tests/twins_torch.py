@@ -7,7 +7,7 @@ Neighbour indices and masks carry no gradient (utils/pointnet_util.py:54-55 wrap
 are integers).
 
 Gradient semantics follow the reference's TF graph: gather_nd -> scatter-add of the incoming
-gradient, reduce_max -> arg-max routing, and the re-projection passes gradients to the scattered
+gradient, reduce_max -> arg-max routing (split evenly among exact ties), and the re-projection passes gradients to the scattered
 VALUES (model_util.py:264-273), never to the cell indices.
 """
 import math
@@ -77,7 +77,9 @@ def group_concat(centre_xyz, src_xyz, src_feat, idx, mask):
 
 
 def masked_maxpool(x, mask):
-    return (x * mask.unsqueeze(-1)).max(dim=2).values
+    """reduce_max over K.  amax, not .max(dim): .max(dim)'s backward sends the whole gradient to ONE arg-max index, where
+    TF's reduce_max gradient (and the kernel) splits it evenly among exact ties -- common after a ReLU and with masked slots."""
+    return torch.amax(x * mask.unsqueeze(-1), dim=2)
 
 
 def _geometry(p, g):
