@@ -167,6 +167,8 @@ SYMBOLS = [
     ("elo_fused_conv_select_k", ctypes.c_int, [ctypes.POINTER(GroupArgs), _vp]),
     ("elo_fused_conv_random_k_dense", ctypes.c_int, [ctypes.POINTER(GroupArgs), _vp]),
     ("elo_fused_conv_select_k_dense", ctypes.c_int, [ctypes.POINTER(GroupArgs), _vp]),
+    ("elo_fused_conv_random_k_dense_fits", ctypes.c_int, [ctypes.c_int] * 5),
+    ("elo_fused_conv_select_k_dense_fits", ctypes.c_int, [ctypes.c_int] * 6),
     ("elo_debug_select_dense_waves", ctypes.c_int, [ctypes.c_int]),
     ("elo_perm_refresh", ctypes.c_int, [ctypes.POINTER(PermRefreshArgs), _vp]),
     ("elo_group_concat", ctypes.c_int, [ctypes.POINTER(GroupConcatArgs), _vp]),

@@ -2798,16 +2798,6 @@ int check_dtype(int feat_dtype, const char *who)
 int &range_check_flag() { return tuning().range_check; }
 
 // the products mode is a property of the LAUNCH (the kernels are instantiated per mode): every layer must agree
-template <typename... Rest>
-int products_mode(const char *who, int *mode, const elo_dense &first, const Rest &...rest)
-{
-    const int m = first.products;
-    for (const elo_dense *L : {&rest...})
-        if (L->products != m) return fail(ELO_ERR_ARG, "%s: the layers of one launch must share one products mode", who);
-    *mode = m == ELO_PRODUCTS_HALF ? MODE_HALF : range_check_flag() ? MODE_CHECKED : MODE_SPLIT;
-    return ELO_OK;
-}
-
 int products_mode(const char *who, int *mode, const elo_dense *layers, int n, const elo_dense *layers2 = nullptr, int n2 = 0)
 {
     const int m = layers[0].products;
@@ -2816,6 +2806,32 @@ int products_mode(const char *who, int *mode, const elo_dense *layers, int n, co
     for (int l = 0; l < n2; ++l)
         if (layers2[l].products != m) return fail(ELO_ERR_ARG, "%s: the layers of one launch must share one products mode", who);
     *mode = m == ELO_PRODUCTS_HALF ? MODE_HALF : range_check_flag() ? MODE_CHECKED : MODE_SPLIT;
+    return ELO_OK;
+}
+
+template <typename... Rest>
+int products_mode(const char *who, int *mode, const elo_dense &first, const Rest &...rest)   // (the named layers of a cost volume)
+{
+    const elo_dense layers[] = {first, rest...};
+    return products_mode(who, mode, layers, 1 + (int)sizeof...(rest));
+}
+
+// ... of one job, or of the two same-shape jobs of a paired launch (lb = NULL: a single job), which must agree
+int pair_products_mode(const char *who, int *mode, int n, int n2, const elo_dense *la, const elo_dense *la2, const elo_dense *lb,
+                       const elo_dense *lb2)
+{
+    int mode_b = 0;
+    if (int rc = products_mode(who, mode, la, n, la2, n2)) return rc;
+    if (lb) {
+        if (int rc = products_mode(who, &mode_b, lb, n, lb2, n2)) return rc;
+        if (*mode != mode_b) return fail(ELO_ERR_ARG, "%s: the two jobs of a paired launch must share one products mode", who);
+    }
+    return ELO_OK;
+}
+
+int check_points(int batch, int npoints, const char *who)
+{
+    if ((long)batch * npoints >= 0x7fffffffL) return fail(ELO_ERR_LIMIT, "%s: batch * npoints beyond 2^31", who);
     return ELO_OK;
 }
 
@@ -2850,27 +2866,48 @@ using namespace elo;
 
 static inline int pad16(int x) { return (x + 15) & ~15; }
 
-// KERNEL<TILE, MODE> for TILE in {32, 16}, picked by (tile16, mode); a -DELO_DENSE_F32 library has no fp16-product kernels
+// X(MODE, ...) for the products mode of a launch; a -DELO_DENSE_F32 library has no fp16-product kernels
 #ifdef ELO_DENSE_F32
-#define ELO_PICK(KERNEL, tile16, mode, CALL)                                                              \
-    do {                                                                                                  \
-        if ((mode) == MODE_CHECKED) { if (tile16) CALL((KERNEL<16, MODE_CHECKED>)); else CALL((KERNEL<32, MODE_CHECKED>)); } \
-        else { if (tile16) CALL((KERNEL<16, MODE_SPLIT>)); else CALL((KERNEL<32, MODE_SPLIT>)); }         \
-    } while (0)
+#define ELO_PICK_MODE(M_, X, ...) do { if ((M_) == MODE_CHECKED) X(MODE_CHECKED, __VA_ARGS__); else X(MODE_SPLIT, __VA_ARGS__); } while (0)
 #else
-#define ELO_PICK(KERNEL, tile16, mode, CALL)                                                              \
+#define ELO_PICK_MODE(M_, X, ...)                                                                         \
     do {                                                                                                  \
-        if ((mode) == MODE_HALF) { if (tile16) CALL((KERNEL<16, MODE_HALF>)); else CALL((KERNEL<32, MODE_HALF>)); } \
-        else if ((mode) == MODE_CHECKED) { if (tile16) CALL((KERNEL<16, MODE_CHECKED>)); else CALL((KERNEL<32, MODE_CHECKED>)); } \
-        else { if (tile16) CALL((KERNEL<16, MODE_SPLIT>)); else CALL((KERNEL<32, MODE_SPLIT>)); }         \
+        if ((M_) == MODE_HALF) X(MODE_HALF, __VA_ARGS__);                                                 \
+        else if ((M_) == MODE_CHECKED) X(MODE_CHECKED, __VA_ARGS__);                                      \
+        else X(MODE_SPLIT, __VA_ARGS__);                                                                  \
     } while (0)
 #endif
+// CALL((KERNEL<TILE, MODE>)) for TILE in {32, 16}, picked by (tile16, mode)
+#define ELO_TILE_OF(M_, KERNEL, t16, CALL) do { if (t16) CALL((KERNEL<16, M_>)); else CALL((KERNEL<32, M_>)); } while (0)
+#define ELO_PICK(KERNEL, tile16, mode, CALL) ELO_PICK_MODE(mode, ELO_TILE_OF, KERNEL, tile16, CALL)
+// CALL((KERNEL<TILE_A, TILE_B, MODE>)) of a launch that carries two kinds of tiles (a cost volume and its riders)
+#define ELO_TILES_OF(M_, KERNEL, a16, b16, CALL)                                                          \
+    do {                                                                                                  \
+        if ((a16) && (b16)) CALL((KERNEL<16, 16, M_>));                                                   \
+        else if (a16) CALL((KERNEL<16, 32, M_>));                                                         \
+        else if (b16) CALL((KERNEL<32, 16, M_>));                                                         \
+        else CALL((KERNEL<32, 32, M_>));                                                                  \
+    } while (0)
+#define ELO_PICK_TILES(KERNEL, a16, b16, mode, CALL) ELO_PICK_MODE(mode, ELO_TILES_OF, KERNEL, a16, b16, CALL)
 
-// CALL_T(MODE) for the products mode of a launch (the heterogeneous launch, mlp_sv_kernel)
-#ifdef ELO_DENSE_F32
-#define ELO_PICK_MODE(M_, CALL_T) do { if ((M_) == MODE_CHECKED) CALL_T(MODE_CHECKED); else CALL_T(MODE_SPLIT); } while (0)
-#else
-#define ELO_PICK_MODE(M_, CALL_T) do { if ((M_) == MODE_HALF) CALL_T(MODE_HALF); else if ((M_) == MODE_CHECKED) CALL_T(MODE_CHECKED); else CALL_T(MODE_SPLIT); } while (0)
+#ifndef ELO_DENSE_F32
+// KERNEL<..., F16, MODE> of a register-resident (chain) kernel, by the feature storage and the products mode -- MODE_HALF or
+// MODE_SPLIT: the chain kernels have no checked form, and a -DELO_DENSE_F32 library has none of them.  The leading template
+// arguments follow CALL; ELO_PICK_RR_C: the kernels whose one leading argument is the channel count C in {16, 32, 64}.
+#define ELO_PICK_RR(KERNEL, f16, mode, CALL, ...)                                                         \
+    do {                                                                                                  \
+        if ((f16) && (mode) == MODE_HALF) CALL((KERNEL<__VA_ARGS__, true, MODE_HALF>));                   \
+        else if (f16) CALL((KERNEL<__VA_ARGS__, true, MODE_SPLIT>));                                      \
+        else if ((mode) == MODE_HALF) CALL((KERNEL<__VA_ARGS__, false, MODE_HALF>));                      \
+        else CALL((KERNEL<__VA_ARGS__, false, MODE_SPLIT>));                                              \
+    } while (0)
+#define ELO_PICK_RR_C(KERNEL, C_, f16, mode, CALL)                                                        \
+    do {                                                                                                  \
+        if ((C_) == 16) ELO_PICK_RR(KERNEL, f16, mode, CALL, 16);                                         \
+        else if ((C_) == 32) ELO_PICK_RR(KERNEL, f16, mode, CALL, 32);                                    \
+        else ELO_PICK_RR(KERNEL, f16, mode, CALL, 64);                                                    \
+    } while (0)
+#define ELO_LAUNCH_RR(k, grid, stream, ...) hipLaunchKernelGGL(k, grid, dim3(RR_WAVES * 64), RR_LDS_BYTES, stream, __VA_ARGS__)
 #endif
 
 // column budget of an in-place chain starting from `width` input columns
@@ -2910,6 +2947,15 @@ static int check_setconv(const elo_setconv_args *a, const char *who)
 // how a tile kernel is launched: LDS row stride, tile height, workgroups (per job), LDS bytes, products mode
 struct TilePlan { int S; bool t16; long units; size_t lds; int mode; };
 
+// tile height and workgroups per job for `points` centres of K rows each, `jobs` same-shape jobs sharing the grid
+static void plan_tiles(TilePlan *p, long points, int K, int jobs = 1)
+{
+    const int P32 = 32 / K, P16 = K <= 16 ? 16 / K : 1;
+    const long u32 = (points + P32 - 1) / P32, u16 = (points + P16 - 1) / P16;
+    p->t16 = small_tile(u32 * jobs, K);
+    p->units = p->t16 ? u16 : u32;
+}
+
 static bool same_shape(const elo_setconv_args *a, const elo_setconv_args *b)
 {
     if (a->batch != b->batch || a->npoints != b->npoints || a->K != b->K || a->C != b->C || a->n_layers != b->n_layers ||
@@ -2924,19 +2970,10 @@ static bool same_shape(const elo_setconv_args *a, const elo_setconv_args *b)
 // the tile-kernel launch of one or two (same-shape, already checked) set-conv jobs
 static int plan_setconv(const elo_setconv_args *a, const elo_setconv_args *b, TilePlan *p, const char *who)
 {
-    const long points = (long)a->batch * a->npoints;
-    if (points >= 0x7fffffffL) return fail(ELO_ERR_LIMIT, "%s: batch * npoints beyond 2^31", who);
+    if (int rc = check_points(a->batch, a->npoints, who)) return rc;
     p->S = row_stride(chain_cols(a->layers, a->n_layers, 3 + a->C));
-    const int P32 = 32 / a->K, P16 = a->K <= 16 ? 16 / a->K : 1;
-    const long u32 = (points + P32 - 1) / P32, u16 = (points + P16 - 1) / P16;
-    int mode_b = 0;
-    if (int rc = products_mode(who, &p->mode, a->layers, a->n_layers)) return rc;
-    if (b) {
-        if (int rc = products_mode(who, &mode_b, b->layers, b->n_layers)) return rc;
-        if (p->mode != mode_b) return fail(ELO_ERR_ARG, "%s: the two jobs of a paired launch must share one products mode", who);
-    }
-    p->t16 = small_tile(u32 * (b ? 2 : 1), a->K);
-    p->units = p->t16 ? u16 : u32;
+    if (int rc = pair_products_mode(who, &p->mode, a->n_layers, 0, a->layers, nullptr, b ? b->layers : nullptr, nullptr)) return rc;
+    plan_tiles(p, (long)a->batch * a->npoints, a->K, b ? 2 : 1);
     const int KT = a->group.random_hw ? a->group.kernel_h * a->group.kernel_w : 0;
     p->lds = tile_lds_bytes(p->t16 ? 16 : 32, p->S, KT, false);
     return check_group(a->group, a->H2, a->W2, p->lds, who);
@@ -3056,6 +3093,12 @@ extern "C" int elo_debug_narrow_launches(unsigned long long *counts2, int reset)
 // The register-resident form (setconv_rr_kernel) is taken for the model's wide shapes -- 64 feature channels, layers
 // 128 -> 64 (the set-upconvs: shape 1), 64 -> 64 -> 128 (2) or 128 -> 64 -> 64 (3) -- with in-kernel grouping, from
 // ELO_SETCONV_RR_ROWS rows per launch on (regimes: elo_mlp_fused2).  0 = the tile kernel.  
+// a single K = 32 job of three layers that carry plain weights: the candidates of the narrow (wave-per-point) kernels
+static bool narrow_chain(const elo_setconv_args *a, const elo_setconv_args *b)
+{
+    return !b && a->K == 32 && a->n_layers == 3 && a->layers[0].w_plain && a->layers[1].w_plain && a->layers[2].w_plain;
+}
+
 static int setconv_chain_shape(const elo_setconv_args *a, const elo_setconv_args *b, int mode)
 {
 #ifdef ELO_DENSE_F32
@@ -3066,8 +3109,7 @@ static int setconv_chain_shape(const elo_setconv_args *a, const elo_setconv_args
     const int shape = (nl == 2 && n1 == 128 && n2 == 64) ? 1 : (nl == 3 && n1 == 64 && n2 == 64 && n3 == 128) ? 2
                     : (nl == 3 && n1 == 128 && n2 == 64 && n3 == 64) ? 3 : 0;
     const int KT = a->group.kernel_h * a->group.kernel_w;
-    const bool narrow = !b && a->K == 32 && nl == 3 && a->layers[0].w_plain && a->layers[1].w_plain && a->layers[2].w_plain;   // (the VALU / narrow kernels)
-    if (!shape || narrow || !a->group.random_hw || !(mode == MODE_SPLIT || mode == MODE_HALF) || !cv1_rr_on() || a->C != 64 ||
+    if (!shape || narrow_chain(a, b) || !a->group.random_hw || !(mode == MODE_SPLIT || mode == MODE_HALF) || !cv1_rr_on() || a->C != 64 ||
         !(a->K == 8 || a->K == 16 || a->K == 32) || KT > 512 || a->group.idx_out || a->group.mask_out ||
         points * a->K * (b ? 2 : 1) < setconv_rr_rows(a->batch))
         return 0;
@@ -3093,12 +3135,12 @@ extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_a
         if (int rc = check_setconv(b, who)) return rc;
         if (!same_shape(a, b)) return fail(ELO_ERR_ARG, "%s: the two jobs of a paired launch must have the same shape", who);
     }
+    if (int rc = check_points(a->batch, a->npoints, who)) return rc;
     const long points = (long)a->batch * a->npoints;
-    if (points >= 0x7fffffffL) return fail(ELO_ERR_LIMIT, "%s: batch * npoints beyond 2^31", who);
     if (points == 0) return ELO_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (!b && a->group.random_hw && a->K == 32 && a->n_layers == 3 && a->layers[0].w_plain && a->layers[1].w_plain &&
-        a->layers[2].w_plain && a->layers[2].relu && a->group.kernel_h * a->group.kernel_w <= SMALL_STEPS * 32) {   // narrow chains: wave-per-point VALU kernel
+    if (narrow_chain(a, b) && a->group.random_hw && a->layers[2].relu &&
+        a->group.kernel_h * a->group.kernel_w <= SMALL_STEPS * 32) {   // narrow chains: wave-per-point VALU kernel
         const int cin = 3 + a->C, n1 = a->layers[0].N, n2 = a->layers[1].N, n3 = a->layers[2].N;
         const unsigned grid = (unsigned)((points + 7) / 8);
         if (int rc = check_group(a->group, a->H2, a->W2, 0, who)) return rc;
@@ -3136,17 +3178,11 @@ extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_a
         const int P = RR_ROWS / a->K;
         const dim3 rgrid((unsigned)((points + P - 1) / P), b ? 2u : 1u);
         const bool f16 = a->feat_dtype == ELO_F16;
-#define RRS(N1_, N2_, N3_)                                                                                                              \
-        do {                                                                                                                        \
-            if (f16 && plan.mode == MODE_HALF) hipLaunchKernelGGL((setconv_rr_kernel<4, N1_, N2_, N3_, true, MODE_HALF>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, pair);  \
-            else if (f16) hipLaunchKernelGGL((setconv_rr_kernel<4, N1_, N2_, N3_, true, MODE_SPLIT>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, pair);  \
-            else if (plan.mode == MODE_HALF) hipLaunchKernelGGL((setconv_rr_kernel<4, N1_, N2_, N3_, false, MODE_HALF>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, pair);     \
-            else hipLaunchKernelGGL((setconv_rr_kernel<4, N1_, N2_, N3_, false, MODE_SPLIT>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, pair);     \
-        } while (0)
-        if (shape == 1) RRS(128, 64, 0);
-        else if (shape == 2) RRS(64, 64, 128);
-        else RRS(128, 64, 64);
-#undef RRS
+#define CALL(k) ELO_LAUNCH_RR(k, rgrid, s, pair)
+        if (shape == 1) ELO_PICK_RR(setconv_rr_kernel, f16, plan.mode, CALL, 4, 128, 64, 0);
+        else if (shape == 2) ELO_PICK_RR(setconv_rr_kernel, f16, plan.mode, CALL, 4, 64, 64, 128);
+        else ELO_PICK_RR(setconv_rr_kernel, f16, plan.mode, CALL, 4, 128, 64, 64);
+#undef CALL
         ++g_rr_launches[2];
         return check_launch(who);
     }
@@ -3224,7 +3260,8 @@ static bool mlp_chain_regime(long rows, bool pair, int batch_hint, int mode)
 }
 
 // everything elo_mlp_fused2 decides before it launches
-struct MlpPlan { int S, mode, C; bool t16, chain; int sv_tiles; };     // sv_tiles: row tiles per batch element of the softmax_valid ride (0: none)
+// sv_tiles: row tiles per batch element of the softmax_valid ride (0: none), sv_lds: mlp_sv_kernel's dynamic LDS bytes for it
+struct MlpPlan { int S, mode, C; bool t16, chain; int sv_tiles; size_t sv_lds; };
 
 static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, const char *who)
 {
@@ -3244,12 +3281,9 @@ static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, co
     p->S = row_stride(mlp_cols(a, in_width));
     const long u32 = (a->rows + 31) / 32;
     p->mode = 0;
-    int mode_b = 0;
-    if (int rc = products_mode(who, &p->mode, a->layers, a->n_layers, a->layers2, a->n_layers2)) return rc;
-    if (b) {
-        if (int rc = products_mode(who, &mode_b, b->layers, b->n_layers, b->layers2, b->n_layers2)) return rc;
-        if (p->mode != mode_b) return fail(ELO_ERR_ARG, "%s: the two jobs of a paired launch must share one products mode", who);
-    }
+    if (int rc = pair_products_mode(who, &p->mode, a->n_layers, a->n_layers2, a->layers, a->layers2, b ? b->layers : nullptr,
+                                    b ? b->layers2 : nullptr))
+        return rc;
     p->t16 = small_tile(u32 * (b ? 2 : 1), 1);
     p->chain = false;
     p->C = a->n_sources == 2 ? a->src_width[1] : 0;
@@ -3258,10 +3292,11 @@ static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, co
         // two regimes (fused._prepass_rows): batch >= 4 keeps the GPU full -- 24.0 k -> 25.5 k pairs/s at batch 8 with the chain at
         // every level; at batch 1 (7200 rows at l0) the tile kernel is faster: 10.2 k vs 9.8 k
         const int C = p->C;
-        const bool aligned = ((uintptr_t)a->src[0] | (uintptr_t)a->src[1] | (uintptr_t)a->before | (uintptr_t)a->after | (uintptr_t)a->out |
-                              (uintptr_t)a->out2) % 16 == 0 &&
-                             (!b || ((uintptr_t)b->src[0] | (uintptr_t)b->src[1] | (uintptr_t)b->before | (uintptr_t)b->after | (uintptr_t)b->out |
-                                     (uintptr_t)b->out2) % 16 == 0);
+        const auto aligned16 = [](const elo_mlp_args *j) {
+            return ((uintptr_t)j->src[0] | (uintptr_t)j->src[1] | (uintptr_t)j->before | (uintptr_t)j->after | (uintptr_t)j->out |
+                    (uintptr_t)j->out2) % 16 == 0;
+        };
+        const bool aligned = aligned16(a) && (!b || aligned16(b));
         p->chain = a->n_sources == 2 && a->src_width[0] == 64 &&
                    (C == 16 || C == 32 || C == 64) && a->n_layers == 2 && a->layers[0].N == 128 && a->layers[1].N == 64 && a->n_layers2 == 2 &&
                    a->layers2[0].N == 128 && a->layers2[1].N == 64 && a->w_before == C && a->w_after == 64 && aligned &&
@@ -3270,6 +3305,7 @@ static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, co
 #endif
     // the softmax_valid ride (elo_mlp_args.sv_*): tile kernel, 64-wide final output, whole tiles per batch element
     p->sv_tiles = 0;
+    p->sv_lds = 0;
     const int final_n = a->n_layers2 > 0 ? a->layers2[a->n_layers2 - 1].N : a->layers[a->n_layers - 1].N;
     if (!p->chain && final_n == 64 && a->sv_npoints > 0 && a->rows > 0 && a->rows % a->sv_npoints == 0) {
         // the ride launches (batch x row tiles per element) workgroups -- a pair is ONE 512-thread workgroup, and an element's last tile
@@ -3280,6 +3316,7 @@ static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, co
         const size_t lds = sizeof(float) * ((size_t)groups * tile * p->S + (b ? 0 : (size_t)tile * 64));   // (mlp_sv_kernel's dynamic LDS)
         if (tiles <= ELO_SV_MAX_PARTS && lds <= 64 * 1024) {      // a wider generic MLP falls back on the separate partial-sums launch
             p->sv_tiles = (int)tiles;
+            p->sv_lds = lds;
             p->t16 = t16;
         }
     }
@@ -3314,8 +3351,7 @@ extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_
         if ((b != nullptr) == (a->sv_feature != nullptr))
             return fail(ELO_ERR_ARG, "%s: a paired launch takes its features from job b (sv_feature NULL), a single launch from sv_feature", who);
         if (!b && ((uintptr_t)a->sv_feature & 15)) return fail(ELO_ERR_ARG, "%s: unaligned sv_feature", who);
-        const int tile = t16 ? 16 : 32, groups = b ? 2 : 1;
-        const size_t lds = sizeof(float) * ((size_t)groups * tile * S + (b ? 0 : (size_t)tile * 64));
+        const size_t lds = plan.sv_lds;
         const dim3 grid((unsigned)(a->rows / a->sv_npoints) * (unsigned)plan.sv_tiles);
         hipStream_t s = (hipStream_t)stream;
 #define CALL_SV(T_, M_)                                                                                                         \
@@ -3323,8 +3359,8 @@ extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_
             if (b) hipLaunchKernelGGL((mlp_sv_kernel<T_, M_, true>), grid, dim3(2 * FUSED_BLOCK), lds, s, pair, S, plan.sv_tiles); \
             else hipLaunchKernelGGL((mlp_sv_kernel<T_, M_, false>), grid, dim3(FUSED_BLOCK), lds, s, pair, S, plan.sv_tiles);     \
         } while (0)
-#define CALL_SV_T(M_) do { if (t16) CALL_SV(16, M_); else CALL_SV(32, M_); } while (0)
-        ELO_PICK_MODE(mode, CALL_SV_T);
+#define CALL_SV_T(M_, t16_) do { if (t16_) CALL_SV(16, M_); else CALL_SV(32, M_); } while (0)
+        ELO_PICK_MODE(mode, CALL_SV_T, t16);
 #undef CALL_SV_T
 #undef CALL_SV
         ++g_sv_ride_launches;
@@ -3333,21 +3369,11 @@ extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_
     const size_t lds = tile_lds_bytes(t16 ? 16 : 32, S);
 #ifndef ELO_DENSE_F32
     if (plan.chain) {
-        const int C = plan.C;
         const dim3 rgrid((unsigned)((a->rows + RR_ROWS - 1) / RR_ROWS), b ? 2u : 1u);
         const bool f16 = a->feat_dtype == ELO_F16;
-        hipStream_t rs = (hipStream_t)stream;
-#define RRM(C_)                                                                                                                      \
-        do {                                                                                                                    \
-            if (f16 && mode == MODE_HALF) hipLaunchKernelGGL((mlp2_rr_kernel<C_, true, MODE_HALF>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, rs, pair);             \
-            else if (f16) hipLaunchKernelGGL((mlp2_rr_kernel<C_, true, MODE_SPLIT>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, rs, pair);             \
-            else if (mode == MODE_HALF) hipLaunchKernelGGL((mlp2_rr_kernel<C_, false, MODE_HALF>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, rs, pair);                \
-            else hipLaunchKernelGGL((mlp2_rr_kernel<C_, false, MODE_SPLIT>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, rs, pair);                \
-        } while (0)
-        if (C == 16) RRM(16);
-        else if (C == 32) RRM(32);
-        else RRM(64);
-#undef RRM
+#define CALL(k) ELO_LAUNCH_RR(k, rgrid, (hipStream_t)stream, pair)
+        ELO_PICK_RR_C(mlp2_rr_kernel, plan.C, f16, mode, CALL);
+#undef CALL
         ++g_rr_launches[3];
         return check_launch(who);
     }
@@ -3390,15 +3416,11 @@ static int plan_cv1(const elo_cv1_args *a, TilePlan *p, const char *who)
     if (int rc = check_dense(a->cv_xyz, 10, 64, who, "CV_xyz")) return rc;
     if (int rc = check_dense(a->sum_cv0, 128, 128, who, "sum_CV_0")) return rc;
     if (int rc = check_dense(a->sum_cv1, 128, 64, who, "sum_CV_1")) return rc;
-    const long points = (long)a->batch * a->npoints;
-    if (points >= 0x7fffffffL) return fail(ELO_ERR_LIMIT, "%s: batch * npoints beyond 2^31", who);
+    if (int rc = check_points(a->batch, a->npoints, who)) return rc;
     const int cols = 128 + cv1_feat_cols(a->C);
     p->S = row_stride(cols > 192 ? cols : 192);
-    const int P32 = 32 / a->K, P16 = a->K <= 16 ? 16 / a->K : 1;
-    const long u32 = (points + P32 - 1) / P32, u16 = (points + P16 - 1) / P16;
     if (int rc = products_mode(who, &p->mode, a->cv0, a->cv1, a->cv2, a->cv_xyz, a->sum_cv0, a->sum_cv1)) return rc;
-    p->t16 = small_tile(u32, a->K);
-    p->units = p->t16 ? u16 : u32;
+    plan_tiles(p, (long)a->batch * a->npoints, a->K);
     const int KT = a->group.random_hw ? a->group.kernel_h * a->group.kernel_w : 0;
     p->lds = tile_lds_bytes(p->t16 ? 16 : 32, p->S);                 // (order + select-k scratch alias the tile: cv1_tile)
     if (sizeof(float) * (((size_t)KT + 3) / 4 * 4 + (size_t)FUSED_WAVES * select_scratch_words(KT, a->K)) > sizeof(float) * (p->t16 ? 16 : 32) * p->S)
@@ -3416,21 +3438,12 @@ extern "C" int elo_cv_stage1_fused(const elo_cv1_args *a, elo_stream_t stream)
     if (!a->group.random_hw && cv_chain(a->C, plan.mode)) {
         const int P = RR_ROWS / a->K;                              // points per workgroup (128 rows)
         const dim3 grid((unsigned)(((long)a->batch * a->npoints + P - 1) / P));
-        const size_t lds = RR_LDS_BYTES;
         hipStream_t s = (hipStream_t)stream;
         const bool f16 = a->feat_dtype == ELO_F16;
         static_assert(RR_LDS_BYTES <= 64 * 1024, "dynamic LDS within the default limit");
-#define RR(CC)                                                                                                      \
-        do {                                                                                                        \
-            if (f16 && plan.mode == MODE_HALF) hipLaunchKernelGGL((cv1_rr_kernel<CC, true, MODE_HALF>), grid, dim3(RR_WAVES * 64), lds, s, *a);          \
-            else if (f16) hipLaunchKernelGGL((cv1_rr_kernel<CC, true, MODE_SPLIT>), grid, dim3(RR_WAVES * 64), lds, s, *a);          \
-            else if (plan.mode == MODE_HALF) hipLaunchKernelGGL((cv1_rr_kernel<CC, false, MODE_HALF>), grid, dim3(RR_WAVES * 64), lds, s, *a);             \
-            else hipLaunchKernelGGL((cv1_rr_kernel<CC, false, MODE_SPLIT>), grid, dim3(RR_WAVES * 64), lds, s, *a);             \
-        } while (0)
-        if (a->C == 16) RR(16);
-        else if (a->C == 32) RR(32);
-        else RR(64);
-#undef RR
+#define CALL(k) ELO_LAUNCH_RR(k, grid, s, *a)
+        ELO_PICK_RR_C(cv1_rr_kernel, a->C, f16, plan.mode, CALL);
+#undef CALL
         ++g_rr_launches[0];
         return check_launch(who);
     }
@@ -3473,14 +3486,9 @@ extern "C" int elo_cv_stage1_setconv_fused(const elo_cv1_args *a, const elo_setc
     const size_t lds = pc.lds > ps.lds ? pc.lds : ps.lds;
     const int S = pc.S;
     hipStream_t s = (hipStream_t)stream;
-#define CALL_T(M) do {                                                                                                  \
-        if (pc.t16 && ps.t16) hipLaunchKernelGGL((cv1_setconv_kernel<16, 16, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);      \
-        else if (pc.t16) hipLaunchKernelGGL((cv1_setconv_kernel<16, 32, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);           \
-        else if (ps.t16) hipLaunchKernelGGL((cv1_setconv_kernel<32, 16, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);           \
-        else hipLaunchKernelGGL((cv1_setconv_kernel<32, 32, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);                        \
-    } while (0)
-    ELO_PICK_MODE(pc.mode, CALL_T);
-#undef CALL_T
+#define CALL(k) hipLaunchKernelGGL(k, grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side)
+    ELO_PICK_TILES(cv1_setconv_kernel, pc.t16, ps.t16, pc.mode, CALL);
+#undef CALL
     return check_launch(who);
 }
 
@@ -3541,17 +3549,9 @@ extern "C" int elo_cv_stage1_setconv_chain(const elo_cv1_args *a, const elo_setc
     pair.job[1] = *jb;
     hipStream_t s = (hipStream_t)stream;
     const bool f16 = a->feat_dtype == ELO_F16;
-#define RRP(CC)                                                                                                                              \
-    do {                                                                                                                                    \
-        if (f16 && mode == MODE_HALF) hipLaunchKernelGGL((cv1_setconv_rr_kernel<CC, true, MODE_HALF>), grid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a, pair, n_cv, n_sc);   \
-        else if (f16) hipLaunchKernelGGL((cv1_setconv_rr_kernel<CC, true, MODE_SPLIT>), grid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a, pair, n_cv, n_sc);                 \
-        else if (mode == MODE_HALF) hipLaunchKernelGGL((cv1_setconv_rr_kernel<CC, false, MODE_HALF>), grid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a, pair, n_cv, n_sc);   \
-        else hipLaunchKernelGGL((cv1_setconv_rr_kernel<CC, false, MODE_SPLIT>), grid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a, pair, n_cv, n_sc);                          \
-    } while (0)
-    if (a->C == 16) RRP(16);
-    else if (a->C == 32) RRP(32);
-    else RRP(64);
-#undef RRP
+#define CALL(k) ELO_LAUNCH_RR(k, grid, s, *a, pair, n_cv, n_sc)
+    ELO_PICK_RR_C(cv1_setconv_rr_kernel, a->C, f16, mode, CALL);
+#undef CALL
     ++g_rr_launches[0];
     ++g_rr_launches[2];
     ++g_chain_pair_launches;
@@ -3573,16 +3573,12 @@ static int plan_cv2(const elo_cv2_args *a, TilePlan *p, const char *who)
     if (int rc = check_dense(a->xyz_enc, 10, 64, who, "sum_xyz_encoding")) return rc;
     if (int rc = check_dense(a->sum_cost0, 128 + a->C, 128, who, "sum_cost_volume_0")) return rc;
     if (int rc = check_dense(a->sum_cost1, 128, 64, who, "sum_cost_volume_1")) return rc;
-    const long points = (long)a->batch * a->npoints;
-    if (points >= 0x7fffffffL) return fail(ELO_ERR_LIMIT, "%s: batch * npoints beyond 2^31", who);
+    if (int rc = check_points(a->batch, a->npoints, who)) return rc;
     p->units = 0;
-    if (points == 0) return ELO_OK;
+    if (a->batch == 0) return ELO_OK;
     p->S = row_stride(208);
-    const int P32 = 32 / a->K, P16 = a->K <= 16 ? 16 / a->K : 1;
-    const long u32 = (points + P32 - 1) / P32, u16 = (points + P16 - 1) / P16;
     if (int rc = products_mode(who, &p->mode, a->xyz_enc, a->sum_cost0, a->sum_cost1)) return rc;
-    p->t16 = small_tile(u32, a->K);
-    p->units = p->t16 ? u16 : u32;
+    plan_tiles(p, (long)a->batch * a->npoints, a->K);
     const int KT = a->group.random_hw ? a->group.kernel_h * a->group.kernel_w : 0;
     p->lds = tile_lds_bytes(p->t16 ? 16 : 32, p->S, KT, false);
     return check_group(a->group, a->H, a->W, p->lds, who);
@@ -3603,17 +3599,9 @@ extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream)
         const int P = RR_ROWS / a->K;                              // points per workgroup (128 rows)
         const dim3 rgrid((unsigned)(((long)a->batch * a->npoints + P - 1) / P));
         const bool f16 = a->feat_dtype == ELO_F16;
-#define RR(CC)                                                                                                           \
-        do {                                                                                                             \
-            if (f16 && mode == MODE_HALF) hipLaunchKernelGGL((cv2_rr_kernel<CC, true, MODE_HALF>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a);     \
-            else if (f16) hipLaunchKernelGGL((cv2_rr_kernel<CC, true, MODE_SPLIT>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a);     \
-            else if (mode == MODE_HALF) hipLaunchKernelGGL((cv2_rr_kernel<CC, false, MODE_HALF>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a);        \
-            else hipLaunchKernelGGL((cv2_rr_kernel<CC, false, MODE_SPLIT>), rgrid, dim3(RR_WAVES * 64), RR_LDS_BYTES, s, *a);        \
-        } while (0)
-        if (a->C == 16) RR(16);
-        else if (a->C == 32) RR(32);
-        else RR(64);
-#undef RR
+#define CALL(k) ELO_LAUNCH_RR(k, rgrid, s, *a)
+        ELO_PICK_RR_C(cv2_rr_kernel, a->C, f16, mode, CALL);
+#undef CALL
         ++g_rr_launches[1];
         return check_launch(who);
     }
@@ -3673,14 +3661,9 @@ extern "C" int elo_cv_stage2_upconv_fused(const elo_cv2_args *a, const elo_mlp_a
     const size_t lm = tile_lds_bytes(tm, pm.S), lds = pc.lds > lm ? pc.lds : lm;
     const int S = pc.S;
     hipStream_t s = (hipStream_t)stream;
-#define CALL_T(M) do {                                                                                                  \
-        if (pc.t16 && pm.t16) hipLaunchKernelGGL((cv2_upconv_kernel<16, 16, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);      \
-        else if (pc.t16) hipLaunchKernelGGL((cv2_upconv_kernel<16, 32, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);           \
-        else if (pm.t16) hipLaunchKernelGGL((cv2_upconv_kernel<32, 16, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);           \
-        else hipLaunchKernelGGL((cv2_upconv_kernel<32, 32, M>), grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side);                        \
-    } while (0)
-    ELO_PICK_MODE(pc.mode, CALL_T);
-#undef CALL_T
+#define CALL(k) hipLaunchKernelGGL(k, grid, dim3(FUSED_BLOCK), lds, s, *a, S, n_cv, side)
+    ELO_PICK_TILES(cv2_upconv_kernel, pc.t16, pm.t16, pc.mode, CALL);
+#undef CALL
     ++g_upconv_ride_launches;
     return check_launch(who);
 }

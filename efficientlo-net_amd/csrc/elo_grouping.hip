@@ -690,16 +690,25 @@ extern "C" int elo_fused_conv_random_k(const elo_group_args *a, elo_stream_t str
     return check_launch("elo_fused_conv_random_k");
 }
 
+static constexpr size_t LDS_LIMIT = 64 * 1024;          // dynamic LDS of the dense forms' workgroups
+
 // LDS bytes of the dense form with `rows` x 64 centres per workgroup, 0 = it does not fit
-static size_t dense_lds_bytes(const elo_group_args *a, int rows)
+static size_t dense_lds_bytes(int kH, int kW, int K, int sh, int sw, int rows)
 {
     using namespace elo;
-    const int KT = a->kernel_h * a->kernel_w, threads = rows * 64;
-    const DenseGeom g = dense_geom(rows, a->kernel_h, a->kernel_w, a->stride_h, a->stride_w);
+    const int KT = kH * kW, threads = rows * 64;
+    const DenseGeom g = dense_geom(rows, kH, kW, sh, sw);
     const int KTp = (KT + DENSE_CHUNK - 1) / DENSE_CHUNK * DENSE_CHUNK;
     const size_t bytes = sizeof(int) * KTp + sizeof(float4) * (size_t)g.RH * g.RW +
-                         sizeof(int) * ((size_t)(threads + 1) * a->K + 2 * threads);
-    return bytes <= 64 * 1024 ? bytes : 0;
+                         sizeof(int) * ((size_t)(threads + 1) * K + 2 * threads);
+    return bytes <= LDS_LIMIT ? bytes : 0;
+}
+
+// the query of the host: the smaller (2 x 64) tile fits, i.e. elo_fused_conv_random_k_dense will not answer ELO_ERR_LIMIT
+extern "C" int elo_fused_conv_random_k_dense_fits(int kernel_h, int kernel_w, int K, int stride_h, int stride_w)
+{
+    if (kernel_h <= 0 || kernel_w <= 0 || K <= 0 || stride_h <= 0 || stride_w <= 0 || (long)kernel_h * kernel_w > ELO_MAX_WINDOW) return 0;
+    return dense_lds_bytes(kernel_h, kernel_w, K, stride_h, stride_w, 2) != 0;
 }
 
 extern "C" int elo_fused_conv_random_k_dense(const elo_group_args *a, elo_stream_t stream)
@@ -711,9 +720,10 @@ extern "C" int elo_fused_conv_random_k_dense(const elo_group_args *a, elo_stream
     // 4 rows per workgroup share more of the window; 2 rows give twice the workgroups (small grids, large windows)
     const int forced = tuning().random_dense_rows;
     const long tiles4 = (long)((a->W + DENSE_COLS - 1) / DENSE_COLS) * ((a->H + 3) / 4) * a->batch;
-    int rows = forced ? forced : (tiles4 >= 1024 && dense_lds_bytes(a, 4) ? 4 : 2);
-    if (rows == 4 && !dense_lds_bytes(a, 4)) rows = 2;
-    const size_t lds = dense_lds_bytes(a, rows);
+    const auto lds_of = [&](int rows) { return dense_lds_bytes(a->kernel_h, a->kernel_w, a->K, a->stride_h, a->stride_w, rows); };
+    int rows = forced ? forced : (tiles4 >= 1024 && lds_of(4) ? 4 : 2);
+    if (rows == 4 && !lds_of(4)) rows = 2;
+    const size_t lds = lds_of(rows);
     if ((rows != 2 && rows != 4) || lds == 0)
         return fail(ELO_ERR_LIMIT, "%s: window %dx%d with K = %d does not fit the LDS tile (use elo_fused_conv_random_k)",
                     who, a->kernel_h, a->kernel_w, a->K);
@@ -749,6 +759,18 @@ extern "C" int elo_debug_select_dense_waves(int waves)      // (shorthand for el
 
 // select-k for the call shape "every pixel a centre" (see group_select_k_dense): K <= 7, flag_copy 0, windows up to 512
 // slots whose union over 64 centres fits the LDS tile
+static bool select_dense_shape(int K, int flag_copy, long KT) { return K <= 7 && flag_copy == 0 && KT <= 512; }
+
+// the query of the host: the form's LARGEST configuration fits (16 waves per tile, with the two count masks), so the answer
+// holds whichever P the launcher picks and whichever outputs the call asks for (the launcher itself sizes LDS for the call)
+extern "C" int elo_fused_conv_select_k_dense_fits(int kernel_h, int kernel_w, int K, int flag_copy, int stride_h, int stride_w)
+{
+    using namespace elo;
+    if (kernel_h <= 0 || kernel_w <= 0 || K <= 0 || stride_h <= 0 || stride_w <= 0) return 0;
+    return select_dense_shape(K, flag_copy, (long)kernel_h * kernel_w) &&
+           sizeof(int) * select_dense_lds_words(16, kernel_h, kernel_w, stride_h, stride_w, true) <= LDS_LIMIT;
+}
+
 extern "C" int elo_fused_conv_select_k_dense(const elo_group_args *a, elo_stream_t stream)
 {
     using namespace elo;
@@ -756,7 +778,7 @@ extern "C" int elo_fused_conv_select_k_dense(const elo_group_args *a, elo_stream
     if (int rc = check_args(a, who, true)) return rc;
     if (a->batch == 0) return ELO_OK;
     const int KT = a->kernel_h * a->kernel_w;
-    if (a->K > 7 || a->flag_copy != 0 || KT > 512)
+    if (!select_dense_shape(a->K, a->flag_copy, KT))
         return fail(ELO_ERR_LIMIT, "%s: K = %d, flag_copy = %d, window %dx%d outside the dense form (K <= 7, flag_copy 0, <= 512 slots): "
                     "use elo_fused_conv_select_k", who, a->K, a->flag_copy, a->kernel_h, a->kernel_w);
     const bool counts = a->valid_idx || a->valid_in_dis_idx;
@@ -766,7 +788,7 @@ extern "C" int elo_fused_conv_select_k_dense(const elo_group_args *a, elo_stream
     int P = forced ? forced : tiles >= 1024 ? 4 : tiles >= 256 ? 8 : 16;
     if (P != 4 && P != 8 && P != 16) return fail(ELO_ERR_ARG, "%s: elo_tuning.select_dense_waves must be 4, 8 or 16", who);
     const size_t lds = sizeof(int) * select_dense_lds_words(P, a->kernel_h, a->kernel_w, a->stride_h, a->stride_w, counts);
-    if (lds > 64 * 1024)
+    if (lds > LDS_LIMIT)
         return fail(ELO_ERR_LIMIT, "%s: window %dx%d does not fit the LDS tile (use elo_fused_conv_select_k)", who, a->kernel_h, a->kernel_w);
     const dim3 grid((unsigned)((a->W + DENSE_COLS - 1) / DENSE_COLS), (unsigned)a->H, (unsigned)a->batch);
     hipStream_t s = (hipStream_t)stream;

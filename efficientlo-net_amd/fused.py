@@ -10,6 +10,7 @@ import torch
 
 from . import _lib as L
 from . import tf_util, tuning
+from .fused_conv import grouping_entry
 
 
 def fp32_mfma():
@@ -453,14 +454,10 @@ def group_prepass(kind, xyz1_grid, xyz2_grid, group, K):
     N, kH, kW = H * W, group.kernel_h, group.kernel_w
     idx = torch.empty((B, N, K, 3), dtype=torch.int32, device=xyz1_grid.device)
     mask = torch.empty((B, N, K), dtype=torch.float32, device=xyz1_grid.device)
-    if kind == "select":
-        from .fused_conv import _select_dense_fits                # the launcher's own bounds (K <= 7, <= 512 slots, 64 KB of LDS)
-        dense = -(-W // 64) * H * B >= tuning.get("select_dense_tiles") and _select_dense_fits(kH, kW, K, 0, group.stride_h, group.stride_w)
-        entry = "elo_fused_conv_select_k_dense" if dense else "elo_fused_conv_select_k"
-    else:
-        RH, RW = 1 // group.stride_h + kH, 63 // group.stride_w + kW           # (fused_conv._dense_fits)
-        dense = 4 * ((kH * kW + 7) & ~7) + 16 * RH * RW + 4 * (129 * K + 256) <= 64 * 1024
-        entry = "elo_fused_conv_random_k_dense" if dense else "elo_fused_conv_random_k"
+    # select-k: the tiled form only on large grids (select_dense_tiles: its fixed cost is three times the wave form's)
+    large = kind != "select" or -(-W // 64) * H * B >= tuning.get("select_dense_tiles")
+    entry = grouping_entry(kind, kH, kW, K, 0, group.stride_h, group.stride_w, large)
+    dense = entry.endswith("_dense")
     hw = None if dense else _all_pixels(B, H, W, xyz1_grid.device)
     a = L.GroupArgs(B, H, W, H2, W2, N, kH, kW, K, 0, group.distance, group.stride_h, group.stride_w,
                     xyz1_grid.data_ptr(), xyz2_grid.data_ptr(), None if dense else hw.data_ptr(), group.random_hw.data_ptr(),

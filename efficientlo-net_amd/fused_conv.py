@@ -64,21 +64,19 @@ def register_dense_index(idx_n2):
     return idx_n2
 
 
-def _select_dense_fits(kH, kW, K, flag_copy, stride_h, stride_w):
-    """Bounds of elo_fused_conv_select_k_dense (csrc/elo_grouping.hip): K <= 7, flag_copy 0, <= 512 slots, 64 KB of LDS at
-    its largest form (16 waves per tile, with the two prefix masks)."""
-    RH, RW = kH, 63 // stride_w + kW
-    words = 4 * RH * RW + 2 * 64 * 32 + 16 * 64 + 64 + 2 * 16 * 64 + 64 + ((kH * kW + 3) & ~3) + 16 * 128
-    return K <= 7 and flag_copy == 0 and kH * kW <= 512 and 4 * words <= 64 * 1024
+def grouping_entry(kind, kH, kW, K, flag_copy, stride_h, stride_w, dense_ok):
+    """Entry point of a grouping call (kind "random" / "select").  dense_ok is the caller's half of the choice: every pixel
+    of xyz1 is a centre in row-major order (and whatever else it wants of the LDS-tiled form); whether the window fits
+    that form's tile is the library's answer (include/elo.h elo_fused_conv_*_k_dense_fits)."""
+    lib = _lib.lib()
+    if kind == "select":
+        fits = lib.elo_fused_conv_select_k_dense_fits(kH, kW, K, flag_copy, stride_h, stride_w)
+    else:
+        fits = lib.elo_fused_conv_random_k_dense_fits(kH, kW, K, stride_h, stride_w)
+    return "elo_fused_conv_%s_k%s" % (kind, "_dense" if dense_ok and fits else "")
 
 
-def _dense_fits(kH, kW, K, stride_h, stride_w):
-    """dense_lds_bytes of csrc/elo_grouping.hip for its smaller (2 x 64) tile: window union + hit lists within 64 KB of LDS."""
-    RH, RW = 1 // stride_h + kH, 63 // stride_w + kW
-    return 4 * ((kH * kW + 7) & ~7) + 16 * RH * RW + 4 * (129 * K + 256) <= 64 * 1024
-
-
-def _launch(entry, name, xyz1, xyz2, idx_n2, random_hw, H, W, npoints, kernel_size_H, kernel_size_W, K,
+def _launch(kind, name, xyz1, xyz2, idx_n2, random_hw, H, W, npoints, kernel_size_H, kernel_size_W, K,
             flag_copy, distance, stride_h, stride_w, want_valid, dense=None):
     # H, W attributes are unused by the reference's Compute as well: the real
     # sizes come from the tensor (fused_conv.cpp:108-110).
@@ -88,19 +86,14 @@ def _launch(entry, name, xyz1, xyz2, idx_n2, random_hw, H, W, npoints, kernel_si
     idx_n2, random_hw = idx_n2.contiguous(), random_hw.contiguous()
     KT = kernel_size_H * kernel_size_W
     dev = xyz1.device
-    if entry == "elo_fused_conv_random_k" and dense is not False and npoints == H * W:
-        known = _DENSE_INDEX.get(idx_n2.data_ptr())
-        if dense or (known is idx_n2 and _dense_fits(kernel_size_H, kernel_size_W, K, stride_h, stride_w)):
-            entry = "elo_fused_conv_random_k_dense"
-    elif entry == "elo_fused_conv_select_k" and dense is not False and npoints == H * W:
-        known = _DENSE_INDEX.get(idx_n2.data_ptr())
-        fits = _select_dense_fits(kernel_size_H, kernel_size_W, K, flag_copy, stride_h, stride_w)
-        if dense and not fits:
-            raise ValueError("the dense select-k form takes K <= 7, flag_copy = 0 and a window of at most 512 slots")
-        if dense or (known is idx_n2 and fits):
-            entry = "elo_fused_conv_select_k_dense"
-    elif dense:
+    if dense and npoints != H * W:
         raise ValueError("the dense form needs npoints == H*W (every pixel a centre)")
+    all_pixels = npoints == H * W and (dense or (dense is None and _DENSE_INDEX.get(idx_n2.data_ptr()) is idx_n2))
+    entry = grouping_entry(kind, kernel_size_H, kernel_size_W, K, flag_copy, stride_h, stride_w, all_pixels)
+    if dense and not entry.endswith("_dense"):                # the caller insists on a form whose tile does not fit
+        if kind == "select":
+            raise ValueError("the dense select-k form takes K <= 7, flag_copy = 0 and a window of at most 512 slots")
+        entry += "_dense"                                     # random-k: the launcher answers ELO_ERR_LIMIT
     sel = torch.empty((B, npoints, K, 3), dtype=torch.int32, device=dev)
     mask = torch.empty((B, npoints, K, 1), dtype=torch.float32, device=dev)
     if want_valid:
@@ -130,7 +123,7 @@ def fused_conv_random_k(xyz1, xyz2, idx_n2, random_hw, H, W, npoints, kernel_siz
     LDS-tiled kernel is used; None = used automatically for index tensors registered with register_dense_index;
     False = always the general kernel.  Same outputs bit for bit either way.
     """
-    return _launch("elo_fused_conv_random_k", "FusedConvRandomK", xyz1, xyz2, idx_n2, random_hw, H, W,
+    return _launch("random", "FusedConvRandomK", xyz1, xyz2, idx_n2, random_hw, H, W,
                    npoints, kernel_size_H, kernel_size_W, K, flag_copy, distance, stride_h, stride_w,
                    want_valid, dense)
 
@@ -140,6 +133,6 @@ def fused_conv_select_k(xyz1, xyz2, idx_n2, random_hw, H, W, npoints, kernel_siz
     """K nearest in-range neighbours of the window (reference tie order).
     dense (extension, as for random-k): the LDS-tiled kernel for "every pixel a centre" with K <= 7 (the refinement cost
     volumes' call); None = automatically for registered index tensors.  Same outputs bit for bit."""
-    return _launch("elo_fused_conv_select_k", "FusedConvSelectK", xyz1, xyz2, idx_n2, random_hw, H, W,
+    return _launch("select", "FusedConvSelectK", xyz1, xyz2, idx_n2, random_hw, H, W,
                    npoints, kernel_size_H, kernel_size_W, K, flag_copy, distance, stride_h, stride_w,
                    want_valid, dense)

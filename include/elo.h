@@ -149,6 +149,13 @@ int elo_fused_conv_random_k_dense(const elo_group_args *a, elo_stream_t stream);
  * order are unique unless two of them are EQUAL, and exactly then the centre is redone by the wave-per-centre form in
  * the reference's visiting order).  Same outputs bit for bit.  ELO_ERR_LIMIT outside those bounds. */
 int elo_fused_conv_select_k_dense(const elo_group_args *a, elo_stream_t stream);
+/* Does a window fit the dense forms AS THIS BUILD sizes their LDS tiles?  1 / 0; host arithmetic only (no device, no stream
+ * work, elo_last_error untouched: legal during graph capture).  A host that picks a grouping entry point asks here instead of
+ * restating the tile geometry.  random_k: the smaller (2 x 64 centres) tile fits, i.e. elo_fused_conv_random_k_dense does not
+ * answer ELO_ERR_LIMIT.  select_k: K <= 7, flag_copy == 0, at most 512 slots and the form's largest configuration (16 waves
+ * per tile, both prefix masks) fits -- stricter than the launcher, which sizes LDS for the outputs and tile count of the call. */
+int elo_fused_conv_random_k_dense_fits(int kernel_h, int kernel_w, int K, int stride_h, int stride_w);
+int elo_fused_conv_select_k_dense_fits(int kernel_h, int kernel_w, int K, int flag_copy, int stride_h, int stride_w);
 /* debugging hook: force 4, 8 or 16 waves per tile in elo_fused_conv_select_k_dense (0 = chosen by grid size; also
  * ELO_SELECT_DENSE_WAVES); returns the previous setting */
 int elo_debug_select_dense_waves(int waves);

@@ -345,3 +345,67 @@ def test_the_lane_range_counter_is_stamped_into_the_fused_argument_blocks():
         assert a.range_counter == 0x1000 and b.range_counter == 0x1000 and m.range_counter == 0x1000
     finally:
         assert L.set_range_counter(prev) == 0x1000
+
+
+def _header_constants():
+    """name -> int of include/elo.h's `#define ELO_X <int>` lines and `enum { ELO_X = <int>, ... }` members."""
+    header = open(os.path.join(ROOT, "include", "elo.h")).read()
+    out = {name: int(value) for name, value in re.findall(r"^#define\s+(ELO_\w+)\s+(-?\d+)\b", header, flags=re.M)}
+    for body in re.findall(r"enum(?:\s+\w+)?\s*\{(.*?)\}", header, flags=re.S):
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        out.update({name: int(value) for name, value in re.findall(r"(ELO_\w+)\s*=\s*(-?\d+)", body)})
+    return out
+
+
+def test_python_mirrors_of_header_constants():
+    """The values the host re-types from include/elo.h are the header's (struct layouts: test_abi_layout_cpu.py)."""
+    L, fused = load_pkg("_lib"), load_pkg("fused")
+    h = _header_constants()
+    assert fused.THROUGHPUT_BATCH == h["ELO_THROUGHPUT_BATCH"]
+    assert L.SV_MAX_PARTS == h["ELO_SV_MAX_PARTS"]
+    assert (fused.PRODUCTS_SPLIT, fused.PRODUCTS_HALF) == (h["ELO_PRODUCTS_SPLIT"], h["ELO_PRODUCTS_HALF"])
+    assert (L.ELO_F32, L.ELO_F16) == (h["ELO_F32"], h["ELO_F16"])
+    for struct, field in ((L.SetconvArgs, "layers"), (L.MlpArgs, "layers"), (L.MlpArgs, "layers2")):
+        assert dict(struct._fields_)[field]._length_ == h["ELO_MAX_CHAIN"], (struct.__name__, field)
+    # the status codes test_argument_validation_without_a_gpu spells as literals, and the limit its message quotes
+    assert (h["ELO_OK"], h["ELO_ERR_ARG"], h["ELO_ERR_LIMIT"]) == (0, -1, -2)
+
+
+# (kernel_h, kernel_w, K) of every grouping call pwclo_model.py makes: the set-convs, the two cost-volume stages, the
+# set-upconvs and the refinement levels' cv_kernel2 windows; with the level strides a call can come with
+_MODEL_WINDOWS = [(9, 15, 32), (7, 11, 32), (5, 9, 16), (5, 9, 32), (3, 5, 4), (5, 35, 32), (7, 15, 8),
+                  (5, 15, 6), (7, 25, 6), (11, 41, 6)]
+_MODEL_STRIDES = [(1, 1), (4, 8), (2, 2), (1, 2)]
+
+
+def test_the_library_says_which_windows_fit_the_dense_grouping_forms():
+    """elo_fused_conv_{random,select}_k_dense_fits: literal answers, taken from a sweep of the two host-side formulas they replace
+    (kernel_h 1..25 x kernel_w 1..80 x K {1..8, 16, 32} x strides {1, 2, 4}^2 x flag_copy {0, 1}: 180 000 + 360 000 cases,
+    no mismatch).  Every random-k window of the model fits its tile at every level stride; select-k's form takes K <= 7 only."""
+    lib = load_pkg("_lib").lib()
+    rand, sel = lib.elo_fused_conv_random_k_dense_fits, lib.elo_fused_conv_select_k_dense_fits
+    for kH, kW, K in _MODEL_WINDOWS:
+        for sh, sw in _MODEL_STRIDES:
+            assert rand(kH, kW, K, sh, sw) == 1, (kH, kW, K, sh, sw)
+            assert sel(kH, kW, K, 0, sh, sw) == (1 if K <= 7 else 0), (kH, kW, K, sh, sw)
+            assert sel(kH, kW, K, 1, sh, sw) == 0
+    # the widest kernel_w that fits and the narrowest that does not, stride 1: random-k bounded by its 64 KB tile ...
+    assert (rand(9, 193, 32, 1, 1), rand(9, 194, 32, 1, 1)) == (1, 0)
+    assert (rand(25, 42, 32, 1, 1), rand(25, 43, 32, 1, 1)) == (1, 0)
+    # ... select-k by its 512 slots (11 rows) or by the tile (25 rows), and by K
+    assert (sel(11, 46, 6, 0, 1, 1), sel(11, 47, 6, 0, 1, 1)) == (1, 0)
+    assert (sel(25, 5, 6, 0, 1, 1), sel(25, 6, 6, 0, 1, 1)) == (1, 0)
+    assert (sel(11, 41, 7, 0, 1, 1), sel(11, 41, 8, 0, 1, 1)) == (1, 0)
+    # host arithmetic only: nonsense sizes are "does not fit", and nothing is recorded as an error
+    assert rand(0, 5, 4, 1, 1) == rand(3, 5, 4, 0, 1) == sel(3, 5, 6, 0, 1, 0) == sel(3, -5, 6, 0, 1, 1) == 0
+
+
+def test_grouping_entry_is_the_one_place_that_names_the_form():
+    fc = load_pkg("fused_conv")
+    assert fc.grouping_entry("random", 3, 5, 4, 0, 1, 1, True) == "elo_fused_conv_random_k_dense"
+    assert fc.grouping_entry("random", 3, 5, 4, 0, 1, 1, False) == "elo_fused_conv_random_k"
+    assert fc.grouping_entry("random", 9, 194, 32, 0, 1, 1, True) == "elo_fused_conv_random_k"
+    assert fc.grouping_entry("select", 11, 41, 6, 0, 1, 1, True) == "elo_fused_conv_select_k_dense"
+    assert fc.grouping_entry("select", 11, 41, 6, 1, 1, 1, True) == "elo_fused_conv_select_k"
+    assert fc.grouping_entry("select", 5, 9, 16, 0, 2, 2, True) == "elo_fused_conv_select_k"
+    assert fc.grouping_entry("select", 11, 41, 6, 0, 1, 1, False) == "elo_fused_conv_select_k"
