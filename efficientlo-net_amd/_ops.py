@@ -499,8 +499,42 @@ def projection_constants(H_input, W_input):
     return az, vres, -down / vres
 
 
+def _aug_frame_dev(aug_frame, B, dev):
+    """(B) int32 on `dev`: an int32 tensor that already lives there is passed through (same memory), anything array-like is
+    built on the host and copied."""
+    if isinstance(aug_frame, torch.Tensor) and aug_frame.dtype == torch.int32 and aug_frame.device == dev:
+        if aug_frame.numel() != B or not aug_frame.is_contiguous():
+            raise ValueError("a device aug_frame is a contiguous int32 tensor of one entry per batch element")
+        return aug_frame.view(B)
+    return torch.as_tensor(np.asarray(aug_frame).reshape(B), dtype=torch.int32).to(dev)
+
+
+def preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame_dev):
+    """elo_preprocess_gt: T_gt (B,4,4), T_trans / T_trans_inv (B,4,4) or both None, aug_frame_dev (B) int32 on the device
+    (None without T_trans) -> (q_gt (B,4), t_gt (B,3)) in one launch."""
+    L.require_gpu(T_gt, T_trans, T_trans_inv)
+    B = T_gt.shape[0]
+    (T_gt,) = _f32(T_gt.reshape(B, 4, 4))
+    dev = T_gt.device
+    if (T_trans is None) != (T_trans_inv is None):
+        raise ValueError("T_trans and T_trans_inv come together")
+    aug = None
+    if T_trans is not None:
+        T_trans, T_trans_inv = _f32(T_trans.reshape(B, 4, 4), T_trans_inv.reshape(B, 4, 4))
+        if not isinstance(aug_frame_dev, torch.Tensor) or aug_frame_dev.dtype != torch.int32:
+            raise TypeError("aug_frame_dev is an int32 tensor on the device (the launch reads it there)")
+        L.require_gpu(aug_frame_dev)
+        aug = _aug_frame_dev(aug_frame_dev, B, dev)
+    q_gt = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    t_gt = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    a = L.PreprocessGtArgs(B, T_gt.data_ptr(), _ptr(T_trans), _ptr(T_trans_inv), _ptr(aug), q_gt.data_ptr(), t_gt.data_ptr())
+    L.call("elo_preprocess_gt", a, q_gt)
+    return q_gt, t_gt
+
+
 def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=35.0):
-    """elo_input_stage: cloud (B, 2N, S>=3) fp32, T_trans (B,4,4) or None, aug_frame (B) of 1/2 (array-like) ->
+    """elo_input_stage: cloud (B, 2N, S>=3) fp32, T_trans (B,4,4) or None, aug_frame (B) of 1/2 (array-like, or an int32
+    tensor already on the cloud's device: its pointer is what the launch -- and a graph that records it -- reads) ->
     (points (2B,N,3), xyz_proj (2B,H,W,3))."""
     L.require_gpu(cloud, T_trans)
     (cloud,) = _f32(cloud)
@@ -510,7 +544,7 @@ def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=35.0):
     N, dev = N2 // 2, cloud.device
     if T_trans is not None:
         (T_trans,) = _f32(T_trans.reshape(B, 4, 4))
-        aug = torch.as_tensor(np.asarray(aug_frame).reshape(B), dtype=torch.int32).to(dev)
+        aug = _aug_frame_dev(aug_frame, B, dev)
     points = torch.empty((2 * B, N, 3), dtype=torch.float32, device=dev)
     out_xyz = torch.empty((2 * B, H, W, 3), dtype=torch.float32, device=dev)
     scratch = torch.empty((2 * B * H * W + 4 * 2 * B + 2 * 2 * B * N,), dtype=torch.int32, device=dev)

@@ -1132,6 +1132,41 @@ __global__ __launch_bounds__(ELO_BLOCK) void input_cell_kernel(const elo_input_s
     }
 }
 
+// The ground-truth half of PreProcess (model_util.py:403, :419, :427-445): one thread per batch element.  fp32 in, double in
+// between, each output rounded to fp32 once (include/elo.h).
+__global__ __launch_bounds__(64) void preprocess_gt_kernel(const elo_preprocess_gt_args a)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    const float *G = a.T_gt + (long)b * 16;
+    const int aug = a.T_trans ? a.aug_frame[b] : 0;
+    double T[3][4];                                                       // (the fourth row of a product is not read)
+    if (aug == 1 || aug == 2) {
+        const float *L = aug == 2 ? a.T_trans + (long)b * 16 : G;         // :403  T_trans . T_gt
+        const float *R = aug == 2 ? G : a.T_trans_inv + (long)b * 16;     // :419  T_gt . T_trans_inv
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) {
+                double s = 0.0;
+                for (int k = 0; k < 4; ++k) s += (double)L[r * 4 + k] * (double)R[k * 4 + c];
+                T[r][c] = s;
+            }
+    } else {
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) T[r][c] = (double)G[r * 4 + c];
+    }
+    // mat2euler, seq 'zyx' (:130-142)
+    const double cyaw = sqrt(T[2][2] * T[2][2] + T[1][2] * T[1][2]);
+    const double z = atan2(-T[0][1], T[0][0]) / 2.0, y = atan2(T[0][2], cyaw) / 2.0, x = atan2(-T[1][2], T[2][2]) / 2.0;
+    // euler2quat (:112-127)
+    const double cz = cos(z), sz = sin(z), cy = cos(y), sy = sin(y), cx = cos(x), sx = sin(x);
+    float *q = a.q_gt + (long)b * 4, *t = a.t_gt + (long)b * 3;
+    q[0] = (float)(cx * cy * cz - sx * sy * sz);
+    q[1] = (float)(cx * sy * sz + cy * cz * sx);
+    q[2] = (float)(cx * cz * sy - sx * cy * sz);
+    q[3] = (float)(cx * cy * sz + sx * cz * sy);
+    t[0] = (float)T[0][3]; t[1] = (float)T[1][3]; t[2] = (float)T[2][3];
+}
+
 // pass B: the point(s) holding the cell minimum are summed into the cell (tf.scatter_nd adds duplicates).
 // fp16 feature storage: a work item is a PAIR of channels, added with one packed fp16 atomic
 __global__ __launch_bounds__(ELO_BLOCK) void scatter_min_kernel(const elo_warp_project_args a, const ProjScratch ps)
@@ -1496,6 +1531,19 @@ extern "C" int elo_input_stage(const elo_input_stage_args *a, elo_stream_t strea
     const size_t elems = pts * 3;
     const unsigned gb = (unsigned)((elems + ELO_BLOCK - 1) / ELO_BLOCK);
     hipLaunchKernelGGL(scatter_min_kernel, dim3(gb > 8192 ? 8192 : gb), dim3(ELO_BLOCK), 0, s, w, ps);
+    return check_launch(who);
+}
+
+extern "C" int elo_preprocess_gt(const elo_preprocess_gt_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_preprocess_gt";
+    ELO_REQUIRE(a, who, "null argument block");
+    ELO_REQUIRE(a->batch >= 0, who, "bad sizes");
+    ELO_REQUIRE((a->T_trans == nullptr) == (a->T_trans_inv == nullptr) && (a->T_trans == nullptr) == (a->aug_frame == nullptr), who,
+                "T_trans, T_trans_inv and aug_frame come together");
+    if (a->batch == 0) return ELO_OK;
+    ELO_REQUIRE(a->T_gt && a->q_gt && a->t_gt, who, "null tensor pointer");
+    hipLaunchKernelGGL(preprocess_gt_kernel, dim3((unsigned)((a->batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, *a);
     return check_launch(who);
 }
 

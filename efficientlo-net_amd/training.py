@@ -2,8 +2,12 @@
 get_loss -> backward -> ONE flat-bucket all-reduce over RCCL -> Adam.  Mirrors main.py:120-176,344-397
 (the reference's single-GPU loop) with the data-parallel exchange of SURVEY.md section 5 added.
 Also here: the reference's training-time input augmentation (main.py:259-297) and checkpoint save / restore
-(variables + Adam state as .npz, or the variables as a TensorFlow bundle, tf_checkpoint.py).  The epoch driver
-(evaluation cadence, best-model directory policy, main.py:185-249) is out of scope.
+(variables + Adam state as .npz, or the variables as a TensorFlow bundle, tf_checkpoint.py).
+The step also runs from what the reference's loop feeds -- raw clouds, T_gt, T_trans, T_trans_inv (main.py:301-397) --
+with crop, augmentation, projection and q_gt / t_gt on the device, eagerly or inside the captured graph
+(`Trainer.step_points` / `capture_points` / `step_graph_points`); `kitti_batches` shuffles and loads an epoch of such
+batches and `train_epoch` drives the trainer over them.  Evaluation cadence and best-model policy (main.py:185-249) are
+out of scope.
 """
 import math
 import os
@@ -11,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import perm, pwclo_model, tf_checkpoint, tf_util
+from . import _ops, kitti, model_util, perm, pwclo_model, tf_checkpoint, tf_util
 from .distributed import FlatGradBucket
 from .model import graph_capture
 
@@ -49,6 +53,84 @@ def data_augmentation(rng=None):
     T[:3, :3] = rot(1, 2, ax) @ rot(2, 0, ay) @ rot(0, 1, az)
     T[:3, 3] = (draw(0.5, 1.0), draw(0.1, 0.2), draw(0.05, 0.15))
     return T
+
+
+def kitti_batches(root, seqs, T_diffs, batch_size, rng, num_points=150000, augment=True):
+    """One epoch of training batches from a KITTI odometry tree (main.py:301-362): yields (cloud (B, 2*num_points, 3) fp32,
+    T_gt, T_trans, T_trans_inv (B,4,4) float64, aug_frame (B) int32) as numpy arrays.
+    `seqs`: sequence names ('00', ...); `T_diffs`: {name: (n,12) frame-to-previous-frame transforms} (or a list in the order
+    of `seqs`).  Every scan of every listed sequence is one sample (kitti_dataset.py: sample 0 pairs scan 0 with itself).  One
+    shuffled permutation over all of them is drawn from `rng` per call and the remainder that does not fill a batch is dropped
+    (main.py:349-353).  A sample is loaded by kitti.load_pair and laid out [pos2 | pos1] as evaluate.py does (main.py:333-334).
+    `augment`: T_trans = data_augmentation(rng) per sample with its inverse (main.py:330-339) and aug_frame drawn from {1, 2}
+    per sample, which is what pwclo_model.get_model assumes when it is given none (pwclo_model.py:59); without it both
+    matrices are the identity (main.py:311-312) and aug_frame is 1."""
+    T_of = T_diffs if isinstance(T_diffs, dict) else dict(zip(seqs, T_diffs))
+    samples = []
+    for seq in seqs:
+        scans = len([f for f in os.listdir(os.path.join(root, seq, "velodyne")) if f.endswith(".bin")])
+        samples += [(seq, i) for i in range(scans)]
+    order = rng.permutation(len(samples))
+    for start in range(0, len(samples) - batch_size + 1, batch_size):
+        cloud = np.zeros((batch_size, 2 * num_points, 3), np.float32)
+        T_gt = np.zeros((batch_size, 4, 4))                              # (float64, as main.py:305-307: the step rounds them)
+        T_trans = np.tile(np.eye(4), (batch_size, 1, 1))
+        T_trans_inv = T_trans.copy()
+        aug_frame = np.ones((batch_size,), np.int32)
+        for j in range(batch_size):
+            seq, i = samples[order[start + j]]
+            pos2, pos1, _n2, _n1, T = kitti.load_pair(root, seq, i, T_of[seq], num_points)
+            cloud[j, :num_points], cloud[j, num_points:], T_gt[j] = pos2, pos1, T
+            if augment:
+                T_aug = data_augmentation(rng)
+                T_trans[j], T_trans_inv[j] = T_aug, np.linalg.inv(T_aug)
+                aug_frame[j] = rng.choice([1, 2])
+        yield cloud, T_gt, T_trans, T_trans_inv, aug_frame
+
+
+def train_epoch(trainer, batches, graph=True, H_input=64, W_input=1800):
+    """Drive `trainer` over `batches` (an iterable of kitti_batches tuples, all of one shape): returns (mean loss over the
+    batches, optimisation steps taken = what `trainer.step_count` advanced by).
+    Each batch goes through one of TWO pinned host staging sets and from there to the device with non_blocking copies, so
+    the host reads and augments the next batch while the device runs the step; a set is rewritten only once the step that
+    copied from it has finished (an event per set).  The loss is summed on the device: one synchronisation per epoch.
+    `graph`: `step_graph_points` (the trainer is capturable), else `step_points`.  One step per batch -- except where
+    `step_graph_points` has to record a graph (none from clouds yet, or the BN-decay schedule moved): the warm-up steps of a
+    capture are optimisation steps on that batch, and the count returned includes them, as `step_count` does.
+    No evaluation and no checkpoint policy here."""
+    dev = trainer.net.device
+    step = trainer.step_graph_points if graph else trainer.step_points
+    sets, done = [None, None], [None, None]
+    total, steps, before = torch.zeros((), dtype=torch.float32, device=dev), 0, trainer.step_count
+
+    def stage(slot, batch):
+        if sets[slot] is None:
+            sets[slot] = [torch.empty(a.shape, dtype=torch.int32 if i == 4 else torch.float32).pin_memory()
+                          for i, a in enumerate(batch)]
+        if done[slot] is not None:
+            done[slot].synchronize()
+        for dst, a in zip(sets[slot], batch):
+            dst.numpy()[...] = a
+
+    it = iter(batches)
+    batch = next(it, None)
+    if batch is not None:
+        stage(0, batch)
+    while batch is not None:
+        slot = steps % 2
+        total += step(*sets[slot], H_input=H_input, W_input=W_input).reshape(())   # async: copies out of the set + the step
+        done[slot] = done[slot] or torch.cuda.Event()
+        done[slot].record(torch.cuda.current_stream(dev))
+        steps += 1
+        batch = next(it, None)                                           # the host loads while the device steps
+        if batch is not None:
+            stage(1 - slot, batch)
+    return (float(total) / steps if steps else float("nan")), trainer.step_count - before
+
+
+def _as_given(*projected):
+    """The prologue of a step whose inputs are already (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)."""
+    return projected
 
 
 class FlatAdam:
@@ -149,7 +231,7 @@ class Trainer:
         can be recorded into a hipGraph (`capture` / `step_graph`)."""
         self.net = net
         self.capturable = capturable
-        self._graph = None
+        self._graph = self._kind = None
         pwclo_model.create_variables(net.store)
         dev = net.device
         self.w_x = torch.nn.Parameter(torch.tensor(0.0, device=dev))     # main.py:151
@@ -185,16 +267,65 @@ class Trainer:
         self.opt.launch()                                                # (its scalars: opt.set_hyper(), outside a captured graph)
         return loss
 
-    def step(self, xyz_f1_proj, xyz_f2_proj, q_gt, t_gt):
-        """One optimisation step on this rank's batch; returns the (local) loss."""
-        B = xyz_f1_proj.shape[0]
+    def _eager(self, B, prologue, inputs):
+        """One eager optimisation step: `prologue(*inputs)` -> (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt) -> `_body`."""
         self._set_lr(B)
         self.opt.set_hyper()
         self.net.perms.reshuffle()                                       # tf.random_shuffle draws per step
-        loss = self._body(xyz_f1_proj, xyz_f2_proj, q_gt, t_gt, bn_decay(self.step_count, self._global_batch(B)))
+        loss = self._body(*prologue(*inputs), bn_decay(self.step_count, self._global_batch(B)))
         self.net.store.invalidate()                                      # folded / packed inference weights are stale
         self.step_count += 1
         return loss
+
+    def step(self, xyz_f1_proj, xyz_f2_proj, q_gt, t_gt):
+        """One optimisation step on this rank's batch; returns the (local) loss."""
+        return self._eager(xyz_f1_proj.shape[0], _as_given, (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt))
+
+    # -- the step from raw clouds ------------------------------------------------
+    def _stage(self, H_input, W_input):
+        """The front of a step from clouds (main.py:362-368 feeds, pwclo_model.py:54-67 + model_util.py:346-445 compute):
+        `elo_input_stage` (crop, augmentation, both projections; three launches, no gradient -- tf.stop_gradient, :66-67)
+        and `elo_preprocess_gt` (one launch) -> what `_body` takes.  Every input is a device tensor, `aug_frame` included:
+        recorded into a graph, the four launches read whatever the static buffers hold at replay time."""
+        def prologue(cloud, T_gt, T_trans, T_trans_inv, aug_frame):
+            B = cloud.shape[0]
+            with torch.no_grad():
+                _points, staged = model_util.input_stage(cloud, T_trans, aug_frame, H_input, W_input)
+                q_gt, t_gt = _ops.preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame)
+            return staged[:B], staged[B:], q_gt, t_gt
+        return prologue
+
+    def _point_inputs(self, point_cloud, T_gt, T_trans, T_trans_inv, aug_frame):
+        """The five inputs of a step from clouds as tensors (host or device, numpy is wrapped without a copy); None stays None.
+        Without `T_trans` there is no augmentation and `aug_frame` is dropped; with it and no `aug_frame`, the frame is drawn
+        per batch element as pwclo_model.get_model draws it (pwclo_model.py:59)."""
+        if (T_trans is None) != (T_trans_inv is None):
+            raise ValueError("T_trans and T_trans_inv come together")
+        if T_trans is None:
+            aug_frame = None
+        elif aug_frame is None:
+            aug_frame = np.random.choice([1, 2], size=point_cloud.shape[0], replace=True)
+        tensor = lambda x: x if x is None or isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        return [tensor(x) for x in (point_cloud, T_gt, T_trans, T_trans_inv, aug_frame)]
+
+    def _point_statics(self, inputs):
+        """Device buffers for `_point_inputs` (fp32, aug_frame int32), filled from them."""
+        dev = self.net.device
+        static = [None if x is None else torch.empty(tuple(x.shape), dtype=torch.int32 if i == 4 else torch.float32, device=dev)
+                  for i, x in enumerate(inputs)]
+        for s, x in zip(static, inputs):
+            if s is not None:
+                s.copy_(x, non_blocking=True)
+        return static
+
+    def step_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800):
+        """`step` from what the reference's training loop feeds (main.py:362-368): point_cloud (B, 2N, S>=3) -- the layout
+        evaluate.predict_sequence builds -- T_gt and, for augmentation, T_trans / T_trans_inv (B,4,4) with `aug_frame` (B) of
+        1 / 2 (array-like, or int32 on the device).  Crop, augmentation, both projections and q_gt / t_gt run on the device."""
+        dev = self.net.device
+        inputs = [None if x is None else x.to(device=dev, dtype=torch.int32 if i == 4 else torch.float32, non_blocking=True)
+                  for i, x in enumerate(self._point_inputs(point_cloud, T_gt, T_trans, T_trans_inv, aug_frame))]
+        return self._eager(point_cloud.shape[0], self._stage(H_input, W_input), inputs)
 
     # -- the step as ONE hipGraph ----------------------------------------------
     def capture(self, xyz_f1_proj, xyz_f2_proj, q_gt, t_gt, warmup=3):
@@ -203,18 +334,36 @@ class Trainer:
         optimisation steps).  Learning rate and visiting orders change between replays through device tensors the
         graph reads; the BN decay is baked in, so `step_graph` re-captures when the schedule moves it (every 200 000
         samples, main.py:130-138)."""
+        self._need_capturable()
+        static = [torch.empty_like(x) for x in (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)]
+        for s, x in zip(static, (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)):
+            s.copy_(x)
+        return self._capture(("projections",), static, _as_given, xyz_f1_proj.shape[0], warmup)
+
+    def capture_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800,
+                       warmup=3):
+        """`capture` for the step from clouds: the static inputs are the cloud, the three matrices and the device `aug_frame`;
+        the input stage and `elo_preprocess_gt` are recorded in front of `_body` in the same graph (with several ranks: in the
+        first of the two), so a replay draws its crop, augmentation, projections and targets from whatever `step_graph_points`
+        copied in.  A graph recorded without T_trans has no augmentation in it."""
+        self._need_capturable()
+        inputs = self._point_inputs(point_cloud, T_gt, T_trans, T_trans_inv, aug_frame)
+        kind = ("points", H_input, W_input, T_trans is not None)
+        return self._capture(kind, self._point_statics(inputs), self._stage(H_input, W_input), point_cloud.shape[0], warmup)
+
+    def _need_capturable(self):
         if not self.capturable:
             raise RuntimeError("Trainer(net, capturable=True) is needed to capture a training step")
+
+    def _capture(self, kind, static, prologue, B, warmup):
+        """Warm up on `static` (eager steps), then record `prologue` + `_body` reading `static`; `kind` names what was recorded."""
         dev = self.net.device
-        self._static = [torch.empty_like(x) for x in (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)]
-        for s, x in zip(self._static, (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)):
-            s.copy_(x)
-        B = xyz_f1_proj.shape[0]
+        self._static, self._kind = static, kind
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                self.step(*self._static)
+                self._eager(B, prologue, static)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self._decay = bn_decay(self.step_count, self._global_batch(B))
@@ -225,7 +374,7 @@ class Trainer:
         self._split = self.bucket.has_collective()
         self._graph = torch.cuda.CUDAGraph()
         with graph_capture(self._graph):
-            self._loss = (self._gradients if self._split else self._body)(*self._static, self._decay)
+            self._loss = (self._gradients if self._split else self._body)(*prologue(*static), self._decay)
         self._graph_opt = None
         if self._split:
             self._graph_opt = torch.cuda.CUDAGraph()
@@ -247,20 +396,33 @@ class Trainer:
             self.bucket.all_reduce_mean()
             self._graph_opt.replay()
 
-    def step_graph(self, xyz_f1_proj, xyz_f2_proj, q_gt, t_gt):
-        """`step` through the captured graph (same batch shape as `capture`)."""
-        B = xyz_f1_proj.shape[0]
-        if self._graph is None or bn_decay(self.step_count, self._global_batch(B)) != self._decay:
-            self.capture(xyz_f1_proj, xyz_f2_proj, q_gt, t_gt, warmup=1 if self._graph is not None else 3)
+    def _step_graph(self, kind, inputs, B, capture):
+        """Replay the graph recorded as `kind` on `inputs`; `capture(warmup)` records it first where there is none of that kind,
+        or the BN-decay schedule has moved since it was recorded."""
+        if self._graph is None or self._kind != kind or bn_decay(self.step_count, self._global_batch(B)) != self._decay:
+            capture(1 if self._graph is not None else 3)
             return self._loss
-        for s, x in zip(self._static, (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)):
-            s.copy_(x, non_blocking=True)
+        for s, x in zip(self._static, inputs):
+            if s is not None:
+                s.copy_(x, non_blocking=True)
         self._set_lr(B)
         self.net.perms.reshuffle()
         self._replay()
         self.net.store.invalidate()
         self.step_count += 1
         return self._loss
+
+    def step_graph(self, xyz_f1_proj, xyz_f2_proj, q_gt, t_gt):
+        """`step` through the captured graph (same batch shape as `capture`)."""
+        return self._step_graph(("projections",), (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt), xyz_f1_proj.shape[0],
+                                lambda warmup: self.capture(xyz_f1_proj, xyz_f2_proj, q_gt, t_gt, warmup=warmup))
+
+    def step_graph_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800):
+        """`step_points` through the captured graph (same shapes as `capture_points`): five copies into the static buffers --
+        asynchronous from pinned host memory -- and one replay."""
+        inputs = self._point_inputs(point_cloud, T_gt, T_trans, T_trans_inv, aug_frame)
+        return self._step_graph(("points", H_input, W_input, T_trans is not None), inputs, point_cloud.shape[0],
+                                lambda warmup: self.capture_points(*inputs, H_input=H_input, W_input=W_input, warmup=warmup))
 
     # -- checkpoints -----------------------------------------------------------
     def save(self, path, tf_bundle=False):

@@ -372,7 +372,7 @@ int elo_warp_project(const elo_warp_project_args *a, elo_stream_t stream);
  *   p4 <- T_trans[b] . p4  when aug_frame[b] == f  (:392-394, :408-410);  out = p4[:3] * valid  (:421-422)
  * then the projection of elo_warp_project (no warp).  Outputs are STACKED over frames, frame 1 of every batch element
  * first: points (2*batch, npoints, 3), out_xyz (2*batch, H, W, 3) -- the layout the Siamese pyramid runs as one batch.
- * q_gt / t_gt of PreProcess (a 4x4 product and an Euler round trip per batch element) stay with the caller.
+ * q_gt / t_gt of PreProcess (a 4x4 product and an Euler round trip per batch element) are elo_preprocess_gt below.
  * scratch: (2*batch*H*W) + 4*(2*batch) + 2*(2*batch*npoints) 32-bit device words. */
 typedef struct elo_input_stage_args {
     int batch, npoints;           /* points per frame */
@@ -388,6 +388,28 @@ typedef struct elo_input_stage_args {
     unsigned *scratch;
 } elo_input_stage_args;
 int elo_input_stage(const elo_input_stage_args *a, elo_stream_t stream);
+
+/* The ground-truth half of PreProcess (model_util.py:403, :419, :427-445) in ONE launch, one thread per batch element:
+ *   T = T_trans . T_gt      where aug_frame[b] == 2  (:403)
+ *   T = T_gt . T_trans_inv  where aug_frame[b] == 1  (:419)
+ *   T = T_gt                otherwise (also: T_trans == NULL)
+ *   (z, y, x) = mat2euler(T[:3,:3]) (:130-142, no branch: cy = sqrt(r33^2 + r23^2), three atan2);
+ *   q_gt = euler2quat(z, y, x) (:112-127), t_gt = T[:3,3].
+ * The inputs are fp32; the arithmetic in between is double and each output is rounded to fp32 once (one thread per batch
+ * element, so the cost is nil: the targets of the loss are then the correctly rounded ones, not what a chain of fp32 roundings
+ * leaves; they may differ from model_util.preprocess_gt's fp32 chain by an ulp or so).
+ * aug_frame is DEVICE memory, as every pointer here: a captured training step draws a fresh augmentation per replay by
+ * rewriting it (and the matrices) between replays.  Additive to ABI 26: no existing struct changes. */
+typedef struct elo_preprocess_gt_args {
+    int batch;
+    const float *T_gt;            /* (batch,4,4) row-major */
+    const float *T_trans;         /* (batch,4,4) row-major, or NULL = no augmentation */
+    const float *T_trans_inv;     /* (batch,4,4) row-major (NULL with T_trans == NULL) */
+    const int *aug_frame;         /* (batch) (NULL with T_trans == NULL) */
+    float *q_gt;                  /* (batch,4) OUT: w, x, y, z */
+    float *t_gt;                  /* (batch,3) OUT */
+} elo_preprocess_gt_args;
+int elo_preprocess_gt(const elo_preprocess_gt_args *a, elo_stream_t stream);
 
 /* elo_pose_head followed by elo_warp_project of the NEXT level's cloud by the pose it just computed
  * (pwclo_model.py:211-236 after :194-208 / :262-280), in three launches instead of five: the projection's buffers
