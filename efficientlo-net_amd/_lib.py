@@ -70,6 +70,10 @@ InputStageArgs = _struct("elo_input_stage_args", [
     ("batch", _i), ("npoints", _i), ("point_stride", _i), ("H", _i), ("W", _i), ("az_res", _f), ("vert_res", _f),
     ("vert_off", _f), ("crop_xy", _f), ("cloud", _vp), ("T_trans", _vp), ("aug_frame", _vp), ("points", _vp),
     ("out_xyz", _vp), ("scratch", _vp)])
+InputStageBeamsArgs = _struct("elo_input_stage_beams_args", [
+    ("batch", _i), ("npoints", _i), ("point_stride", _i), ("H", _i), ("W", _i), ("az_res", _f), ("crop_xy", _f), ("cloud", _vp),
+    ("T_trans", _vp), ("aug_frame", _vp), ("points", _vp), ("out_xyz", _vp), ("scratch", _vp), ("beam_elev", _vp)])
+MAX_BEAMS = 256        # ELO_MAX_BEAMS
 PreprocessGtArgs = _struct("elo_preprocess_gt_args", [
     ("batch", _i), ("T_gt", _vp), ("T_trans", _vp), ("T_trans_inv", _vp), ("aug_frame", _vp), ("q_gt", _vp), ("t_gt", _vp)])
 
@@ -182,6 +186,7 @@ SYMBOLS = [
     ("elo_pose_head", ctypes.c_int, [ctypes.POINTER(PoseHeadArgs), _vp]),
     ("elo_warp_project", ctypes.c_int, [ctypes.POINTER(WarpProjectArgs), _vp]),
     ("elo_input_stage", ctypes.c_int, [ctypes.POINTER(InputStageArgs), _vp]),
+    ("elo_input_stage_beams", ctypes.c_int, [ctypes.POINTER(InputStageBeamsArgs), _vp]),
     ("elo_preprocess_gt", ctypes.c_int, [ctypes.POINTER(PreprocessGtArgs), _vp]),
     ("elo_pose_head_warp", ctypes.c_int, [ctypes.POINTER(PoseHeadArgs), ctypes.POINTER(WarpProjectArgs), _vp]),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),

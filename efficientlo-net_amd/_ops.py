@@ -3,8 +3,6 @@ backward passes (csrc/elo_backward.hip).  Every public operator here is ONE impl
 input requires grad (training) the call goes through a torch.autograd.Function whose forward is that same kernel and
 whose backward is the matching `elo_*_backward` kernel -- there is no second (torch) implementation to fall onto and
 nothing here looks at the global autograd mode.  Shapes are validated in C as well.  No CPU fallback: CPU tensors raise."""
-import math
-
 import numpy as np
 
 import ctypes
@@ -12,7 +10,9 @@ import ctypes
 import torch
 
 from . import _lib as L
+from . import sensor as _sensor
 from . import tuning
+from .sensor import projection_constants          # (H, W, sensor=None) -> (az_res, vert_res, vert_off), python doubles
 
 
 def _wants_grad(*ts):
@@ -421,7 +421,7 @@ class PoseRing:
 
 
 def pose_head(feature_bnc, weight_bnc, xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t, q_coarse=None, t_coarse=None, pose7=None,
-              clear=None, warp=None, next_orders=None, partials=None):
+              clear=None, warp=None, next_orders=None, partials=None, sensor=None):
     """softmax_valid -> conv1d(256) -> q,t heads -> normalise -> compose with the coarse pose, two launches.
     pwclo_model.py:194-208 / :262-280.  Returns (q (B,4), t (B,3), q_norm (B,4)); `pose7` (B,7), if given, also receives [q_norm | t].
     `next_orders`: an elo_perm_refresh_args (perm.PermSource.refresh_args): the next pooled set of visiting orders is
@@ -431,7 +431,8 @@ def pose_head(feature_bnc, weight_bnc, xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t
     `clear`: ProjectionBuffers of the projection that will consume this pose (cleared on the side).
     `warp` = (xyz (B,N,3), feat (B,N,C) or None) with `clear`: that projection itself -- warp by this pose, spherical
     re-projection -- is run by this call (elo_pose_head_warp: 3 launches instead of 2 + 2); its result is left in
-    `clear.result` for the warp_project call that follows."""
+    `clear.result` for the warp_project call that follows.  `sensor`: whose field of view that projection uses (None: the
+    reference's HDL-64E)."""
     L.require_gpu(feature_bnc, weight_bnc, xyz_bn3, W_big, W_q, W_t, q_coarse, t_coarse)
     xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t = _f32(xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t)
     (feature_bnc, weight_bnc), fdt, fcode = _feature_dtype(feature_bnc, weight_bnc)      # fp32 or fp16 storage
@@ -478,7 +479,7 @@ def pose_head(feature_bnc, weight_bnc, xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t
                 raise TypeError("the warped features and the pose head's features must share one storage dtype")
             feat_w = feat_w.contiguous()
         warped = torch.empty((Bw, Nw, 3), dtype=torch.float32, device=dev)
-        az, vres, voff = projection_constants(Hw, Ww)
+        az, vres, voff = projection_constants(Hw, Ww, sensor)
         w = L.WarpProjectArgs(Bw, Nw, Cw, Hw, Ww, az, vres, voff, xyz_w.data_ptr(), ptr(feat_w), None, None,
                               warped.data_ptr(), clear.out_xyz.data_ptr(), ptr(clear.out_feat), clear.scratch.data_ptr(), 1, fcode)
         L.call2("elo_pose_head_warp", a, w, q)
@@ -488,15 +489,6 @@ def pose_head(feature_bnc, weight_bnc, xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t
     if clear is not None:
         clear.cleared = True
     return q, t, q_norm
-
-
-def projection_constants(H_input, W_input):
-    """model_util.py:189-200: python doubles (cast to float32 by the ctypes struct)."""
-    d2r = math.pi / 180
-    az = (360.0 / W_input) * d2r
-    down, up = -24.8 * d2r, 2.0 * d2r
-    vres = (up - down) / (H_input - 1)
-    return az, vres, -down / vres
 
 
 def _aug_frame_dev(aug_frame, B, dev):
@@ -532,28 +524,65 @@ def preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame_dev):
     return q_gt, t_gt
 
 
-def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=35.0):
+def beam_table(table, H, device):
+    """The (H) float32 device tensor elo_input_stage_beams reads (radians, row 0 = the highest beam) from a Sensor with a beam
+    table or from a host array-like of radians.  Checked here, on the host, where the values can be seen: H finite, strictly
+    descending float32 entries (EloError otherwise) -- the entry point itself cannot look into device memory.  The caller owns
+    the tensor: a graph that records a launch reading it keeps its pointer (include/elo.h, LIFETIME)."""
+    if isinstance(table, _sensor.Sensor):
+        table = table.beam_elevations_rad()
+        if table is None:
+            raise L.EloError("this sensor has no beam table")
+    if isinstance(table, torch.Tensor):
+        table = table.detach().cpu().numpy()
+    host = np.asarray(table, dtype=np.float64).astype(np.float32)
+    if host.ndim != 1 or host.shape[0] != H:
+        raise L.EloError("a beam table has one elevation per image row (got shape %s for H = %d)" % (host.shape, H))
+    if not np.isfinite(host).all() or not (host[:-1] > host[1:]).all():
+        raise L.EloError("beam elevations must be finite and strictly descending in float32 (row 0 is the highest beam)")
+    return torch.from_numpy(host).to(device)
+
+
+def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam_elev=None):
     """elo_input_stage: cloud (B, 2N, S>=3) fp32, T_trans (B,4,4) or None, aug_frame (B) of 1/2 (array-like, or an int32
     tensor already on the cloud's device: its pointer is what the launch -- and a graph that records it -- reads) ->
-    (points (2B,N,3), xyz_proj (2B,H,W,3))."""
+    (points (2B,N,3), xyz_proj (2B,H,W,3)).
+    `sensor` (None: the reference's HDL-64E) gives the field of view and, unless `crop_xy` is passed, the crop.  A sensor with
+    a beam table -- or an explicit `beam_elev` -- takes elo_input_stage_beams: the row of a point is the beam nearest in
+    elevation.  `beam_elev`: that table as a float32 tensor on the cloud's device (beam_table(); used as it is -- its owner
+    validated it and keeps it alive for every graph that recorded this call), or a host array-like of radians (validated and
+    uploaded here: not inside a graph capture)."""
     L.require_gpu(cloud, T_trans)
     (cloud,) = _f32(cloud)
     B, N2, S = cloud.shape
     if N2 % 2 or S < 3:
         raise ValueError("point_cloud must be (B, 2*N, >=3)")
     N, dev = N2 // 2, cloud.device
+    sensor = _sensor.resolve(sensor)
+    if crop_xy is None:
+        crop_xy = sensor.crop_xy
     if T_trans is not None:
         (T_trans,) = _f32(T_trans.reshape(B, 4, 4))
         aug = _aug_frame_dev(aug_frame, B, dev)
     points = torch.empty((2 * B, N, 3), dtype=torch.float32, device=dev)
     out_xyz = torch.empty((2 * B, H, W, 3), dtype=torch.float32, device=dev)
     scratch = torch.empty((2 * B * H * W + 4 * 2 * B + 2 * 2 * B * N,), dtype=torch.int32, device=dev)
-    az, vres, voff = projection_constants(H, W)
-    a = L.InputStageArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), cloud.data_ptr(),
-                         T_trans.data_ptr() if T_trans is not None else None,
-                         aug.data_ptr() if T_trans is not None else None, points.data_ptr(), out_xyz.data_ptr(),
-                         scratch.data_ptr())
-    L.call("elo_input_stage", a, out_xyz)
+    az, vres, voff = projection_constants(H, W, sensor)
+    tail = (cloud.data_ptr(), T_trans.data_ptr() if T_trans is not None else None,
+            aug.data_ptr() if T_trans is not None else None, points.data_ptr(), out_xyz.data_ptr(), scratch.data_ptr())
+    if beam_elev is None and sensor.beam_elevations_deg is None:
+        a = L.InputStageArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), *tail)
+        L.call("elo_input_stage", a, out_xyz)
+        return points, out_xyz
+    if isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda:
+        if beam_elev.device != dev or beam_elev.dtype != torch.float32 or not beam_elev.is_contiguous() or beam_elev.numel() != H:
+            raise L.EloError("a device beam table is a contiguous float32 tensor of H = %d entries on the cloud's device" % H)
+    else:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
+        beam_elev = beam_table(beam_elev if beam_elev is not None else sensor, H, dev)
+    a = L.InputStageBeamsArgs(B, N, S, H, W, az, float(crop_xy), *tail, beam_elev.data_ptr())
+    L.call("elo_input_stage_beams", a, out_xyz)
     return points, out_xyz
 
 
@@ -561,13 +590,14 @@ class _WarpProject(torch.autograd.Function):
     """elo_warp_project / elo_warp_project_backward.  The forward's scratch (who won each cell) is kept for the backward."""
 
     @staticmethod
-    def forward(ctx, xyz, feat, q, t, H, W):
+    def forward(ctx, xyz, feat, q, t, H, W, sensor=None):
         B, N, _ = xyz.shape
         C = 0 if feat is None else feat.shape[-1]
         buffers = ProjectionBuffers(B, N, H, W, C, xyz.device)
-        warped, out_xyz, out_feat = _warp_project(xyz, feat, q, t, H, W, buffers)
+        warped, out_xyz, out_feat = _warp_project(xyz, feat, q, t, H, W, buffers, sensor)
         ctx.save_for_backward(xyz, q, t, buffers.scratch)
         ctx.dims = (B, N, C, H, W)
+        ctx.sensor = sensor
         return warped, out_xyz, out_feat
 
     @staticmethod
@@ -583,28 +613,29 @@ class _WarpProject(torch.autograd.Function):
             g_feat_proj = torch.zeros((B, H, W, C), dtype=torch.float32, device=dev)
         g_q = torch.zeros((B, 4), dtype=torch.float32, device=dev) if q is not None else None
         g_t = torch.zeros((B, 3), dtype=torch.float32, device=dev) if q is not None else None
-        az, vres, voff = projection_constants(H, W)
+        az, vres, voff = projection_constants(H, W, ctx.sensor)
         a = L.WarpProjectBwdArgs(B, N, C, H, W, az, vres, voff, xyz.data_ptr(), _ptr(q), _ptr(t), scratch.data_ptr(),
                                  _ptr(g_xyz_proj), _ptr(g_feat_proj), _ptr(g_warped), _ptr(g_x), _ptr(g_f), _ptr(g_q), _ptr(g_t))
         L.call("elo_warp_project_backward", a, xyz)
-        return g_x, g_f, g_q, g_t, None, None
+        return g_x, g_f, g_q, g_t, None, None, None
 
 
-def warp_project(xyz, feat, q, t, H, W, buffers=None):
+def warp_project(xyz, feat, q, t, H, W, buffers=None, sensor=None):
     """Optional quaternion warp (q,t: (B,4),(B,3) or None) + ProjectPC2SphericalRing.
     Returns (warped (B,N,3) or None, xyz_proj (B,H,W,3), feat_proj (B,H,W,C) or None).
-    `buffers`: a ProjectionBuffers of this call's shape, used (and, if a pose head cleared it, not re-initialised)."""
+    `buffers`: a ProjectionBuffers of this call's shape, used (and, if a pose head cleared it, not re-initialised).
+    `sensor`: whose field of view the uniform row formula uses (None: the reference's HDL-64E), forward and backward."""
     if buffers is None and _wants_grad(xyz, feat, q, t):
         B = xyz.shape[0]
         if feat is not None and feat.dtype != torch.float32:
             raise TypeError("training stores its features in float32")
         return _WarpProject.apply(_f32(xyz)[0], None if feat is None else feat.contiguous(),
                                   None if q is None else _f32(q.reshape(B, 4))[0],
-                                  None if q is None else _f32(t.reshape(B, 3))[0], H, W)
-    return _warp_project(xyz, feat, q, t, H, W, buffers)
+                                  None if q is None else _f32(t.reshape(B, 3))[0], H, W, sensor)
+    return _warp_project(xyz, feat, q, t, H, W, buffers, sensor)
 
 
-def _warp_project(xyz, feat, q, t, H, W, buffers=None):
+def _warp_project(xyz, feat, q, t, H, W, buffers=None, sensor=None):
     if buffers is not None and buffers.result is not None:   # the pose head that produced (q, t) already did it
         result, buffers.result = buffers.result, None
         return result
@@ -626,7 +657,7 @@ def _warp_project(xyz, feat, q, t, H, W, buffers=None):
     if buffers.out_feat is not None and buffers.out_feat.dtype != fdt:
         raise TypeError("ProjectionBuffers of dtype %s given to a projection of %s features" % (buffers.out_feat.dtype, fdt))
     out_xyz, out_feat, scratch = buffers.out_xyz, buffers.out_feat, buffers.scratch
-    az, vres, voff = projection_constants(H, W)
+    az, vres, voff = projection_constants(H, W, sensor)
     ptr = lambda x: x.data_ptr() if x is not None else None
     a = L.WarpProjectArgs(B, N, C, H, W, az, vres, voff, xyz.data_ptr(), ptr(feat), ptr(q), ptr(t), ptr(warped),
                           out_xyz.data_ptr(), ptr(out_feat), scratch.data_ptr(), 1 if buffers.cleared else 0, fcode)

@@ -824,12 +824,45 @@ __host__ __device__ inline ProjScratch proj_scratch(unsigned *s, size_t cells, s
 // the flag of (image, zero cell) -- zflag <- 0, a plain store of a constant to a word no atomic touches -- and pass B
 // lets nothing else win that cell.  For the other points a cell's value only ever decreases, so a (possibly stale)
 // read that is already <= rb proves the atomicMin would change nothing.
-__device__ __forceinline__ void bin_point(float x, float y, float z, long i, int b, int H, int W, float az_res, float vert_res,
-                                          float vert_off, const ProjScratch &ps)
+// The ROW RULE of the per-point pass is a parameter: how (atan2f(y, x), z, r) becomes a cell.
+// RowsByFormula: the reference's uniform formula (cell_of_point), every projection of the model.
+struct RowsByFormula {
+    float vert_res, vert_off;
+    __device__ __forceinline__ int cell(float at, float z, float r, int H, int W, float az_res) const
+    {
+        return cell_of_point(at, z, r, H, W, az_res, vert_res, vert_off);
+    }
+};
+
+// RowsByBeams (elo_input_stage_beams): the row of the beam nearest in elevation = the number of midpoints between consecutive
+// beams that lie above the point.  `mid` (LDS): the SINES of the H-1 midpoints, descending, padded with -inf to 2*half - 1
+// entries (2*half = the power of two >= H): z/r is compared with them -- monotone in the elevation, no asinf -- by a branch-free
+// binary search of log2(2*half) steps.  !(s >= mid): a zero point (s = 0/0 = NaN) counts every entry and lands in row H-1, the
+// row the formula's NaN -> 0 conversion gives it.  The column is cell_of_point's.
+struct RowsByBeams {
+    const float *mid;
+    int half;
+    __device__ __forceinline__ int cell(float at, float z, float r, int H, int W, float az_res) const
+    {
+        const float PI_F = 3.14159265358979323846f;
+        const float c = (PI_F - at) / az_res;                                // model_util.py:234-235 (atan2f is never NaN here)
+        int col = c != c ? 0 : (int)c;
+        const float s = z / r;
+        int row = 0;
+        for (int step = half; step >= 1; step >>= 1) row += !(s >= mid[row + step - 1]) ? step : 0;
+        row = row > H - 1 ? H - 1 : row;
+        col = col < 0 ? 0 : col > W - 1 ? W - 1 : col;
+        return row * W + col;
+    }
+};
+
+template <class Rows>
+__device__ __forceinline__ void bin_point_by(float x, float y, float z, long i, int b, int H, int W, float az_res, const Rows &rows,
+                                             const ProjScratch &ps)
 {
     const float r = sqrtf(x * x + y * y + z * z);
     const float at = atan2f(y, x);
-    const int cell = cell_of_point(at, z, r, H, W, az_res, vert_res, vert_off);
+    const int cell = rows.cell(at, z, r, H, W, az_res);
     const unsigned rb = __float_as_uint(r);        // r >= 0: bit order == float order; NaN sorts last
     ps.cell_of[i] = cell;
     ps.rbits[i] = rb;
@@ -842,6 +875,12 @@ __device__ __forceinline__ void bin_point(float x, float y, float z, long i, int
     }
     unsigned *slot = ps.minr + (long)b * H * W + cell;
     if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > rb) atomicMin(slot, rb);
+}
+
+__device__ __forceinline__ void bin_point(float x, float y, float z, long i, int b, int H, int W, float az_res, float vert_res,
+                                          float vert_off, const ProjScratch &ps)
+{
+    bin_point_by(x, y, z, i, b, H, W, az_res, RowsByFormula{vert_res, vert_off}, ps);
 }
 
 // pass A of the projection for ONE point: warp by (q, t) (q == nullptr: no warp), range bits, cell id, atomicMin of the
@@ -1104,32 +1143,52 @@ __global__ __launch_bounds__(ELO_BLOCK) void warp_cell_kernel(const elo_warp_pro
     }
 }
 
-// pass A of the raw-cloud input stage: PreProcess of one point of frame f (model_util.py:346-422) + binning.
-// Stacked index: frame f of batch element b is image f*batch + b.
+// pass A of the raw-cloud input stage for ONE point: PreProcess of point i of the stacked 2 * per_frame (model_util.py:346-422)
+// + binning.  Stacked index: frame f of batch element b is image f*batch + b.  Args: elo_input_stage_args /
+// elo_input_stage_beams_args (the same fields by name); Rows: the row rule the cell is taken by.
+template <class Args, class Rows>
+__device__ __forceinline__ void input_cell_point(const Args &a, const ProjScratch &ps, const Rows &rows, long i, long per_frame)
+{
+    const int f = i >= per_frame;                                     // 0: frame 1, 1: frame 2
+    const long j = i - f * per_frame;
+    const int b = point_batch(j, a.npoints);
+    const long n = j - (long)b * a.npoints;
+    const float *p = a.cloud + ((long)b * 2 * a.npoints + (long)f * a.npoints + n) * a.point_stride;
+    float x = p[0], y = p[1], z = p[2], w = 1.0f;
+    const float valid = (x != 0.0f || y != 0.0f || z != 0.0f) ? 1.0f : 0.0f;                  // :357-363
+    if (sqrtf(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y))) > a.crop_xy) x = y = z = w = 0.0f;   // :380-383 (no FMA: the
+                                                                                              // threshold decides like numpy's)
+    if (a.T_trans && a.aug_frame[b] == f + 1) {                                               // :392-394, :408-410
+        const float *T = a.T_trans + b * 16;
+        const float nx = T[0] * x + T[1] * y + T[2] * z + T[3] * w;
+        const float ny = T[4] * x + T[5] * y + T[6] * z + T[7] * w;
+        const float nz = T[8] * x + T[9] * y + T[10] * z + T[11] * w;
+        x = nx; y = ny; z = nz;
+    }
+    x *= valid; y *= valid; z *= valid;                                                       // :421-422
+    a.points[i * 3 + 0] = x; a.points[i * 3 + 1] = y; a.points[i * 3 + 2] = z;
+    bin_point_by(x, y, z, i, f * a.batch + b, a.H, a.W, a.az_res, rows, ps);
+}
+
 __global__ __launch_bounds__(ELO_BLOCK) void input_cell_kernel(const elo_input_stage_args a, const ProjScratch ps)
 {
     const long per_frame = (long)a.batch * a.npoints, total = 2 * per_frame;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int f = i >= per_frame;                                     // 0: frame 1, 1: frame 2
-        const long j = i - f * per_frame;
-        const int b = point_batch(j, a.npoints);
-        const long n = j - (long)b * a.npoints;
-        const float *p = a.cloud + ((long)b * 2 * a.npoints + (long)f * a.npoints + n) * a.point_stride;
-        float x = p[0], y = p[1], z = p[2], w = 1.0f;
-        const float valid = (x != 0.0f || y != 0.0f || z != 0.0f) ? 1.0f : 0.0f;                  // :357-363
-        if (sqrtf(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y))) > a.crop_xy) x = y = z = w = 0.0f;   // :380-383 (no FMA: the
-                                                                                                  // threshold decides like numpy's)
-        if (a.T_trans && a.aug_frame[b] == f + 1) {                                               // :392-394, :408-410
-            const float *T = a.T_trans + b * 16;
-            const float nx = T[0] * x + T[1] * y + T[2] * z + T[3] * w;
-            const float ny = T[4] * x + T[5] * y + T[6] * z + T[7] * w;
-            const float nz = T[8] * x + T[9] * y + T[10] * z + T[11] * w;
-            x = nx; y = ny; z = nz;
-        }
-        x *= valid; y *= valid; z *= valid;                                                       // :421-422
-        a.points[i * 3 + 0] = x; a.points[i * 3 + 1] = y; a.points[i * 3 + 2] = z;
-        bin_point(x, y, z, i, f * a.batch + b, a.H, a.W, a.az_res, a.vert_res, a.vert_off, ps);
-    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+        input_cell_point(a, ps, RowsByFormula{a.vert_res, a.vert_off}, i, per_frame);
+}
+
+// ... by beam table: every workgroup first stages the sines of the H-1 midpoints (one sinf per thread at most: H <= ELO_MAX_BEAMS
+// = the block size; the same instructions on the same table in every workgroup, so every workgroup holds the same floats)
+__global__ __launch_bounds__(ELO_BLOCK) void input_cell_beams_kernel(const elo_input_stage_beams_args a, const ProjScratch ps,
+                                                                     const int half)
+{
+    __shared__ float mid[ELO_MAX_BEAMS];
+    for (int k = threadIdx.x; k < 2 * half - 1; k += blockDim.x)
+        mid[k] = k < a.H - 1 ? sinf(0.5f * (a.beam_elev[k] + a.beam_elev[k + 1])) : -INFINITY;
+    __syncthreads();
+    const long per_frame = (long)a.batch * a.npoints, total = 2 * per_frame;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+        input_cell_point(a, ps, RowsByBeams{mid, half}, i, per_frame);
 }
 
 // The ground-truth half of PreProcess (model_util.py:403, :419, :427-445): one thread per batch element.  fp32 in, double in
@@ -1507,6 +1566,29 @@ extern "C" int elo_pose_head_warp(const elo_pose_head_args *a, const elo_warp_pr
     return pose_head_impl(a, w, stream, who);
 }
 
+// The three launches of an input stage (clear, per-point pass, scatter); `cells_launch(grid, ps)` is the per-point pass of the
+// entry's row rule.  The scatter only asks the row rule for the cells of a ZERO point, which every rule puts in row H-1
+// (asinf(0/0) = NaN -> 0 in the formula, whatever vert_res / vert_off): it runs on (vert_res, vert_off).
+template <class Args, class CellsLaunch>
+static int input_stage_launches(const Args *a, float vert_res, float vert_off, hipStream_t s, const char *who, CellsLaunch cells_launch)
+{
+    const size_t images = 2 * (size_t)a->batch, cells = images * a->H * a->W, pts = images * a->npoints;
+    const ProjScratch ps = proj_scratch(a->scratch, cells, images, pts);
+    const unsigned gi = (unsigned)((cells * 4 + ELO_BLOCK - 1) / ELO_BLOCK);
+    hipLaunchKernelGGL(project_init_kernel, dim3(gi > 4096 ? 4096 : gi), dim3(ELO_BLOCK), 0, s, ps.minr, a->out_xyz,
+                       (unsigned *)nullptr, cells, 0, (int)images);
+    const unsigned ga = (unsigned)((pts + ELO_BLOCK - 1) / ELO_BLOCK);
+    cells_launch(dim3(ga > 8192 ? 8192 : ga), ps);
+    elo_warp_project_args w = {};
+    w.batch = (int)images; w.npoints = a->npoints; w.C = 0; w.H = a->H; w.W = a->W;
+    w.az_res = a->az_res; w.vert_res = vert_res; w.vert_off = vert_off;
+    w.xyz = a->points; w.out_xyz = a->out_xyz; w.scratch = a->scratch;
+    const size_t elems = pts * 3;
+    const unsigned gb = (unsigned)((elems + ELO_BLOCK - 1) / ELO_BLOCK);
+    hipLaunchKernelGGL(scatter_min_kernel, dim3(gb > 8192 ? 8192 : gb), dim3(ELO_BLOCK), 0, s, w, ps);
+    return check_launch(who);
+}
+
 extern "C" int elo_input_stage(const elo_input_stage_args *a, elo_stream_t stream)
 {
     const char *who = "elo_input_stage";
@@ -1517,21 +1599,31 @@ extern "C" int elo_input_stage(const elo_input_stage_args *a, elo_stream_t strea
     if (a->batch == 0) return ELO_OK;                 // (an empty batch has no buffers to name)
     ELO_REQUIRE(a->cloud && a->points && a->out_xyz && a->scratch, who, "null tensor pointer");
     hipStream_t s = (hipStream_t)stream;
-    const size_t images = 2 * (size_t)a->batch, cells = images * a->H * a->W, pts = images * a->npoints;
-    const ProjScratch ps = proj_scratch(a->scratch, cells, images, pts);
-    const unsigned gi = (unsigned)((cells * 4 + ELO_BLOCK - 1) / ELO_BLOCK);
-    hipLaunchKernelGGL(project_init_kernel, dim3(gi > 4096 ? 4096 : gi), dim3(ELO_BLOCK), 0, s, ps.minr, a->out_xyz,
-                       (unsigned *)nullptr, cells, 0, (int)images);
-    const unsigned ga = (unsigned)((pts + ELO_BLOCK - 1) / ELO_BLOCK);
-    hipLaunchKernelGGL(input_cell_kernel, dim3(ga > 8192 ? 8192 : ga), dim3(ELO_BLOCK), 0, s, *a, ps);
-    elo_warp_project_args w = {};
-    w.batch = (int)images; w.npoints = a->npoints; w.C = 0; w.H = a->H; w.W = a->W;
-    w.az_res = a->az_res; w.vert_res = a->vert_res; w.vert_off = a->vert_off;
-    w.xyz = a->points; w.out_xyz = a->out_xyz; w.scratch = a->scratch;
-    const size_t elems = pts * 3;
-    const unsigned gb = (unsigned)((elems + ELO_BLOCK - 1) / ELO_BLOCK);
-    hipLaunchKernelGGL(scatter_min_kernel, dim3(gb > 8192 ? 8192 : gb), dim3(ELO_BLOCK), 0, s, w, ps);
-    return check_launch(who);
+    return input_stage_launches(a, a->vert_res, a->vert_off, s, who, [&](dim3 grid, const ProjScratch &ps) {
+        hipLaunchKernelGGL(input_cell_kernel, grid, dim3(ELO_BLOCK), 0, s, *a, ps);
+    });
+}
+
+extern "C" int elo_input_stage_beams(const elo_input_stage_beams_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_input_stage_beams";
+    static_assert(ELO_MAX_BEAMS <= ELO_BLOCK, "one midpoint per thread of the staging loop's first trip");
+    ELO_REQUIRE(a, who, "null argument block");
+    ELO_REQUIRE(a->batch >= 0 && a->npoints > 0 && a->H > 0 && a->W > 0 && a->point_stride >= 3, who, "bad sizes");
+    ELO_REQUIRE(a->H <= ELO_MAX_BEAMS, who, "more beams than ELO_MAX_BEAMS");
+    ELO_REQUIRE(a->beam_elev, who, "null beam table");
+    ELO_REQUIRE((a->T_trans == nullptr) == (a->aug_frame == nullptr), who, "T_trans and aug_frame come together");
+    ELO_REQUIRE(a->az_res > 0.0f, who, "bad projection constants");
+    ELO_REQUIRE(a->crop_xy == a->crop_xy, who, "crop_xy is NaN");
+    if (a->batch == 0) return ELO_OK;
+    ELO_REQUIRE(a->cloud && a->points && a->out_xyz && a->scratch, who, "null tensor pointer");
+    int half = 0;                                     // 2 * half: the power of two >= H (H = 1: no midpoint, no step)
+    while (2 * half < a->H) half = half ? 2 * half : 1;
+    if (a->H == 1) half = 0;
+    hipStream_t s = (hipStream_t)stream;
+    return input_stage_launches(a, 1.0f, 0.0f, s, who, [&](dim3 grid, const ProjScratch &ps) {
+        hipLaunchKernelGGL(input_cell_beams_kernel, grid, dim3(ELO_BLOCK), 0, s, *a, ps, half);
+    });
 }
 
 extern "C" int elo_preprocess_gt(const elo_preprocess_gt_args *a, elo_stream_t stream)

@@ -36,13 +36,18 @@ def pose_rows(q_n4, t_n3, Tr):
 
 
 def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_size=1, num_points=150000, frames=None,
-                     lanes=0):
+                     lanes=0, sensor=None):
     """Run the network over samples `frames` (default: all scans found) of sequence `seq`; returns (q (n,4), t (n,3))
     = the l0 pose of every sample, in sample order.  Batches are padded by repeating the last sample
     (main.py:497-509 keeps stale rows instead; either way the padding rows are dropped).
     `lanes` > 0: through `lanes` hipGraphs recorded from the raw clouds on (`PWCLONet.capture(num_points=...)`: input
     stage + pyramid in one replay, several batches in flight while the host reads the next scans) instead of the eager
-    `forward_points`; same results (no augmentation in evaluation: the identity T_trans of the eager call is a no-op)."""
+    `forward_points`; same results (no augmentation in evaluation: the identity T_trans of the eager call is a no-op).
+    `sensor`: the LiDAR the scans come from.  A net projects with the sensor it was built with (`PWCLONet(sensor=...)`, fixed for
+    its life and baked into its graphs), so this is a check that the caller and the net agree: None, or the net's."""
+    if sensor is not None and sensor != net.sensor:
+        raise ValueError("this net was built for %r, the sequence is said to come from %r: build PWCLONet(sensor=...) for it"
+                         % (net.sensor, sensor))
     seq_dir = os.path.join(root, seq)
     if frames is None:
         frames = range(len([f for f in os.listdir(os.path.join(seq_dir, "velodyne")) if f.endswith(".bin")]))

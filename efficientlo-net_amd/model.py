@@ -13,6 +13,7 @@ import time
 import torch
 
 from . import _ops, fused, model_util, perm, pwclo_model, tf_util, tuning
+from . import sensor as sensor_mod
 
 
 def graph_capture(graph):
@@ -74,10 +75,17 @@ def _cached_tensors():
 
 
 class PWCLONet:
-    def __init__(self, device="cuda:0", seed=0, perm_source=None, feature_dtype=torch.float32):
+    def __init__(self, device="cuda:0", seed=0, perm_source=None, feature_dtype=torch.float32, sensor=None):
         """feature_dtype=torch.float16: fp16 feature STORAGE in HBM between the fused kernels (BASELINE configs[2]);
-        geometry, weights and arithmetic are unchanged (fused inference path only)."""
+        geometry, weights and arithmetic are unchanged (fused inference path only).
+        sensor (sensor.Sensor; None: the reference's HDL-64E): the LiDAR's field of view, crop and -- optionally -- beam table,
+        fixed for the net's life: every forward, eager or captured, projects with it.  A beam table lives on the device as
+        `beam_elev`, a tensor this net owns for as long as its graphs (which hold its pointer) exist."""
         self.device = torch.device(device)
+        self.sensor = sensor_mod.resolve(sensor)
+        self.beam_elev = None
+        if self.sensor.beam_elevations_deg is not None:
+            self.beam_elev = _ops.beam_table(self.sensor, len(self.sensor.beam_elevations_deg), self.device)
         self.feature_dtype = feature_dtype
         self.store = tf_util.VariableStore(self.device, seed=seed)
         self.perms = perm_source if perm_source is not None else perm.PermSource(seed=seed)
@@ -94,9 +102,9 @@ class PWCLONet:
             if is_training:
                 if self.feature_dtype != torch.float32:
                     raise NotImplementedError("training stores its features in fp32")
-                return pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, True, bn_decay, pose_out)
+                return pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, True, bn_decay, pose_out, sensor=self.sensor)
             with torch.no_grad():
-                return pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, False, bn_decay, pose_out)
+                return pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, False, bn_decay, pose_out, sensor=self.sensor)
 
     def forward_points(self, point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training=False,
                        bn_decay=None, aug_frame=None):
@@ -105,7 +113,7 @@ class PWCLONet:
             ctx = torch.enable_grad() if is_training else torch.no_grad()
             with ctx:
                 return pwclo_model.get_model(point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training,
-                                             bn_decay, aug_frame)
+                                             bn_decay, aug_frame, sensor=self.sensor, beam_elev=self.beam_elev)
 
     def check_range(self, xyz_f1_proj, xyz_f2_proj):
         """One eager forward on the CHECKED instances of the fused kernels (include/elo.h elo_range_check): the number of
@@ -126,7 +134,7 @@ class PWCLONet:
                 fresh_orders=0, check_every=0):
         """Record the inference forward into `lanes` independent hipGraphs (torch.cuda.CUDAGraph on ROCm).
         With `num_points` the graph starts from RAW clouds: a lane owns a (B, 2*num_points, point_stride) cloud buffer
-        and records the input stage (model_util.input_stage: 35 m crop + both projections, no augmentation) in front
+        and records the input stage (model_util.input_stage: the sensor's crop + both projections, no augmentation) in front
         of the pyramid; feed it with `submit_points`.
 
         One frame pair keeps only a few of the 256 CUs busy per kernel, and frame pairs are independent,
@@ -180,7 +188,7 @@ class PWCLONet:
         if num_points is not None:                   # warm the input stage's allocations up as well
             with torch.cuda.stream(side):
                 model_util.input_stage(torch.zeros((batch_size, 2 * num_points, point_stride), device=dev), None, None,
-                                       H_input, W_input)
+                                       H_input, W_input, sensor=self.sensor, beam_elev=self.beam_elev)
             torch.cuda.synchronize(dev)
         for i in range(lanes):
             both = zeros()
@@ -200,7 +208,8 @@ class PWCLONet:
             self.perms.tail_armed = bool(fresh_orders)    # the recorded forward's last launch loads the NEXT replay's orders
             with graph_capture(lane["graph"]):
                 if num_points is not None:
-                    _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input)
+                    _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
+                                                          beam_elev=self.beam_elev)
                     lane["out"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"])
                 else:
                     lane["out"] = self.forward(*lane["in"], pose_out=lane["pose"])
@@ -220,7 +229,8 @@ class PWCLONet:
                     self.perms.tail_armed = bool(fresh_orders)
                     with graph_capture(lane["graph_checked"]):
                         if num_points is not None:
-                            _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input)
+                            _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
+                                                                  beam_elev=self.beam_elev)
                             lane["out_checked"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"])
                         else:
                             lane["out_checked"] = self.forward(*lane["in"], pose_out=lane["pose"])

@@ -84,20 +84,21 @@ def mat2euler(M, seq='zyx'):
     return z, y, x
 
 
-def ProjectPC2SphericalRing(PC, Feature, H_input, W_input):
+def ProjectPC2SphericalRing(PC, Feature, H_input, W_input, sensor=None):
     """model_util.py:181-292: (B,N,3[+]) points [+ (B,N,C) features] -> (B,H,W,3) [, (B,H,W,C)].
-    One HIP launch pair for the whole batch (the reference loops over the batch in Python, :213)."""
-    _, xyz_proj, feat_proj = _ops.warp_project(PC[..., :3], Feature, None, None, H_input, W_input)
+    One HIP launch pair for the whole batch (the reference loops over the batch in Python, :213).
+    `sensor` (sensor.Sensor; None: the reference's HDL-64E): the field of view of the row formula."""
+    _, xyz_proj, feat_proj = _ops.warp_project(PC[..., :3], Feature, None, None, H_input, W_input, sensor=sensor)
     return (xyz_proj, feat_proj) if Feature is not None else (xyz_proj, xyz_proj)
 
 
-def warp_and_project(xyz, feature, q_coarse, t_coarse, H_input, W_input, buffers=None):
+def warp_and_project(xyz, feature, q_coarse, t_coarse, H_input, W_input, buffers=None, sensor=None):
     """pwclo_model.py:213-232 fused: p' = (q (x) [0,p] (x) q^-1)[1:] + t, zeroed where p == 0, then
     ProjectPC2SphericalRing(p', feature).  Returns (warped (B,N,3), xyz_proj, feat_proj).
     `buffers` (inference only): _ops.ProjectionBuffers already cleared by the pose head that produced q, t."""
     if buffers is not None:
-        return _ops.warp_project(xyz, feature, q_coarse, t_coarse, H_input, W_input, buffers)
-    return _ops.warp_project(xyz, feature, q_coarse, t_coarse, H_input, W_input)
+        return _ops.warp_project(xyz, feature, q_coarse, t_coarse, H_input, W_input, buffers, sensor=sensor)
+    return _ops.warp_project(xyz, feature, q_coarse, t_coarse, H_input, W_input, sensor=sensor)
 
 
 _sel_cache = {}
@@ -168,8 +169,10 @@ def preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame):
     return q_gt, t_gt
 
 
-def input_stage(point_cloud, T_trans, aug_frame, H_input, W_input):
+def input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=None, beam_elev=None):
     """The point half of PreProcess + both input projections (pwclo_model.py:54-67) as ONE C-ABI call
     (`elo_input_stage`: three launches).  point_cloud (B, 2N, >=3) -> (points (2B,N,3), xyz_proj (2B,H,W,3)), frame 1
-    of every batch element first.  Inference only (the reference wraps this stage in stop_gradient, :66-67)."""
-    return _ops.input_stage(point_cloud, T_trans, aug_frame, H_input, W_input)
+    of every batch element first.  Inference only (the reference wraps this stage in stop_gradient, :66-67).
+    `sensor`: field of view, crop and -- with a beam table -- the row rule (`elo_input_stage_beams`); `beam_elev`: that table on
+    the device, kept by whoever captures this call (_ops.input_stage)."""
+    return _ops.input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=sensor, beam_elev=beam_elev)

@@ -149,7 +149,8 @@ def _pose_head(feat_b1c, level, coarse, is_training, raw=False):
     return (q if raw else _normalise_q(q)), t
 
 
-def _estimate_pose(predict, weight, xyz, level, q_coarse, t_coarse, is_training, pose7=None, clear=None, warp=None, partials=None):
+def _estimate_pose(predict, weight, xyz, level, q_coarse, t_coarse, is_training, pose7=None, clear=None, warp=None, partials=None,
+                   sensor=None):
     """softmax_valid + pose head + composition with the coarse pose (q_coarse None at l3).
     Returns (q (B,4), t (B,3), q_norm (B,4)): the level's pose and its final normalisation (:427-430).
     Inference: two fused HIP launches (_ops.pose_head).  Training: the literal operator chain."""
@@ -163,7 +164,8 @@ def _estimate_pose(predict, weight, xyz, level, q_coarse, t_coarse, is_training,
         # the l0 head is the last launch of a forward: in a graph captured with fresh_orders it also loads the NEXT replay's orders
         from . import perm
         nxt = perm.tail_refresh_args() if level == 0 else None
-        return _ops.pose_head(predict, weight, xyz, W_big, b_big, W_q, b_q, W_t, b_t, q_coarse, t_coarse, pose7, clear, warp, nxt, partials)
+        return _ops.pose_head(predict, weight, xyz, W_big, b_big, W_q, b_q, W_t, b_t, q_coarse, t_coarse, pose7, clear, warp, nxt, partials,
+                              sensor=sensor)
     summed = softmax_valid(feature_bnc=predict, weight_bnc=weight, mask_valid=xyz)                  # :194 / :262
     if predict.is_cuda and pose7 is None:
         # the pose algebra of :206-208 / :271-280 in ONE launch forward and one backward (_ops.pose_compose; the literal chain
@@ -186,11 +188,12 @@ def _estimate_pose(predict, weight, xyz, level, q_coarse, t_coarse, is_training,
     return q, t, q_norm
 
 
-def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training, bn_decay=None, pose_out=None):
+def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training, bn_decay=None, pose_out=None, sensor=None):
     """pwclo_model.py:69-433 from the projected inputs on.
     Returns (l0_q_norm, l0_t, l1_q_norm, l1_t, l2_q_norm, l2_t, l3_q_norm, l3_t, l0_xyz_f1).
     `pose_out` (B,7), if given, also receives [l0_q_norm | l0_t] (written by the l0 pose-head kernel: the row a
-    caller logs per frame pair, main.py:557-572)."""
+    caller logs per frame pair, main.py:557-572).
+    `sensor` (sensor.Sensor; None: the reference's HDL-64E): the field of view of the three warp re-projections."""
     batch_size, H_input, W_input, _ = xyz_f1_input_proj.shape
     dev = xyz_f1_input_proj.device
     out_h_list, out_w_list = pyramid_sizes(H_input, W_input)
@@ -328,7 +331,7 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
                                       **({"sv": sv3} if sv3 is not None else {}))
     l3_cost_volume_w_proj = l3_cost_volume_w.reshape(batch_size, out_h_list[5], out_w_list[5], -1)
     l3_q, l3_t, l3_q_norm = _estimate_pose(l3_points_predict, l3_cost_volume_w, l3_xyz_f1, 3, None, None,
-                                           is_training, clear=next_buffers, warp=next_warp(2), partials=sv3)             # :194-208
+                                           is_training, clear=next_buffers, warp=next_warp(2), partials=sv3, sensor=sensor)  # :194-208
 
     # three warp-refinement levels (:211-425); one loop instead of three pasted blocks
     cv_kernel2 = {2: [5, 15], 1: [7, 25], 0: [11, 41]}                                              # :243,:317,:391
@@ -341,7 +344,7 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
         xyz_f1 = xyz_proj_f1[level].reshape(batch_size, -1, 3)
         # warp by the coarse pose, zero invalid points, re-project with the level's features (:217-236)
         _warped, xyz_warp_proj_f1, points_warp_proj_f1 = warp_and_project(
-            xyz_f1, pts_f1[level], q_coarse, t_coarse, out_h_list[g], out_w_list[g], next_buffers)
+            xyz_f1, pts_f1[level], q_coarse, t_coarse, out_h_list[g], out_w_list[g], next_buffers, sensor=sensor)
         if PROJECTION_TAP is not None and next_buffers is not None:      # (parity tests: the cell every warped point landed in)
             PROJECTION_TAP.append((level, next_buffers.scratch, batch_size, xyz_f1.shape[1], out_h_list[g], out_w_list[g], xyz_warp_proj_f1, _warped))
         next_buffers = projection_buffers(level - 1, g - 1) if level > 0 else None
@@ -419,7 +422,7 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
         q_prev, t_prev, q_norm = _estimate_pose(predict, weight, xyz_warp_f1, level, q_coarse, t_coarse,
                                                 is_training, pose_out if level == 0 else None,
                                                 clear=next_buffers,
-                                                warp=next_warp(level - 1) if level > 0 else None, partials=sv)  # :262-280
+                                                warp=next_warp(level - 1) if level > 0 else None, partials=sv, sensor=sensor)  # :262-280
         poses[level] = (q_norm, t_prev)
 
         coarse_w_proj = weight.reshape(batch_size, out_h_list[g], out_w_list[g], -1)                # :256-257
@@ -431,18 +434,20 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
             l0_xyz_f1)                                                                              # :427-433
 
 
-def get_model(point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training, bn_decay=None, aug_frame=None):
+def get_model(point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training, bn_decay=None, aug_frame=None, sensor=None,
+              beam_elev=None):
     """pwclo_model.py:30-433 with the reference's signature: point_cloud (B, 2*N, >=3), three (B,4,4).
-    Returns the reference's 11-tuple."""
+    Returns the reference's 11-tuple.  `sensor` / `beam_elev`: as model_util.input_stage; the pyramid below projects with the
+    sensor's field of view."""
     batch_size = point_cloud.shape[0]
     if aug_frame is None:
         aug_frame = np.random.choice([1, 2], size=batch_size, replace=True)                         # :59
     with torch.no_grad():                                                                           # tf.stop_gradient, :66-67
         # PreProcess's crop + augmentation and both ProjectPC2SphericalRing calls in one C-ABI call (three launches)
-        _points, both = input_stage(point_cloud, T_trans, aug_frame, H_input, W_input)
+        _points, both = input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=sensor, beam_elev=beam_elev)
         xyz_f1_proj, xyz_f2_proj = both[:batch_size], both[batch_size:]         # adjacent: one 2B Siamese batch
         q_gt, t_gt = preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame)
-    out = get_model_from_projection(xyz_f1_proj, xyz_f2_proj, is_training, bn_decay)
+    out = get_model_from_projection(xyz_f1_proj, xyz_f2_proj, is_training, bn_decay, sensor=sensor)
     return out + (q_gt, t_gt)
 
 

@@ -1,0 +1,94 @@
+"""The LiDAR's geometry as a value: vertical field of view, horizontal crop and -- optionally -- the calibrated elevation of
+every beam.  `Sensor()` is the HDL-64E of the reference (model_util.py:189-200: -24.8 / +2.0 degrees, 35 m crop,
+model_util.py:380); everything that projects takes `sensor=None` = that one.
+
+The uniform row formula  row = H - int(beta / vert_res + vert_off)  at the sensor's field of view is the rule of every projection
+(the level grids reuse the field of view with nLines = the level's H) except the raw-scan input stage of a
+sensor WITH a beam table: there a point goes to the row of the beam nearest in elevation (elo_input_stage_beams, include/elo.h),
+so every laser has its own row whatever the spacing of the blocks it is built from.
+"""
+import math
+
+
+class Sensor:
+    """Sensor(fov_up_deg=2.0, fov_down_deg=-24.8, crop_xy=35.0, beam_elevations_deg=None): frozen and hashable.
+    beam_elevations_deg: the elevation of every beam in degrees, row 0 (the highest) first, strictly descending; with a table
+    and no explicit field of view, fov_up / fov_down are its first / last entry."""
+    __slots__ = ("fov_up_deg", "fov_down_deg", "crop_xy", "beam_elevations_deg")
+
+    def __init__(self, fov_up_deg=None, fov_down_deg=None, crop_xy=35.0, beam_elevations_deg=None):
+        table = None
+        if beam_elevations_deg is not None:
+            table = tuple(float(e) for e in beam_elevations_deg)
+            if len(table) < 2:
+                raise ValueError("a beam table has at least two beams")
+            if not all(math.isfinite(e) for e in table):
+                raise ValueError("beam elevations must be finite")
+            if not all(a > b for a, b in zip(table, table[1:])):
+                raise ValueError("beam elevations must be strictly descending (row 0 is the highest beam)")
+        up = float(fov_up_deg) if fov_up_deg is not None else (table[0] if table else 2.0)
+        down = float(fov_down_deg) if fov_down_deg is not None else (table[-1] if table else -24.8)
+        crop = float(crop_xy)
+        if not (math.isfinite(up) and math.isfinite(down) and up > down):
+            raise ValueError("fov_up_deg must lie above fov_down_deg (got %r, %r)" % (up, down))
+        if not (crop > 0):
+            raise ValueError("crop_xy must be positive (got %r)" % (crop,))
+        for name, value in (("fov_up_deg", up), ("fov_down_deg", down), ("crop_xy", crop), ("beam_elevations_deg", table)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Sensor is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("Sensor is immutable")
+
+    def _key(self):
+        return (self.fov_up_deg, self.fov_down_deg, self.crop_xy, self.beam_elevations_deg)
+
+    def __eq__(self, other):
+        return isinstance(other, Sensor) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        table = "" if self.beam_elevations_deg is None else ", beam_elevations_deg=<%d beams>" % len(self.beam_elevations_deg)
+        return "Sensor(fov_up_deg=%r, fov_down_deg=%r, crop_xy=%r%s)" % (self.fov_up_deg, self.fov_down_deg, self.crop_xy, table)
+
+    def beam_elevations_rad(self):
+        """The table in radians (python doubles), or None."""
+        if self.beam_elevations_deg is None:
+            return None
+        return tuple(e * (math.pi / 180) for e in self.beam_elevations_deg)
+
+    def row_elevations_deg(self, H):
+        """The elevation a generator gives row h of an H-row image: the table (which must have H beams), else H beams spread
+        evenly from fov_up to fov_down."""
+        if self.beam_elevations_deg is not None:
+            if len(self.beam_elevations_deg) != H:
+                raise ValueError("the sensor has %d beams, the image %d rows" % (len(self.beam_elevations_deg), H))
+            return self.beam_elevations_deg
+        return tuple(self.fov_up_deg - h * (self.fov_up_deg - self.fov_down_deg) / max(H - 1, 1) for h in range(H))
+
+
+KITTI_HDL64 = Sensor()
+
+
+def resolve(sensor):
+    """sensor=None is the reference's sensor."""
+    if sensor is None:
+        return KITTI_HDL64
+    if not isinstance(sensor, Sensor):
+        raise TypeError("sensor is a Sensor or None (got %r)" % (type(sensor).__name__,))
+    return sensor
+
+
+def projection_constants(H_input, W_input, sensor=None):
+    """model_util.py:189-200 at the sensor's field of view: python doubles (cast to float32 by the ctypes struct).  The
+    arithmetic and its order are the reference's, so the default sensor gives the reference's three floats exactly."""
+    s = resolve(sensor)
+    d2r = math.pi / 180
+    az = (360.0 / W_input) * d2r
+    down, up = s.fov_down_deg * d2r, s.fov_up_deg * d2r
+    vres = (up - down) / (H_input - 1)
+    return az, vres, -down / vres

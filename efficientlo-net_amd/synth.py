@@ -17,8 +17,11 @@ FOV_DOWN_DEG = -24.8      # model_util.py:192
 
 
 def range_image(H=64, W=1800, seed=0, yaw=0.0, shift=(0.0, 0.0, 0.0), hole_rate=0.05,
-                noise=0.02, crop=35.0, dtype=np.float32, profile="dense", scene_seed=None):
+                noise=0.02, crop=35.0, dtype=np.float32, profile="dense", scene_seed=None, sensor=None):
     """One (H, W, 3) xyz range image.
+
+    `sensor` (sensor.Sensor; None: the Velodyne-64-like default above): row h looks along the sensor's beam h -- its beam
+    table (H beams), else H beams spread evenly over its field of view -- and the crop is the sensor's instead of `crop`.
 
     profile "dense" (default): the smooth scene with `hole_rate` uniform holes -- a 95 %-filled grid, the best case for
     every kernel regime.  profile "kitti": the DENSITY of a projected HDL-64 scan after the 35 m crop (kitti_dataset.py:38-103
@@ -33,7 +36,14 @@ def range_image(H=64, W=1800, seed=0, yaw=0.0, shift=(0.0, 0.0, 0.0), hole_rate=
     h = np.arange(H, dtype=np.float64)[:, None]
     w = np.arange(W, dtype=np.float64)[None, :]
     az = math.pi - (w + 0.5) * (2.0 * math.pi / W) + yaw
-    el = np.deg2rad(FOV_UP_DEG - h * (FOV_UP_DEG - FOV_DOWN_DEG) / max(H - 1, 1))
+    if sensor is None:
+        el = np.deg2rad(FOV_UP_DEG - h * (FOV_UP_DEG - FOV_DOWN_DEG) / max(H - 1, 1))
+    else:
+        crop = sensor.crop_xy
+        if sensor.beam_elevations_deg is not None:
+            el = np.deg2rad(np.asarray(sensor.row_elevations_deg(H), dtype=np.float64))[:, None]
+        else:
+            el = np.deg2rad(sensor.fov_up_deg - h * (sensor.fov_up_deg - sensor.fov_down_deg) / max(H - 1, 1))
     el = np.broadcast_to(el, (H, W))
     az = np.broadcast_to(az, (H, W))
     wall = 20.0 + 5.0 * np.sin(3.0 * az)
@@ -67,6 +77,7 @@ def range_image(H=64, W=1800, seed=0, yaw=0.0, shift=(0.0, 0.0, 0.0), hole_rate=
 def frame_pair(B=1, H=64, W=1800, seed=0, starved=None, **kw):
     """(B,H,W,3) x2: frame 2 is the same scene seen after a small ego-motion
     (yaw 0.01 rad, 0.8 m forward), with its own noise/holes (seed+1).
+    Keywords go to range_image (`sensor=` among them).
     `starved` (default: True for profile "kitti" with B >= 2): the LAST batch element keeps only a 2 x 3 patch of valid pixels
     in each frame -- fewer valid points than any operator's K at every level, none at the coarse ones: the all-masked /
     empty-element paths of a batch (model_util.py:319-343 softmax_valid over no valid point, pointnet_util.py:92-98)."""

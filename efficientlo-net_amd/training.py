@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _ops, kitti, model_util, perm, pwclo_model, tf_checkpoint, tf_util
+from . import sensor as sensor_mod
 from .distributed import FlatGradBucket
 from .model import graph_capture
 
@@ -88,7 +89,7 @@ def kitti_batches(root, seqs, T_diffs, batch_size, rng, num_points=150000, augme
         yield cloud, T_gt, T_trans, T_trans_inv, aug_frame
 
 
-def train_epoch(trainer, batches, graph=True, H_input=64, W_input=1800):
+def train_epoch(trainer, batches, graph=True, H_input=64, W_input=1800, sensor=None):
     """Drive `trainer` over `batches` (an iterable of kitti_batches tuples, all of one shape): returns (mean loss over the
     batches, optimisation steps taken = what `trainer.step_count` advanced by).
     Each batch goes through one of TWO pinned host staging sets and from there to the device with non_blocking copies, so
@@ -97,6 +98,7 @@ def train_epoch(trainer, batches, graph=True, H_input=64, W_input=1800):
     `graph`: `step_graph_points` (the trainer is capturable), else `step_points`.  One step per batch -- except where
     `step_graph_points` has to record a graph (none from clouds yet, or the BN-decay schedule moved): the warm-up steps of a
     capture are optimisation steps on that batch, and the count returned includes them, as `step_count` does.
+    `sensor` (sensor.Sensor; None: the trainer's net's): the LiDAR the scans come from (`Trainer.step_points`).
     No evaluation and no checkpoint policy here."""
     dev = trainer.net.device
     step = trainer.step_graph_points if graph else trainer.step_points
@@ -118,7 +120,7 @@ def train_epoch(trainer, batches, graph=True, H_input=64, W_input=1800):
         stage(0, batch)
     while batch is not None:
         slot = steps % 2
-        total += step(*sets[slot], H_input=H_input, W_input=W_input).reshape(())   # async: copies out of the set + the step
+        total += step(*sets[slot], H_input=H_input, W_input=W_input, sensor=sensor).reshape(())   # async: copies out of the set + the step
         done[slot] = done[slot] or torch.cuda.Event()
         done[slot].record(torch.cuda.current_stream(dev))
         steps += 1
@@ -240,6 +242,21 @@ class Trainer:
         self.bucket = FlatGradBucket(self.params)
         self.opt = FlatAdam(self.params, self.bucket, lr=BASE_LEARNING_RATE)   # main.py:174; one launch per step, capturable as it is
         self.step_count = 0
+        self._sensor = net.sensor                                        # whose field of view the step's projections use
+        self._beam_tables = {}                                           # sensor -> its beam table on the device, kept for the graphs
+
+    def _use_sensor(self, sensor):
+        """The sensor of the steps from here on (None: the net's) and its beam table on the device (or None).  The trainer owns
+        the tables: a captured step keeps the pointer of the one it was recorded with."""
+        sensor = self.net.sensor if sensor is None else sensor_mod.resolve(sensor)
+        self._sensor = sensor
+        if sensor.beam_elevations_deg is None:
+            return sensor, None
+        if sensor == self.net.sensor:
+            return sensor, self.net.beam_elev
+        if sensor not in self._beam_tables:
+            self._beam_tables[sensor] = _ops.beam_table(sensor, len(sensor.beam_elevations_deg), self.net.device)
+        return sensor, self._beam_tables[sensor]
 
     def _global_batch(self, B):
         """Samples per step over all ranks: the staircase schedules of main.py:120-138 count samples seen."""
@@ -254,7 +271,7 @@ class Trainer:
         self.bucket.release()
         with torch.enable_grad():
             with tf_util.default_store(self.net.store), perm.default_perm_source(self.net.perms):
-                out = pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, True, decay)
+                out = pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, True, decay, sensor=self._sensor)
             loss = pwclo_model.get_loss(*out[:8], q_gt, t_gt, self.w_x, self.w_q)
             loss.backward()
         self.bucket.collect()
@@ -279,18 +296,23 @@ class Trainer:
 
     def step(self, xyz_f1_proj, xyz_f2_proj, q_gt, t_gt):
         """One optimisation step on this rank's batch; returns the (local) loss."""
+        self._use_sensor(None)                                           # range images in: the net's sensor projects the warps
         return self._eager(xyz_f1_proj.shape[0], _as_given, (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt))
 
     # -- the step from raw clouds ------------------------------------------------
-    def _stage(self, H_input, W_input):
+    def _stage(self, H_input, W_input, sensor=None):
         """The front of a step from clouds (main.py:362-368 feeds, pwclo_model.py:54-67 + model_util.py:346-445 compute):
         `elo_input_stage` (crop, augmentation, both projections; three launches, no gradient -- tf.stop_gradient, :66-67)
         and `elo_preprocess_gt` (one launch) -> what `_body` takes.  Every input is a device tensor, `aug_frame` included:
-        recorded into a graph, the four launches read whatever the static buffers hold at replay time."""
+        recorded into a graph, the four launches read whatever the static buffers hold at replay time.  `sensor` (None: the
+        net's): crop, field of view and, with a beam table, the input stage's row rule; the pyramid behind it projects with it too."""
+        sensor, beam_elev = self._use_sensor(sensor)
+
         def prologue(cloud, T_gt, T_trans, T_trans_inv, aug_frame):
             B = cloud.shape[0]
             with torch.no_grad():
-                _points, staged = model_util.input_stage(cloud, T_trans, aug_frame, H_input, W_input)
+                _points, staged = model_util.input_stage(cloud, T_trans, aug_frame, H_input, W_input, sensor=sensor,
+                                                         beam_elev=beam_elev)
                 q_gt, t_gt = _ops.preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame)
             return staged[:B], staged[B:], q_gt, t_gt
         return prologue
@@ -318,14 +340,15 @@ class Trainer:
                 s.copy_(x, non_blocking=True)
         return static
 
-    def step_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800):
+    def step_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800, sensor=None):
         """`step` from what the reference's training loop feeds (main.py:362-368): point_cloud (B, 2N, S>=3) -- the layout
         evaluate.predict_sequence builds -- T_gt and, for augmentation, T_trans / T_trans_inv (B,4,4) with `aug_frame` (B) of
-        1 / 2 (array-like, or int32 on the device).  Crop, augmentation, both projections and q_gt / t_gt run on the device."""
+        1 / 2 (array-like, or int32 on the device).  Crop, augmentation, both projections and q_gt / t_gt run on the device.
+        `sensor` (sensor.Sensor; None: the net's): see `_stage`."""
         dev = self.net.device
         inputs = [None if x is None else x.to(device=dev, dtype=torch.int32 if i == 4 else torch.float32, non_blocking=True)
                   for i, x in enumerate(self._point_inputs(point_cloud, T_gt, T_trans, T_trans_inv, aug_frame))]
-        return self._eager(point_cloud.shape[0], self._stage(H_input, W_input), inputs)
+        return self._eager(point_cloud.shape[0], self._stage(H_input, W_input, sensor), inputs)
 
     # -- the step as ONE hipGraph ----------------------------------------------
     def capture(self, xyz_f1_proj, xyz_f2_proj, q_gt, t_gt, warmup=3):
@@ -335,21 +358,22 @@ class Trainer:
         graph reads; the BN decay is baked in, so `step_graph` re-captures when the schedule moves it (every 200 000
         samples, main.py:130-138)."""
         self._need_capturable()
+        self._use_sensor(None)
         static = [torch.empty_like(x) for x in (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)]
         for s, x in zip(static, (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt)):
             s.copy_(x)
         return self._capture(("projections",), static, _as_given, xyz_f1_proj.shape[0], warmup)
 
     def capture_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800,
-                       warmup=3):
+                       warmup=3, sensor=None):
         """`capture` for the step from clouds: the static inputs are the cloud, the three matrices and the device `aug_frame`;
         the input stage and `elo_preprocess_gt` are recorded in front of `_body` in the same graph (with several ranks: in the
         first of the two), so a replay draws its crop, augmentation, projections and targets from whatever `step_graph_points`
-        copied in.  A graph recorded without T_trans has no augmentation in it."""
+        copied in.  A graph recorded without T_trans has no augmentation in it; the `sensor` (None: the net's) is baked in."""
         self._need_capturable()
         inputs = self._point_inputs(point_cloud, T_gt, T_trans, T_trans_inv, aug_frame)
-        kind = ("points", H_input, W_input, T_trans is not None)
-        return self._capture(kind, self._point_statics(inputs), self._stage(H_input, W_input), point_cloud.shape[0], warmup)
+        kind = ("points", H_input, W_input, T_trans is not None, self.net.sensor if sensor is None else sensor)
+        return self._capture(kind, self._point_statics(inputs), self._stage(H_input, W_input, sensor), point_cloud.shape[0], warmup)
 
     def _need_capturable(self):
         if not self.capturable:
@@ -417,12 +441,14 @@ class Trainer:
         return self._step_graph(("projections",), (xyz_f1_proj, xyz_f2_proj, q_gt, t_gt), xyz_f1_proj.shape[0],
                                 lambda warmup: self.capture(xyz_f1_proj, xyz_f2_proj, q_gt, t_gt, warmup=warmup))
 
-    def step_graph_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800):
+    def step_graph_points(self, point_cloud, T_gt, T_trans=None, T_trans_inv=None, aug_frame=None, H_input=64, W_input=1800,
+                          sensor=None):
         """`step_points` through the captured graph (same shapes as `capture_points`): five copies into the static buffers --
-        asynchronous from pinned host memory -- and one replay."""
+        asynchronous from pinned host memory -- and one replay.  Another `sensor` than the recorded one records a new graph."""
         inputs = self._point_inputs(point_cloud, T_gt, T_trans, T_trans_inv, aug_frame)
-        return self._step_graph(("points", H_input, W_input, T_trans is not None), inputs, point_cloud.shape[0],
-                                lambda warmup: self.capture_points(*inputs, H_input=H_input, W_input=W_input, warmup=warmup))
+        kind = ("points", H_input, W_input, T_trans is not None, self.net.sensor if sensor is None else sensor)
+        return self._step_graph(kind, inputs, point_cloud.shape[0],
+                                lambda warmup: self.capture_points(*inputs, H_input=H_input, W_input=W_input, warmup=warmup, sensor=sensor))
 
     # -- checkpoints -----------------------------------------------------------
     def save(self, path, tf_bundle=False):

@@ -389,6 +389,40 @@ typedef struct elo_input_stage_args {
 } elo_input_stage_args;
 int elo_input_stage(const elo_input_stage_args *a, elo_stream_t stream);
 
+/* elo_input_stage for a sensor with a calibrated BEAM TABLE: the same three launches, crop, T_trans / aug_frame, point_stride,
+ * minimum-range winner per cell with duplicates summed, scratch layout and stacked outputs -- only the ROW of a point differs.
+ * Instead of the uniform formula (which lets the beams of an unevenly spaced sensor share rows and leaves other rows empty)
+ *   row = the beam nearest in elevation to beta = asin(z / r)
+ *       = the number of midpoints  m_k = (beam_elev[k] + beam_elev[k+1]) / 2,  k = 0 .. H-2,  that lie above beta:
+ * above the top midpoint row 0, below the bottom one row H-1.  The kernel compares z / r with sin(m_k) (monotone, no asinf),
+ * H-1 sines staged per workgroup in LDS, by a branch-free binary search; a point within 4 float32 ulps (of z / r) of a midpoint
+ * may take either neighbouring row.  A zero point (r = 0, z / r = NaN) counts every midpoint as above it -- the comparison is
+ * written !(s >= m_k) -- and lands in row H-1, where the formula's NaN -> 0 conversion puts it too; its column follows atan2 as
+ * before, so the three zero cells and the blanking convention of elo_warp_project hold unchanged.
+ * beam_elev: H floats in DEVICE memory, radians, strictly descending (row 0 is the highest beam); the order is the caller's to
+ * guarantee (efficientlo-net_amd/sensor.py validates the table it is built from), the entry checks what the host can see:
+ * H <= ELO_MAX_BEAMS, a non-NULL table, the sizes and pairings elo_input_stage checks.  On ELO_ERR_ARG nothing is launched.
+ * LIFETIME: the launches read beam_elev when they RUN.  A captured graph bakes the pointer in: the table stays alive and
+ * unchanged for as long as a graph recorded with it may be replayed -- the rule of every other buffer a captured launch names
+ * (elo_graph_submit); efficientlo-net_amd keeps it as a tensor owned by the net / trainer whose graphs read it.
+ * Additive to ABI 26: no existing struct changes. */
+#define ELO_MAX_BEAMS 256
+typedef struct elo_input_stage_beams_args {
+    int batch, npoints;           /* points per frame */
+    int point_stride;             /* floats per point in `cloud` (>= 3) */
+    int H, W;                     /* H = number of beams, 1 .. ELO_MAX_BEAMS */
+    float az_res;                 /* as in elo_warp_project_args */
+    float crop_xy;
+    const float *cloud;           /* (batch, 2*npoints, point_stride) */
+    const float *T_trans;         /* (batch,4,4) row-major, or NULL = no augmentation */
+    const int *aug_frame;         /* (batch) 1 or 2 (NULL with T_trans == NULL) */
+    float *points;                /* (2*batch, npoints, 3) OUT */
+    float *out_xyz;               /* (2*batch, H, W, 3) OUT */
+    unsigned *scratch;            /* as elo_input_stage_args.scratch */
+    const float *beam_elev;       /* (H) radians, strictly descending */
+} elo_input_stage_beams_args;
+int elo_input_stage_beams(const elo_input_stage_beams_args *a, elo_stream_t stream);
+
 /* The ground-truth half of PreProcess (model_util.py:403, :419, :427-445) in ONE launch, one thread per batch element:
  *   T = T_trans . T_gt      where aug_frame[b] == 2  (:403)
  *   T = T_gt . T_trans_inv  where aug_frame[b] == 1  (:419)
