@@ -7,4 +7,4 @@ The directory name contains a hyphen; import it with
     importlib.import_module("efficientlo-net_amd")
 """
 from .fused_conv import fused_conv_random_k, fused_conv_select_k  # noqa: F401
-from .sensor import KITTI_HDL64, Sensor  # noqa: F401
+from .sensor import KITTI_HDL64, Sensor, Sweep  # noqa: F401

@@ -74,6 +74,13 @@ InputStageBeamsArgs = _struct("elo_input_stage_beams_args", [
     ("batch", _i), ("npoints", _i), ("point_stride", _i), ("H", _i), ("W", _i), ("az_res", _f), ("crop_xy", _f), ("cloud", _vp),
     ("T_trans", _vp), ("aug_frame", _vp), ("points", _vp), ("out_xyz", _vp), ("scratch", _vp), ("beam_elev", _vp)])
 MAX_BEAMS = 256        # ELO_MAX_BEAMS
+InputStageDeskewArgs = _struct("elo_input_stage_deskew_args", [
+    ("batch", _i), ("npoints", _i), ("point_stride", _i), ("H", _i), ("W", _i), ("az_res", _f), ("vert_res", _f), ("vert_off", _f),
+    ("crop_xy", _f), ("cloud", _vp), ("T_trans", _vp), ("aug_frame", _vp), ("points", _vp), ("out_xyz", _vp), ("scratch", _vp),
+    ("beam_elev", _vp), ("motion", _vp), ("motion2", _vp), ("invert", _i), ("phase_mode", _i), ("phase_channel", _i),
+    ("phase_ref", _f)])
+PHASE_CHANNEL, PHASE_AZIMUTH = 0, 1        # ELO_PHASE_*
+DESKEW_MAX_BATCH = 512                     # ELO_DESKEW_MAX_BATCH
 PreprocessGtArgs = _struct("elo_preprocess_gt_args", [
     ("batch", _i), ("T_gt", _vp), ("T_trans", _vp), ("T_trans_inv", _vp), ("aug_frame", _vp), ("q_gt", _vp), ("t_gt", _vp)])
 
@@ -187,6 +194,7 @@ SYMBOLS = [
     ("elo_warp_project", ctypes.c_int, [ctypes.POINTER(WarpProjectArgs), _vp]),
     ("elo_input_stage", ctypes.c_int, [ctypes.POINTER(InputStageArgs), _vp]),
     ("elo_input_stage_beams", ctypes.c_int, [ctypes.POINTER(InputStageBeamsArgs), _vp]),
+    ("elo_input_stage_deskew", ctypes.c_int, [ctypes.POINTER(InputStageDeskewArgs), _vp]),
     ("elo_preprocess_gt", ctypes.c_int, [ctypes.POINTER(PreprocessGtArgs), _vp]),
     ("elo_pose_head_warp", ctypes.c_int, [ctypes.POINTER(PoseHeadArgs), ctypes.POINTER(WarpProjectArgs), _vp]),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),

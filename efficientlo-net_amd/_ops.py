@@ -543,7 +543,40 @@ def beam_table(table, H, device):
     return torch.from_numpy(host).to(device)
 
 
-def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam_elev=None):
+def _motion_dev(motion, B, dev, name):
+    """(B,7) float32 on `dev`: a contiguous float32 tensor that already lives there is passed through (same memory: its pointer is
+    what the launch -- and a graph that records it -- reads), anything else is converted and copied (not inside a capture)."""
+    if isinstance(motion, torch.Tensor) and motion.is_cuda:
+        if motion.device == dev and motion.dtype == torch.float32 and motion.is_contiguous() and tuple(motion.shape) == (B, 7):
+            return motion
+    if torch.cuda.is_current_stream_capturing():
+        raise L.EloError("a graph capture needs `%s` as a contiguous float32 (B,7) tensor on the cloud's device" % name)
+    if not isinstance(motion, torch.Tensor):
+        motion = torch.from_numpy(np.ascontiguousarray(np.asarray(motion, dtype=np.float32)))
+    if motion.numel() != B * 7:
+        raise L.EloError("`%s` is one [q0 q1 q2 q3 | t0 t1 t2] row per batch element: (%d, 7) (got %s)" % (name, B, tuple(motion.shape)))
+    return motion.to(device=dev, dtype=torch.float32).reshape(B, 7).contiguous()
+
+
+def _check_sweep(sweep, motion, motion2, motion_is_pose, cloud):
+    """input_stage's sweep and motion come together; the phase channel exists in the cloud; the batch fits the kernel's staging."""
+    if sweep is None:
+        if motion is not None or motion2 is not None or motion_is_pose:
+            raise L.EloError("a motion without a sweep: pass sweep=Sweep(...) to say when each point was acquired")
+        return
+    if not isinstance(sweep, _sensor.Sweep):
+        raise TypeError("sweep is a Sweep or None (got %r)" % (type(sweep).__name__,))
+    if motion is None:
+        raise L.EloError("a sweep without a motion: pass motion=(B,7) rows [q | t] (the identity row is 1 0 0 0 0 0 0)")
+    if sweep.phase != "azimuth" and sweep.phase >= cloud.shape[-1]:
+        raise L.EloError("the sweep's phase is channel %d, the cloud has %d floats per point" % (sweep.phase, cloud.shape[-1]))
+    if cloud.shape[0] > L.DESKEW_MAX_BATCH:
+        raise L.EloError("elo_input_stage_deskew stages the motions of at most %d batch elements (got %d)"
+                         % (L.DESKEW_MAX_BATCH, cloud.shape[0]))
+
+
+def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam_elev=None, sweep=None, motion=None, motion2=None,
+                motion_is_pose=False):
     """elo_input_stage: cloud (B, 2N, S>=3) fp32, T_trans (B,4,4) or None, aug_frame (B) of 1/2 (array-like, or an int32
     tensor already on the cloud's device: its pointer is what the launch -- and a graph that records it -- reads) ->
     (points (2B,N,3), xyz_proj (2B,H,W,3)).
@@ -551,13 +584,26 @@ def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam
     a beam table -- or an explicit `beam_elev` -- takes elo_input_stage_beams: the row of a point is the beam nearest in
     elevation.  `beam_elev`: that table as a float32 tensor on the cloud's device (beam_table(); used as it is -- its owner
     validated it and keeps it alive for every graph that recorded this call), or a host array-like of radians (validated and
-    uploaded here: not inside a graph capture)."""
+    uploaded here: not inside a graph capture).
+    `sweep` (sensor.Sweep) with `motion`: the scan is NOT motion-compensated -- elo_input_stage_deskew first carries every point
+    from its acquisition phase (sweep.phase: "azimuth", or the channel of the cloud that holds it) to sweep.phase_ref by the
+    sensor's motion during the sweep, then does all of the above on the corrected cloud.  `motion`: (B,7) rows [q | t], the
+    transform from the sensor frame at the END of the sweep to the one at its START, for both frames; `motion2`: frame 2's, if
+    it differs.  `motion_is_pose`: the rows are the net's [q_norm | t] of the previous pair (frame 1 -> frame 2) and are inverted
+    in the kernel.  A contiguous float32 tensor on the cloud's device is used as it is and read when the launch RUNS (a graph that
+    records this call sees what it holds at every replay); anything else is uploaded here.  One without the other is an EloError;
+    with neither this is exactly the calls above."""
+    _check_sweep(sweep, motion, motion2, motion_is_pose, cloud)        # (what the host can refuse without a GPU, first)
     L.require_gpu(cloud, T_trans)
     (cloud,) = _f32(cloud)
     B, N2, S = cloud.shape
     if N2 % 2 or S < 3:
         raise ValueError("point_cloud must be (B, 2*N, >=3)")
     N, dev = N2 // 2, cloud.device
+    if sweep is not None:
+        motion = _motion_dev(motion, B, dev, "motion")
+        if motion2 is not None:
+            motion2 = _motion_dev(motion2, B, dev, "motion2")
     sensor = _sensor.resolve(sensor)
     if crop_xy is None:
         crop_xy = sensor.crop_xy
@@ -570,7 +616,15 @@ def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam
     az, vres, voff = projection_constants(H, W, sensor)
     tail = (cloud.data_ptr(), T_trans.data_ptr() if T_trans is not None else None,
             aug.data_ptr() if T_trans is not None else None, points.data_ptr(), out_xyz.data_ptr(), scratch.data_ptr())
+    if sweep is not None:
+        skew = (motion.data_ptr(), motion2.data_ptr() if motion2 is not None else None, 1 if motion_is_pose else 0,
+                L.PHASE_AZIMUTH if sweep.phase == "azimuth" else L.PHASE_CHANNEL, 0 if sweep.phase == "azimuth" else sweep.phase,
+                sweep.phase_ref)
     if beam_elev is None and sensor.beam_elevations_deg is None:
+        if sweep is not None:
+            a = L.InputStageDeskewArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), *tail, None, *skew)
+            L.call("elo_input_stage_deskew", a, out_xyz)
+            return points, out_xyz
         a = L.InputStageArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), *tail)
         L.call("elo_input_stage", a, out_xyz)
         return points, out_xyz
@@ -581,6 +635,10 @@ def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam
         if torch.cuda.is_current_stream_capturing():
             raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
         beam_elev = beam_table(beam_elev if beam_elev is not None else sensor, H, dev)
+    if sweep is not None:
+        a = L.InputStageDeskewArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), *tail, beam_elev.data_ptr(), *skew)
+        L.call("elo_input_stage_deskew", a, out_xyz)
+        return points, out_xyz
     a = L.InputStageBeamsArgs(B, N, S, H, W, az, float(crop_xy), *tail, beam_elev.data_ptr())
     L.call("elo_input_stage_beams", a, out_xyz)
     return points, out_xyz

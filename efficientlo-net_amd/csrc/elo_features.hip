@@ -1145,9 +1145,72 @@ __global__ __launch_bounds__(ELO_BLOCK) void warp_cell_kernel(const elo_warp_pro
 
 // pass A of the raw-cloud input stage for ONE point: PreProcess of point i of the stacked 2 * per_frame (model_util.py:346-422)
 // + binning.  Stacked index: frame f of batch element b is image f*batch + b.  Args: elo_input_stage_args /
-// elo_input_stage_beams_args (the same fields by name); Rows: the row rule the cell is taken by.
-template <class Args, class Rows>
-__device__ __forceinline__ void input_cell_point(const Args &a, const ProjScratch &ps, const Rows &rows, long i, long per_frame)
+// elo_input_stage_beams_args / elo_input_stage_deskew_args (the same fields by name); Rows: the row rule the cell is taken by;
+// Skew: what happens to the raw point before anything else (NoSkew: nothing -- the scan is one instant).
+struct NoSkew {
+    __device__ __forceinline__ void apply(float &, float &, float &, const float *, int) const {}
+};
+
+// SkewByMotion (elo_input_stage_deskew): p' = Rot(u, a theta) p + a t with a = s - phase_ref, s the point's acquisition phase.
+// `m` (LDS, stage_motion below): (u0 u1 u2 theta t0 t1 t2) per image.  One sincosf of a theta / 2 and the quaternion sandwich
+// p + 2 c (w x p) + 2 w x (w x p), (c, w) = (cos, sin . u); with theta = 0 or a = 0 every added term is a zero, so p' == p.  A
+// zero point (padding) is left alone, bits and signs.  In azimuth mode the raw point's atan2f gives s (x 1 / 2 pi); the binning
+// takes its own of p'.
+struct SkewByMotion {
+    const float *m;
+    int mode, channel;
+    float phase_ref;
+    __device__ __forceinline__ void apply(float &x, float &y, float &z, const float *p, int img) const
+    {
+        if (x == 0.0f && y == 0.0f && z == 0.0f) return;
+        const float PI_F = 3.14159265358979323846f, INV_2PI_F = 0.15915494309189533577f;
+        const float s = mode == ELO_PHASE_AZIMUTH ? (PI_F - atan2f(y, x)) * INV_2PI_F : p[channel];
+        const float a = s - phase_ref;
+        const float *e = m + img * 7;
+        float sn, c;
+        sincosf(0.5f * (a * e[3]), &sn, &c);
+        const float wx = sn * e[0], wy = sn * e[1], wz = sn * e[2];
+        const float cx = wy * z - wz * y, cy = wz * x - wx * z, cz = wx * y - wy * x;          // w x p
+        const float dx = wy * cz - wz * cy, dy = wz * cx - wx * cz, dz = wx * cy - wy * cx;    // w x (w x p)
+        const float c2 = 2.0f * c;
+        x = x + c2 * cx + 2.0f * dx + a * e[4];
+        y = y + c2 * cy + 2.0f * dy + a * e[5];
+        z = z + c2 * cz + 2.0f * dz + a * e[6];
+    }
+};
+
+// (u, theta, t) of the 2 * batch images into `m`, one thread per image: q normalised (a zero quaternion: no rotation), negated
+// where q0 < 0 (the shorter arc), the whole transform inverted where a.invert -- (q^-1, -q^-1 t q) --, theta = 2 atan2f(|v|, q0),
+// u = v / |v| (|v| = 0: u = 0, theta = 0).  The same instructions on the same rows in every workgroup: the same floats everywhere.
+template <class Args>
+__device__ __forceinline__ void stage_motion(const Args &a, float *m)
+{
+    for (int img = threadIdx.x; img < 2 * a.batch; img += blockDim.x) {
+        const int f = img >= a.batch, b = img - f * a.batch;
+        const float *row = (f && a.motion2 ? a.motion2 : a.motion) + b * 7;
+        float q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3], t0 = row[4], t1 = row[5], t2 = row[6];
+        const float n = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+        const float inv = (n > 0.0f ? 1.0f / n : 0.0f) * (q0 < 0.0f ? -1.0f : 1.0f);
+        q0 *= inv; q1 *= inv; q2 *= inv; q3 *= inv;
+        if (a.invert) {
+            q1 = -q1; q2 = -q2; q3 = -q3;
+            const float cx = q2 * t2 - q3 * t1, cy = q3 * t0 - q1 * t2, cz = q1 * t1 - q2 * t0;    // v x t, v of q^-1
+            const float dx = q2 * cz - q3 * cy, dy = q3 * cx - q1 * cz, dz = q1 * cy - q2 * cx;
+            t0 = -(t0 + 2.0f * q0 * cx + 2.0f * dx);
+            t1 = -(t1 + 2.0f * q0 * cy + 2.0f * dy);
+            t2 = -(t2 + 2.0f * q0 * cz + 2.0f * dz);
+        }
+        const float vn = sqrtf(q1 * q1 + q2 * q2 + q3 * q3);
+        const float iv = vn > 0.0f ? 1.0f / vn : 0.0f;
+        float *e = m + img * 7;
+        e[0] = q1 * iv; e[1] = q2 * iv; e[2] = q3 * iv; e[3] = 2.0f * atan2f(vn, q0);
+        e[4] = t0; e[5] = t1; e[6] = t2;
+    }
+}
+
+template <class Args, class Rows, class Skew>
+__device__ __forceinline__ void input_cell_point(const Args &a, const ProjScratch &ps, const Rows &rows, const Skew &skew, long i,
+                                                 long per_frame)
 {
     const int f = i >= per_frame;                                     // 0: frame 1, 1: frame 2
     const long j = i - f * per_frame;
@@ -1155,6 +1218,7 @@ __device__ __forceinline__ void input_cell_point(const Args &a, const ProjScratc
     const long n = j - (long)b * a.npoints;
     const float *p = a.cloud + ((long)b * 2 * a.npoints + (long)f * a.npoints + n) * a.point_stride;
     float x = p[0], y = p[1], z = p[2], w = 1.0f;
+    skew.apply(x, y, z, p, f * a.batch + b);
     const float valid = (x != 0.0f || y != 0.0f || z != 0.0f) ? 1.0f : 0.0f;                  // :357-363
     if (sqrtf(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y))) > a.crop_xy) x = y = z = w = 0.0f;   // :380-383 (no FMA: the
                                                                                               // threshold decides like numpy's)
@@ -1174,7 +1238,7 @@ __global__ __launch_bounds__(ELO_BLOCK) void input_cell_kernel(const elo_input_s
 {
     const long per_frame = (long)a.batch * a.npoints, total = 2 * per_frame;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-        input_cell_point(a, ps, RowsByFormula{a.vert_res, a.vert_off}, i, per_frame);
+        input_cell_point(a, ps, RowsByFormula{a.vert_res, a.vert_off}, NoSkew{}, i, per_frame);
 }
 
 // ... by beam table: every workgroup first stages the sines of the H-1 midpoints (one sinf per thread at most: H <= ELO_MAX_BEAMS
@@ -1188,7 +1252,35 @@ __global__ __launch_bounds__(ELO_BLOCK) void input_cell_beams_kernel(const elo_i
     __syncthreads();
     const long per_frame = (long)a.batch * a.npoints, total = 2 * per_frame;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-        input_cell_point(a, ps, RowsByBeams{mid, half}, i, per_frame);
+        input_cell_point(a, ps, RowsByBeams{mid, half}, NoSkew{}, i, per_frame);
+}
+
+// ... of a scan that is not motion-compensated (elo_input_stage_deskew): every workgroup first stages the motions of the 2 * batch
+// images (dynamic LDS, 7 floats each), the beams kernel its midpoints as above.
+__global__ __launch_bounds__(ELO_BLOCK) void input_cell_deskew_kernel(const elo_input_stage_deskew_args a, const ProjScratch ps)
+{
+    extern __shared__ float motion_lds[];
+    stage_motion(a, motion_lds);
+    __syncthreads();
+    const SkewByMotion skew{motion_lds, a.phase_mode, a.phase_channel, a.phase_ref};
+    const long per_frame = (long)a.batch * a.npoints, total = 2 * per_frame;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+        input_cell_point(a, ps, RowsByFormula{a.vert_res, a.vert_off}, skew, i, per_frame);
+}
+
+__global__ __launch_bounds__(ELO_BLOCK) void input_cell_deskew_beams_kernel(const elo_input_stage_deskew_args a, const ProjScratch ps,
+                                                                            const int half)
+{
+    __shared__ float mid[ELO_MAX_BEAMS];
+    extern __shared__ float motion_lds[];
+    for (int k = threadIdx.x; k < 2 * half - 1; k += blockDim.x)
+        mid[k] = k < a.H - 1 ? sinf(0.5f * (a.beam_elev[k] + a.beam_elev[k + 1])) : -INFINITY;
+    stage_motion(a, motion_lds);
+    __syncthreads();
+    const SkewByMotion skew{motion_lds, a.phase_mode, a.phase_channel, a.phase_ref};
+    const long per_frame = (long)a.batch * a.npoints, total = 2 * per_frame;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+        input_cell_point(a, ps, RowsByBeams{mid, half}, skew, i, per_frame);
 }
 
 // The ground-truth half of PreProcess (model_util.py:403, :419, :427-445): one thread per batch element.  fp32 in, double in
@@ -1623,6 +1715,38 @@ extern "C" int elo_input_stage_beams(const elo_input_stage_beams_args *a, elo_st
     hipStream_t s = (hipStream_t)stream;
     return input_stage_launches(a, 1.0f, 0.0f, s, who, [&](dim3 grid, const ProjScratch &ps) {
         hipLaunchKernelGGL(input_cell_beams_kernel, grid, dim3(ELO_BLOCK), 0, s, *a, ps, half);
+    });
+}
+
+extern "C" int elo_input_stage_deskew(const elo_input_stage_deskew_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_input_stage_deskew";
+    ELO_REQUIRE(a, who, "null argument block");
+    ELO_REQUIRE(a->batch >= 0 && a->npoints > 0 && a->H > 0 && a->W > 0 && a->point_stride >= 3, who, "bad sizes");
+    ELO_REQUIRE(a->batch <= ELO_DESKEW_MAX_BATCH, who, "batch above ELO_DESKEW_MAX_BATCH");
+    ELO_REQUIRE(!a->beam_elev || a->H <= ELO_MAX_BEAMS, who, "more beams than ELO_MAX_BEAMS");
+    ELO_REQUIRE((a->T_trans == nullptr) == (a->aug_frame == nullptr), who, "T_trans and aug_frame come together");
+    ELO_REQUIRE(a->az_res > 0.0f && (a->beam_elev || a->vert_res > 0.0f), who, "bad projection constants");
+    ELO_REQUIRE(a->crop_xy == a->crop_xy, who, "crop_xy is NaN");
+    ELO_REQUIRE(a->motion, who, "null motion");
+    ELO_REQUIRE(a->invert == 0 || a->invert == 1, who, "invert is 0 or 1");
+    ELO_REQUIRE(a->phase_mode == ELO_PHASE_CHANNEL || a->phase_mode == ELO_PHASE_AZIMUTH, who, "unknown phase_mode");
+    ELO_REQUIRE(a->phase_mode != ELO_PHASE_CHANNEL || (a->phase_channel >= 3 && a->phase_channel < a->point_stride), who,
+                "phase_channel outside 3 .. point_stride - 1");
+    ELO_REQUIRE(a->phase_ref - a->phase_ref == 0.0f, who, "phase_ref is not finite");
+    if (a->batch == 0) return ELO_OK;
+    ELO_REQUIRE(a->cloud && a->points && a->out_xyz && a->scratch, who, "null tensor pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lds = 2 * (size_t)a->batch * 7 * sizeof(float);         // <= 28 KB beside the 1 KB of midpoints
+    if (!a->beam_elev)
+        return input_stage_launches(a, a->vert_res, a->vert_off, s, who, [&](dim3 grid, const ProjScratch &ps) {
+            hipLaunchKernelGGL(input_cell_deskew_kernel, grid, dim3(ELO_BLOCK), lds, s, *a, ps);
+        });
+    int half = 0;                                     // as elo_input_stage_beams
+    while (2 * half < a->H) half = half ? 2 * half : 1;
+    if (a->H == 1) half = 0;
+    return input_stage_launches(a, 1.0f, 0.0f, s, who, [&](dim3 grid, const ProjScratch &ps) {
+        hipLaunchKernelGGL(input_cell_deskew_beams_kernel, grid, dim3(ELO_BLOCK), lds, s, *a, ps, half);
     });
 }
 

@@ -36,7 +36,7 @@ def pose_rows(q_n4, t_n3, Tr):
 
 
 def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_size=1, num_points=150000, frames=None,
-                     lanes=0, sensor=None):
+                     lanes=0, sensor=None, sweep=None):
     """Run the network over samples `frames` (default: all scans found) of sequence `seq`; returns (q (n,4), t (n,3))
     = the l0 pose of every sample, in sample order.  Batches are padded by repeating the last sample
     (main.py:497-509 keeps stale rows instead; either way the padding rows are dropped).
@@ -44,7 +44,13 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     stage + pyramid in one replay, several batches in flight while the host reads the next scans) instead of the eager
     `forward_points`; same results (no augmentation in evaluation: the identity T_trans of the eager call is a no-op).
     `sensor`: the LiDAR the scans come from.  A net projects with the sensor it was built with (`PWCLONet(sensor=...)`, fixed for
-    its life and baked into its graphs), so this is a check that the caller and the net agree: None, or the net's."""
+    its life and baked into its graphs), so this is a check that the caller and the net agree: None, or the net's.
+    `sweep` (sensor.Sweep): the scans are NOT motion-compensated; the input stage de-skews both scans of every pair with a
+    constant-velocity guess -- the l0 pose of the previous chunk's last pair, handed over on the device as a pose
+    (`motion_is_pose`), the identity for the first chunk.  Sequential path only: with `lanes` the pairs in flight do not wait for
+    one another's poses (NotImplementedError)."""
+    if sweep is not None and lanes > 0:
+        raise NotImplementedError("de-skewing feeds each chunk the previous chunk's pose: the lanes run chunks concurrently")
     if sensor is not None and sensor != net.sensor:
         raise ValueError("this net was built for %r, the sequence is said to come from %r: build PWCLONet(sensor=...) for it"
                          % (net.sensor, sensor))
@@ -57,6 +63,10 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
         return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes)
     eye = torch.eye(4, dtype=torch.float32, device=dev).repeat(batch_size, 1, 1)      # main.py:308-309: no augmentation
     qs, ts = [], []
+    skew = {}
+    if sweep is not None:
+        identity = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], device=dev).repeat(batch_size, 1)
+        skew = dict(sweep=sweep, motion=identity, motion_is_pose=True)
     for start in range(0, len(frames), batch_size):
         chunk = frames[start:start + batch_size]
         cloud = np.zeros((batch_size, 2 * num_points, 3), np.float32)
@@ -65,7 +75,10 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
             pos2, pos1, _n2, _n1, T = kitti.load_pair(root, seq, chunk[min(j, len(chunk) - 1)], T_diff, num_points)
             cloud[j, :num_points], cloud[j, num_points:], T_gt[j] = pos2, pos1, T     # main.py:316-320
         out = net.forward_points(torch.from_numpy(cloud).to(dev), H_input, W_input, torch.from_numpy(T_gt).to(dev),
-                                 eye, eye, is_training=False, aug_frame=np.ones(batch_size, np.int64))
+                                 eye, eye, is_training=False, aug_frame=np.ones(batch_size, np.int64), **skew)
+        if sweep is not None:                                # [q_norm | t] of this chunk's last pair, for every pair of the next
+            last = len(chunk) - 1
+            skew["motion"] = torch.cat([out[0][last].reshape(4), out[1][last].reshape(3)]).repeat(batch_size, 1).contiguous()
         qs.append(out[0][:len(chunk)].reshape(-1, 4).cpu().numpy())
         ts.append(out[1][:len(chunk)].reshape(-1, 3).cpu().numpy())
     return np.concatenate(qs), np.concatenate(ts)

@@ -10,6 +10,8 @@ new range images in and replays.
 """
 import time
 
+import numpy as np
+
 import torch
 
 from . import _ops, fused, model_util, perm, pwclo_model, tf_util, tuning
@@ -107,13 +109,15 @@ class PWCLONet:
                 return pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, False, bn_decay, pose_out, sensor=self.sensor)
 
     def forward_points(self, point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training=False,
-                       bn_decay=None, aug_frame=None):
-        """get_model with the reference's full signature (raw clouds in)."""
+                       bn_decay=None, aug_frame=None, sweep=None, motion=None, motion2=None, motion_is_pose=False):
+        """get_model with the reference's full signature (raw clouds in).  `sweep` / `motion` / `motion2` / `motion_is_pose`: the
+        scans are not motion-compensated and are de-skewed inside the input stage (_ops.input_stage)."""
         with tf_util.default_store(self.store), perm.default_perm_source(self.perms), fused.storage(self.feature_dtype):
             ctx = torch.enable_grad() if is_training else torch.no_grad()
             with ctx:
                 return pwclo_model.get_model(point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training,
-                                             bn_decay, aug_frame, sensor=self.sensor, beam_elev=self.beam_elev)
+                                             bn_decay, aug_frame, sensor=self.sensor, beam_elev=self.beam_elev, sweep=sweep,
+                                             motion=motion, motion2=motion2, motion_is_pose=motion_is_pose)
 
     def check_range(self, xyz_f1_proj, xyz_f2_proj):
         """One eager forward on the CHECKED instances of the fused kernels (include/elo.h elo_range_check): the number of
@@ -131,11 +135,16 @@ class PWCLONet:
 
     # -- HIP graph -----------------------------------------------------------
     def capture(self, batch_size, H_input, W_input, warmup=3, lanes=1, num_points=None, point_stride=3, pose_ring=0, sample=None,
-                fresh_orders=0, check_every=0):
+                fresh_orders=0, check_every=0, sweep=None, motion_is_pose=False):
         """Record the inference forward into `lanes` independent hipGraphs (torch.cuda.CUDAGraph on ROCm).
         With `num_points` the graph starts from RAW clouds: a lane owns a (B, 2*num_points, point_stride) cloud buffer
         and records the input stage (model_util.input_stage: the sensor's crop + both projections, no augmentation) in front
         of the pyramid; feed it with `submit_points`.
+        With `sweep` (sensor.Sweep; needs `num_points`) the scans are not motion-compensated: the recorded input stage is
+        elo_input_stage_deskew, and a lane also owns a (B,7) `motion` buffer -- rows [q | t], initialised to the identity
+        1 0 0 0 0 0 0 -- that the launch reads at every REPLAY: `submit_points(..., motion=m)` copies into it on the lane's
+        stream, `lane_motion(lane)` hands it to a producer on the device.  `motion_is_pose` (the rows are [q_norm | t] poses of
+        the previous pair, inverted in the kernel) is part of the recorded arguments: fixed here, for the life of the graphs.
 
         One frame pair keeps only a few of the 256 CUs busy per kernel, and frame pairs are independent,
         so several forwards can be in flight: lane i owns a graph and its static input / output buffers and
@@ -165,6 +174,11 @@ class PWCLONet:
         lane writes slot r % R (the l0 pose-head kernel keeps the cursor on the device), so a stream of pairs is not
         followed by one copy-out launch per pair: `lane_poses(lane)` returns the rows written since `reset_poses(lane)`."""
         dev = self.device
+        if sweep is not None and num_points is None:
+            raise ValueError("a sweep de-skews raw clouds: capture(..., num_points=N, sweep=...)")
+        if sweep is None and motion_is_pose:
+            raise ValueError("motion_is_pose says how a sweep's motion is given: capture(..., sweep=...)")
+        skew = lambda lane: dict(sweep=sweep, motion=lane["motion"], motion_is_pose=motion_is_pose) if sweep is not None else {}
         if sample is not None:                       # a representative (2B,H,W,3) pair: vet the operand ranges on it
             bad = self.check_range(sample[:batch_size], sample[batch_size:])
             if bad:
@@ -188,7 +202,8 @@ class PWCLONet:
         if num_points is not None:                   # warm the input stage's allocations up as well
             with torch.cuda.stream(side):
                 model_util.input_stage(torch.zeros((batch_size, 2 * num_points, point_stride), device=dev), None, None,
-                                       H_input, W_input, sensor=self.sensor, beam_elev=self.beam_elev)
+                                       H_input, W_input, sensor=self.sensor, beam_elev=self.beam_elev,
+                                       **skew({"motion": torch.zeros((batch_size, 7), device=dev)}))
             torch.cuda.synchronize(dev)
         for i in range(lanes):
             both = zeros()
@@ -200,6 +215,11 @@ class PWCLONet:
                 lane["order"].record()                # (materialises the hipEvent_t: elo_graph_submit gets the raw handle)
             if num_points is not None:
                 lane["cloud"] = torch.zeros((batch_size, 2 * num_points, point_stride), device=dev)
+            if sweep is not None:
+                with torch.cuda.stream(side):
+                    lane["motion"] = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], device=dev).repeat(batch_size, 1).contiguous()
+                    lane["motion_is_pose"] = bool(motion_is_pose)
+                torch.cuda.synchronize(dev)
             if fresh_orders:                          # this lane's order buffers; caches keyed on them filled before the capture
                 self.perms.active_lane, self.perms.tail_armed = i, False
                 with torch.cuda.stream(side):
@@ -209,7 +229,7 @@ class PWCLONet:
             with graph_capture(lane["graph"]):
                 if num_points is not None:
                     _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
-                                                          beam_elev=self.beam_elev)
+                                                          beam_elev=self.beam_elev, **skew(lane))
                     lane["out"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"])
                 else:
                     lane["out"] = self.forward(*lane["in"], pose_out=lane["pose"])
@@ -230,7 +250,7 @@ class PWCLONet:
                     with graph_capture(lane["graph_checked"]):
                         if num_points is not None:
                             _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
-                                                                  beam_elev=self.beam_elev)
+                                                                  beam_elev=self.beam_elev, **skew(lane))
                             lane["out_checked"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"])
                         else:
                             lane["out_checked"] = self.forward(*lane["in"], pose_out=lane["pose"])
@@ -417,15 +437,37 @@ class PWCLONet:
             out = self._replay_lane(lane)
         return out
 
-    def submit_points(self, lane_index, point_cloud, ready=None):
-        """Enqueue one forward from raw clouds (B, 2N, stride) on a lane captured with `num_points`.  `ready`: as submit()."""
+    def submit_points(self, lane_index, point_cloud, ready=None, motion=None, motion_is_pose=None):
+        """Enqueue one forward from raw clouds (B, 2N, stride) on a lane captured with `num_points`.  `ready`: as submit().
+        `motion` (a lane captured with `sweep`): (B,7) rows [q | t] of the sensor's motion during these sweeps, copied into the
+        lane's motion buffer on the lane's stream ahead of the replay; None: the buffer is used as it stands (the identity, an
+        earlier motion, or what a device-side producer wrote into lane_motion()).  `motion_is_pose`: None, or what the capture was
+        given -- it is recorded in the graph and cannot change per submit."""
         self._check_fresh()
         lane = self._lanes[lane_index]
-        self._order_lane(lane, ready, point_cloud)
+        if "motion" not in lane:
+            if motion is not None or motion_is_pose:
+                raise RuntimeError("this lane was captured without a sweep: capture(..., num_points=N, sweep=Sweep(...))")
+        elif motion_is_pose is not None and bool(motion_is_pose) != lane["motion_is_pose"]:
+            raise RuntimeError("motion_is_pose=%r was recorded into this lane's graph at capture()" % lane["motion_is_pose"])
+        if motion is not None and not isinstance(motion, torch.Tensor):
+            motion = torch.from_numpy(np.ascontiguousarray(np.asarray(motion, dtype=np.float32)))
+        self._order_lane(lane, ready, point_cloud, motion)
         with torch.cuda.stream(lane["stream"]):
             lane["cloud"].copy_(point_cloud, non_blocking=True)
+            if motion is not None:
+                lane["motion"].copy_(motion.reshape(lane["motion"].shape), non_blocking=True)
             out = self._replay_lane(lane)
         return out
+
+    def lane_motion(self, lane_index):
+        """The (B,7) motion buffer of a lane captured with `sweep`: rows [q | t], read by the lane's input stage when its graph
+        RUNS.  A producer on the device (the pose head of the previous pair, a filter) writes here -- on the lane's stream, or
+        ordered before the submit -- and submit_points(lane, cloud) then de-skews with what it holds."""
+        lane = self._lanes[lane_index]
+        if "motion" not in lane:
+            raise RuntimeError("this lane was captured without a sweep: it has no motion buffer")
+        return lane["motion"]
 
     def lane_pose(self, lane_index):
         """The lane's (B,7) [l0_q_norm | l0_t] block, written by the l0 pose-head kernel of its last replay

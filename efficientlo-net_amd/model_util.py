@@ -169,10 +169,14 @@ def preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame):
     return q_gt, t_gt
 
 
-def input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=None, beam_elev=None):
+def input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=None, beam_elev=None, sweep=None, motion=None, motion2=None,
+                motion_is_pose=False):
     """The point half of PreProcess + both input projections (pwclo_model.py:54-67) as ONE C-ABI call
     (`elo_input_stage`: three launches).  point_cloud (B, 2N, >=3) -> (points (2B,N,3), xyz_proj (2B,H,W,3)), frame 1
     of every batch element first.  Inference only (the reference wraps this stage in stop_gradient, :66-67).
     `sensor`: field of view, crop and -- with a beam table -- the row rule (`elo_input_stage_beams`); `beam_elev`: that table on
-    the device, kept by whoever captures this call (_ops.input_stage)."""
-    return _ops.input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=sensor, beam_elev=beam_elev)
+    the device, kept by whoever captures this call (_ops.input_stage).
+    `sweep` / `motion` / `motion2` / `motion_is_pose`: the scan is not motion-compensated -- `elo_input_stage_deskew` carries every
+    point to one instant of its sweep first (sensor.Sweep, _ops.input_stage)."""
+    return _ops.input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=sensor, beam_elev=beam_elev, sweep=sweep,
+                            motion=motion, motion2=motion2, motion_is_pose=motion_is_pose)

@@ -435,16 +435,18 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
 
 
 def get_model(point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training, bn_decay=None, aug_frame=None, sensor=None,
-              beam_elev=None):
+              beam_elev=None, sweep=None, motion=None, motion2=None, motion_is_pose=False):
     """pwclo_model.py:30-433 with the reference's signature: point_cloud (B, 2*N, >=3), three (B,4,4).
     Returns the reference's 11-tuple.  `sensor` / `beam_elev`: as model_util.input_stage; the pyramid below projects with the
-    sensor's field of view."""
+    sensor's field of view.  `sweep` / `motion` / `motion2` / `motion_is_pose`: as model_util.input_stage (a scan that is not
+    motion-compensated is de-skewed inside the input stage)."""
     batch_size = point_cloud.shape[0]
     if aug_frame is None:
         aug_frame = np.random.choice([1, 2], size=batch_size, replace=True)                         # :59
     with torch.no_grad():                                                                           # tf.stop_gradient, :66-67
         # PreProcess's crop + augmentation and both ProjectPC2SphericalRing calls in one C-ABI call (three launches)
-        _points, both = input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=sensor, beam_elev=beam_elev)
+        _points, both = input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=sensor, beam_elev=beam_elev, sweep=sweep,
+                                    motion=motion, motion2=motion2, motion_is_pose=motion_is_pose)
         xyz_f1_proj, xyz_f2_proj = both[:batch_size], both[batch_size:]         # adjacent: one 2B Siamese batch
         q_gt, t_gt = preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame)
     out = get_model_from_projection(xyz_f1_proj, xyz_f2_proj, is_training, bn_decay, sensor=sensor)

@@ -6,6 +6,10 @@ The uniform row formula  row = H - int(beta / vert_res + vert_off)  at the senso
 (the level grids reuse the field of view with nLines = the level's H) except the raw-scan input stage of a
 sensor WITH a beam table: there a point goes to the row of the beam nearest in elevation (elo_input_stage_beams, include/elo.h),
 so every laser has its own row whatever the spacing of the blocks it is built from.
+
+`Sweep` is the other half of a real spinning sensor: its scans are not one instant.  It says where the acquisition phase of a point
+is found and which instant the input stage carries the points to, given the sensor's motion during the sweep
+(elo_input_stage_deskew).  It is a value of its own: `Sensor` does not change.
 """
 import math
 
@@ -72,6 +76,49 @@ class Sensor:
 
 
 KITTI_HDL64 = Sensor()
+
+
+class Sweep:
+    """Sweep(phase="azimuth", phase_ref=1.0): how a scan that is NOT motion-compensated tells WHEN each of its points was
+    acquired, and the instant the input stage carries them all to (elo_input_stage_deskew, include/elo.h).  Frozen and hashable.
+    phase: "azimuth" -- the fraction of the turn, (pi - atan2(y, x)) / 2 pi, of a sensor that starts its sweep at azimuth pi --
+    or an int >= 3: the channel of the cloud that holds the phase of every point (0 = start of the sweep, 1 = its end).
+    phase_ref: the phase every point is carried to (finite; 1.0: the end of the sweep, where the scan's pose is usually stamped)."""
+    __slots__ = ("phase", "phase_ref")
+
+    def __init__(self, phase="azimuth", phase_ref=1.0):
+        if isinstance(phase, str):
+            if phase != "azimuth":
+                raise ValueError("phase is \"azimuth\" or the channel of the cloud that holds it (got %r)" % (phase,))
+        else:
+            if isinstance(phase, bool) or not hasattr(phase, "__index__"):
+                raise ValueError("a phase channel is an integer (got %r)" % (phase,))
+            phase = phase.__index__()
+            if phase < 3:
+                raise ValueError("channels 0 .. 2 of a cloud are x, y, z: a phase channel is >= 3 (got %d)" % phase)
+        ref = float(phase_ref)
+        if not math.isfinite(ref):
+            raise ValueError("phase_ref must be finite (got %r)" % (ref,))
+        object.__setattr__(self, "phase", phase)
+        object.__setattr__(self, "phase_ref", ref)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Sweep is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("Sweep is immutable")
+
+    def _key(self):
+        return (self.phase, self.phase_ref)
+
+    def __eq__(self, other):
+        return isinstance(other, Sweep) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "Sweep(phase=%r, phase_ref=%r)" % (self.phase, self.phase_ref)
 
 
 def resolve(sensor):

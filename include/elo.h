@@ -423,6 +423,57 @@ typedef struct elo_input_stage_beams_args {
 } elo_input_stage_beams_args;
 int elo_input_stage_beams(const elo_input_stage_beams_args *a, elo_stream_t stream);
 
+/* elo_input_stage / elo_input_stage_beams for a scan that is NOT motion-compensated: every point is first carried from the
+ * instant it was acquired to one reference instant of its sweep, by a constant-velocity model of the sensor's motion during that
+ * sweep; the stage then runs on the corrected cloud.  The same three launches, scratch layout and stacked outputs.
+ * A MOTION is a row [q0 q1 q2 q3 | t0 t1 t2] per image: the rigid transform that carries coordinates from the sensor frame at the
+ * END of the sweep (phase 1) to the sensor frame at its START (phase 0),  p_start = R(q) p_end + t.  The kernel normalises q and,
+ * where q0 < 0, negates it (the shorter arc); theta = 2 atan2(|v|, q0), u = v / |v| with v = (q1, q2, q3); |v| = 0 (and a zero
+ * quaternion): no rotation.  A point p acquired at phase s becomes
+ *   a = s - phase_ref;   p' = Rot(u, a theta) p + a t        (slerp from the identity + a linear translation; a may be negative)
+ * and the entry is DEFINED as elo_input_stage (beam_elev == NULL) / elo_input_stage_beams (beam_elev != NULL, vert_res / vert_off
+ * unused) applied to the cloud whose non-zero points were replaced by p': the crop, T_trans / aug_frame, the validity re-mask, the
+ * binning and the scatter all see p'.  A point whose x, y, z are all zero (padding) is not touched and keeps its bits, signs
+ * included.  With the identity row, or where s == phase_ref, p' == p bit for bit unless p has a -0 component (which becomes +0).
+ * invert = 1: the inverse of the given transform is used, (q^-1, -q^-1 t q) -- the [q_norm | t] row a net writes for the PREVIOUS
+ * pair (frame 1 -> frame 2: elo_pose_head_args.pose7) can be named as it stands.
+ * phase_mode ELO_PHASE_CHANNEL: s = float number phase_channel of the point (3 <= phase_channel < point_stride), used as given,
+ * not clamped.  ELO_PHASE_AZIMUTH: s = (pi - atan2f(y, x)) / 2 pi of the RAW point, the fraction of the row at which the
+ * projection puts its column (a sensor that starts its sweep at azimuth pi and turns towards -pi).
+ * motion: (batch, 7) in DEVICE memory, the motion of both frames of a batch element; motion2 (or NULL): (batch, 7) for frame 2,
+ * motion then serving frame 1 only.  Every workgroup of the per-point launch first stages (u, theta, t) of the 2 * batch images in
+ * LDS, 28 bytes each: batch <= ELO_DESKEW_MAX_BATCH.  Per point: one sincosf and the quaternion sandwich, in float32.
+ * The entry checks what elo_input_stage / elo_input_stage_beams check, and: a non-NULL motion, a known phase_mode, the channel
+ * bound, a finite phase_ref, the batch bound.  On ELO_ERR_ARG nothing is launched.
+ * LIFETIME: as beam_elev -- the launches read motion / motion2 when they RUN.  A captured graph bakes the pointers in and sees at
+ * every replay what the rows hold THEN: a producer (the pose head of the previous pair, a copy on the replaying stream) may
+ * rewrite them between replays; the buffers stay alive for as long as the graph may be replayed.
+ * Additive to ABI 26: no existing struct changes. */
+#define ELO_PHASE_CHANNEL 0
+#define ELO_PHASE_AZIMUTH 1
+#define ELO_DESKEW_MAX_BATCH 512
+typedef struct elo_input_stage_deskew_args {
+    int batch, npoints;           /* points per frame */
+    int point_stride;             /* floats per point in `cloud` (>= 3) */
+    int H, W;
+    float az_res, vert_res, vert_off;   /* as in elo_input_stage_args (vert_res / vert_off: only with beam_elev == NULL) */
+    float crop_xy;
+    const float *cloud;           /* (batch, 2*npoints, point_stride) */
+    const float *T_trans;         /* (batch,4,4) row-major, or NULL = no augmentation */
+    const int *aug_frame;         /* (batch) 1 or 2 (NULL with T_trans == NULL) */
+    float *points;                /* (2*batch, npoints, 3) OUT */
+    float *out_xyz;               /* (2*batch, H, W, 3) OUT */
+    unsigned *scratch;            /* as elo_input_stage_args.scratch */
+    const float *beam_elev;       /* NULL: the uniform row formula; else (H) radians, strictly descending, H <= ELO_MAX_BEAMS */
+    const float *motion;          /* (batch,7) [q | t], end of sweep -> start of sweep */
+    const float *motion2;         /* (batch,7) for frame 2, or NULL = frame 2 uses `motion` */
+    int invert;                   /* 1: use the inverse of every row */
+    int phase_mode;               /* ELO_PHASE_CHANNEL / ELO_PHASE_AZIMUTH */
+    int phase_channel;            /* ELO_PHASE_CHANNEL: which float of a point holds its phase */
+    float phase_ref;              /* the phase every point is carried to (0: start of the sweep, 1: its end) */
+} elo_input_stage_deskew_args;
+int elo_input_stage_deskew(const elo_input_stage_deskew_args *a, elo_stream_t stream);
+
 /* The ground-truth half of PreProcess (model_util.py:403, :419, :427-445) in ONE launch, one thread per batch element:
  *   T = T_trans . T_gt      where aug_frame[b] == 2  (:403)
  *   T = T_gt . T_trans_inv  where aug_frame[b] == 1  (:419)
