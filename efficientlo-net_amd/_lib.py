@@ -83,6 +83,11 @@ PHASE_CHANNEL, PHASE_AZIMUTH = 0, 1        # ELO_PHASE_*
 DESKEW_MAX_BATCH = 512                     # ELO_DESKEW_MAX_BATCH
 PreprocessGtArgs = _struct("elo_preprocess_gt_args", [
     ("batch", _i), ("T_gt", _vp), ("T_trans", _vp), ("T_trans_inv", _vp), ("aug_frame", _vp), ("q_gt", _vp), ("t_gt", _vp)])
+PoseFitArgs = _struct("elo_pose_fit_args", [
+    ("batch", _i), ("H", _i), ("W", _i), ("az_res", _f), ("vert_res", _f), ("vert_off", _f), ("xyz1", _vp), ("xyz2", _vp),
+    ("pose_in", _vp), ("beam_elev", _vp), ("iters", _i), ("gate", _f), ("huber", _f), ("jump_rel", _f), ("min_count", _i),
+    ("damping", _f), ("pose_out", _vp), ("info", _vp), ("grad", _vp), ("stats", _vp), ("scratch", _vp)])
+FIT_FEW, FIT_SINGULAR, FIT_FEW_FINAL = 1, 2, 4        # ELO_FIT_*
 
 # backward passes (csrc/elo_backward.hip)
 GroupConcatBwdArgs = _struct("elo_group_concat_bwd_args", [
@@ -197,6 +202,9 @@ SYMBOLS = [
     ("elo_input_stage_deskew", ctypes.c_int, [ctypes.POINTER(InputStageDeskewArgs), _vp]),
     ("elo_preprocess_gt", ctypes.c_int, [ctypes.POINTER(PreprocessGtArgs), _vp]),
     ("elo_pose_head_warp", ctypes.c_int, [ctypes.POINTER(PoseHeadArgs), ctypes.POINTER(WarpProjectArgs), _vp]),
+    ("elo_pose_fit", ctypes.c_int, [ctypes.POINTER(PoseFitArgs), _vp]),
+    ("elo_pose_fit_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
+    ("elo_pose_fit_parts", ctypes.c_int, [ctypes.c_int] * 2),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),
     ("elo_masked_maxpool_backward", ctypes.c_int, [ctypes.POINTER(MaskedMaxpoolBwdArgs), _vp]),
     ("elo_cv_encode1_backward", ctypes.c_int, [ctypes.POINTER(CvEncode1BwdArgs), _vp]),

@@ -644,6 +644,99 @@ def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam
     return points, out_xyz
 
 
+class PoseFitResult:
+    """What elo_pose_fit wrote for a batch: pose (B,7) [q | t] -- the input pose, or the polished one --, info (B,6,6) = the
+    normal matrix A at that pose (rotation first, then translation; left perturbation), grad (B,6) = b, and views of the (B,4)
+    stats block: count (terms, an exact integer in float32), cost = sum w r^2, rms = sqrt(cost / sum w), status (0: fine; bits
+    _lib.FIT_FEW / FIT_SINGULAR: a step was refused and the pose is the input's; FIT_FEW_FINAL: the reported evaluation has fewer
+    than min_count terms).  The tensors are the launch's own outputs: valid once its stream has been synchronised or waited on."""
+    __slots__ = ("pose", "info", "grad", "stats", "scratch")
+
+    def __init__(self, pose, info, grad, stats, scratch=None):
+        self.pose, self.info, self.grad, self.stats, self.scratch = pose, info, grad, stats, scratch
+
+    count = property(lambda self: self.stats[:, 0])
+    cost = property(lambda self: self.stats[:, 1])
+    rms = property(lambda self: self.stats[:, 2])
+    status = property(lambda self: self.stats[:, 3])
+
+    def covariance(self):
+        """sigma^2 A^-1 with sigma^2 = cost / (count - 6), per image, (B,6,6) float64 on the host -- for reporting.  NaN rows
+        where count <= 6 or A is singular."""
+        A = self.info.detach().cpu().numpy().astype(np.float64)
+        st = self.stats.detach().cpu().numpy().astype(np.float64)
+        out = np.full(A.shape, np.nan)
+        for b in range(A.shape[0]):
+            if st[b, 0] > 6:
+                try:
+                    out[b] = st[b, 1] / (st[b, 0] - 6) * np.linalg.inv(A[b])
+                except np.linalg.LinAlgError:
+                    pass
+        return out
+
+
+def _check_pose_fit(xyz1, xyz2, pose7, fit, beam_elev):
+    """What the host can refuse about a pose fit without a GPU or the library: the value, shapes, dtypes, layout, devices."""
+    if not isinstance(fit, _sensor.PoseFit):
+        raise TypeError("fit is a PoseFit (got %r)" % (type(fit).__name__,))
+    for name, t in (("xyz1", xyz1), ("xyz2", xyz2), ("pose7", pose7)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s is a tensor (got %r)" % (name, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s is float32 (got %s)" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise L.EloError("%s must be contiguous: the launch reads it in place" % name)
+    if xyz1.dim() != 4 or xyz1.shape[-1] != 3 or xyz1.shape != xyz2.shape:
+        raise L.EloError("xyz1 / xyz2 are two (B,H,W,3) range images of one shape (got %s, %s)" % (tuple(xyz1.shape), tuple(xyz2.shape)))
+    B, H, W, _ = xyz1.shape
+    if H < 3:
+        raise L.EloError("a normal needs three rows: H >= 3 (got %d)" % H)
+    if tuple(pose7.shape) != (B, 7):
+        raise L.EloError("pose7 is one [q0 q1 q2 q3 | t0 t1 t2] row per image: (%d, 7) (got %s)" % (B, tuple(pose7.shape)))
+    if xyz2.device != xyz1.device or pose7.device != xyz1.device:
+        raise L.EloError("xyz1, xyz2 and pose7 live on one device")
+    if isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda:
+        if (beam_elev.device != xyz1.device or beam_elev.dtype != torch.float32 or not beam_elev.is_contiguous()
+                or beam_elev.numel() != H):
+            raise L.EloError("a device beam table is a contiguous float32 tensor of H = %d entries on the images' device" % H)
+    if (beam_elev is not None) and H > L.MAX_BEAMS:
+        raise L.EloError("a beam table has at most %d beams (H = %d)" % (L.MAX_BEAMS, H))
+
+
+def pose_fit(xyz1, xyz2, pose7, fit, sensor=None, beam_elev=None):
+    """elo_pose_fit: the point-to-plane fit of the poses `pose7` (B,7) [q | t] (frame 1 -> frame 2) on the range images xyz1 / xyz2
+    (B,H,W,3) -> PoseFitResult.  `fit`: a sensor.PoseFit.  `sensor` (None: the reference's HDL-64E) gives the field of view of the
+    cell rule; a sensor with a beam table -- or an explicit `beam_elev`, as input_stage takes it -- matches by the beam-table rows
+    the input stage of such a sensor wrote the images with.  Inputs are float32, contiguous and used in place: pose7 is read when
+    the launches RUN (a graph that records this call fits what the row holds at every replay).  Bad shapes, dtypes or layouts
+    are refused here, before anything is launched."""
+    _check_pose_fit(xyz1, xyz2, pose7, fit, beam_elev)
+    sensor = _sensor.resolve(sensor)
+    L.require_gpu(xyz1, xyz2, pose7)
+    B, H, W, _ = xyz1.shape
+    dev = xyz1.device
+    if beam_elev is None and sensor.beam_elevations_deg is not None:
+        beam_elev = sensor
+    if beam_elev is not None and not (isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda):
+        if torch.cuda.is_current_stream_capturing():
+            raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
+        beam_elev = beam_table(beam_elev, H, dev)
+    words = L.lib().elo_pose_fit_scratch_words(B, H, W)
+    if words < 0:
+        raise L.EloError("elo_pose_fit refuses a (%d,%d,%d) batch of images" % (B, H, W))
+    res = PoseFitResult(torch.empty((B, 7), dtype=torch.float32, device=dev), torch.empty((B, 6, 6), dtype=torch.float32, device=dev),
+                        torch.empty((B, 6), dtype=torch.float32, device=dev), torch.empty((B, 4), dtype=torch.float32, device=dev),
+                        torch.empty((max(words, 1),), dtype=torch.int32, device=dev))
+    az, vres, voff = projection_constants(H, W, sensor)
+    a = L.PoseFitArgs(B, H, W, az, vres, voff, xyz1.data_ptr(), xyz2.data_ptr(), pose7.data_ptr(), _ptr(beam_elev), fit.iters, fit.gate,
+                      fit.huber, fit.jump_rel, fit.min_count, fit.damping, res.pose.data_ptr(), res.info.data_ptr(), res.grad.data_ptr(),
+                      res.stats.data_ptr(), res.scratch.data_ptr())
+    L.call("elo_pose_fit", a, xyz1)
+    if beam_elev is not None:
+        res.scratch = (res.scratch, beam_elev)          # (the launches read the table when they run: it lives as long as the result)
+    return res
+
+
 class _WarpProject(torch.autograd.Function):
     """elo_warp_project / elo_warp_project_backward.  The forward's scratch (who won each cell) is kept for the backward."""
 

@@ -824,38 +824,8 @@ __host__ __device__ inline ProjScratch proj_scratch(unsigned *s, size_t cells, s
 // the flag of (image, zero cell) -- zflag <- 0, a plain store of a constant to a word no atomic touches -- and pass B
 // lets nothing else win that cell.  For the other points a cell's value only ever decreases, so a (possibly stale)
 // read that is already <= rb proves the atomicMin would change nothing.
-// The ROW RULE of the per-point pass is a parameter: how (atan2f(y, x), z, r) becomes a cell.
-// RowsByFormula: the reference's uniform formula (cell_of_point), every projection of the model.
-struct RowsByFormula {
-    float vert_res, vert_off;
-    __device__ __forceinline__ int cell(float at, float z, float r, int H, int W, float az_res) const
-    {
-        return cell_of_point(at, z, r, H, W, az_res, vert_res, vert_off);
-    }
-};
-
-// RowsByBeams (elo_input_stage_beams): the row of the beam nearest in elevation = the number of midpoints between consecutive
-// beams that lie above the point.  `mid` (LDS): the SINES of the H-1 midpoints, descending, padded with -inf to 2*half - 1
-// entries (2*half = the power of two >= H): z/r is compared with them -- monotone in the elevation, no asinf -- by a branch-free
-// binary search of log2(2*half) steps.  !(s >= mid): a zero point (s = 0/0 = NaN) counts every entry and lands in row H-1, the
-// row the formula's NaN -> 0 conversion gives it.  The column is cell_of_point's.
-struct RowsByBeams {
-    const float *mid;
-    int half;
-    __device__ __forceinline__ int cell(float at, float z, float r, int H, int W, float az_res) const
-    {
-        const float PI_F = 3.14159265358979323846f;
-        const float c = (PI_F - at) / az_res;                                // model_util.py:234-235 (atan2f is never NaN here)
-        int col = c != c ? 0 : (int)c;
-        const float s = z / r;
-        int row = 0;
-        for (int step = half; step >= 1; step >>= 1) row += !(s >= mid[row + step - 1]) ? step : 0;
-        row = row > H - 1 ? H - 1 : row;
-        col = col < 0 ? 0 : col > W - 1 ? W - 1 : col;
-        return row * W + col;
-    }
-};
-
+// The ROW RULE of the per-point pass is a parameter: how (atan2f(y, x), z, r) becomes a cell -- RowsByFormula / RowsByBeams
+// (elo_project_device.h, shared with the pose fit of elo_posefit.hip: both must name the same cells).
 template <class Rows>
 __device__ __forceinline__ void bin_point_by(float x, float y, float z, long i, int b, int H, int W, float az_res, const Rows &rows,
                                              const ProjScratch &ps)
@@ -1247,8 +1217,7 @@ __global__ __launch_bounds__(ELO_BLOCK) void input_cell_beams_kernel(const elo_i
                                                                      const int half)
 {
     __shared__ float mid[ELO_MAX_BEAMS];
-    for (int k = threadIdx.x; k < 2 * half - 1; k += blockDim.x)
-        mid[k] = k < a.H - 1 ? sinf(0.5f * (a.beam_elev[k] + a.beam_elev[k + 1])) : -INFINITY;
+    stage_beam_midpoints(mid, a.beam_elev, a.H, half);
     __syncthreads();
     const long per_frame = (long)a.batch * a.npoints, total = 2 * per_frame;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
@@ -1273,8 +1242,7 @@ __global__ __launch_bounds__(ELO_BLOCK) void input_cell_deskew_beams_kernel(cons
 {
     __shared__ float mid[ELO_MAX_BEAMS];
     extern __shared__ float motion_lds[];
-    for (int k = threadIdx.x; k < 2 * half - 1; k += blockDim.x)
-        mid[k] = k < a.H - 1 ? sinf(0.5f * (a.beam_elev[k] + a.beam_elev[k + 1])) : -INFINITY;
+    stage_beam_midpoints(mid, a.beam_elev, a.H, half);
     stage_motion(a, motion_lds);
     __syncthreads();
     const SkewByMotion skew{motion_lds, a.phase_mode, a.phase_channel, a.phase_ref};
@@ -1709,9 +1677,7 @@ extern "C" int elo_input_stage_beams(const elo_input_stage_beams_args *a, elo_st
     ELO_REQUIRE(a->crop_xy == a->crop_xy, who, "crop_xy is NaN");
     if (a->batch == 0) return ELO_OK;
     ELO_REQUIRE(a->cloud && a->points && a->out_xyz && a->scratch, who, "null tensor pointer");
-    int half = 0;                                     // 2 * half: the power of two >= H (H = 1: no midpoint, no step)
-    while (2 * half < a->H) half = half ? 2 * half : 1;
-    if (a->H == 1) half = 0;
+    const int half = beam_search_half(a->H);
     hipStream_t s = (hipStream_t)stream;
     return input_stage_launches(a, 1.0f, 0.0f, s, who, [&](dim3 grid, const ProjScratch &ps) {
         hipLaunchKernelGGL(input_cell_beams_kernel, grid, dim3(ELO_BLOCK), 0, s, *a, ps, half);
@@ -1742,9 +1708,7 @@ extern "C" int elo_input_stage_deskew(const elo_input_stage_deskew_args *a, elo_
         return input_stage_launches(a, a->vert_res, a->vert_off, s, who, [&](dim3 grid, const ProjScratch &ps) {
             hipLaunchKernelGGL(input_cell_deskew_kernel, grid, dim3(ELO_BLOCK), lds, s, *a, ps);
         });
-    int half = 0;                                     // as elo_input_stage_beams
-    while (2 * half < a->H) half = half ? 2 * half : 1;
-    if (a->H == 1) half = 0;
+    const int half = beam_search_half(a->H);
     return input_stage_launches(a, 1.0f, 0.0f, s, who, [&](dim3 grid, const ProjScratch &ps) {
         hipLaunchKernelGGL(input_cell_deskew_beams_kernel, grid, dim3(ELO_BLOCK), lds, s, *a, ps, half);
     });

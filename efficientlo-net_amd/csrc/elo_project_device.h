@@ -21,6 +21,54 @@ __device__ __forceinline__ int cell_of_point(float at, float z, float r, int H, 
     return row * W + col;
 }
 
+// The ROW RULE of a per-point pass is a parameter: how (atan2f(y, x), z, r) becomes a cell.
+// RowsByFormula: the reference's uniform formula (cell_of_point), every projection of the model.
+struct RowsByFormula {
+    float vert_res, vert_off;
+    __device__ __forceinline__ int cell(float at, float z, float r, int H, int W, float az_res) const
+    {
+        return cell_of_point(at, z, r, H, W, az_res, vert_res, vert_off);
+    }
+};
+
+// RowsByBeams (elo_input_stage_beams): the row of the beam nearest in elevation = the number of midpoints between consecutive
+// beams that lie above the point.  `mid` (LDS): the SINES of the H-1 midpoints, descending, padded with -inf to 2*half - 1
+// entries (2*half = the power of two >= H): z/r is compared with them -- monotone in the elevation, no asinf -- by a branch-free
+// binary search of log2(2*half) steps.  !(s >= mid): a zero point (s = 0/0 = NaN) counts every entry and lands in row H-1, the
+// row the formula's NaN -> 0 conversion gives it.  The column is cell_of_point's.
+struct RowsByBeams {
+    const float *mid;
+    int half;
+    __device__ __forceinline__ int cell(float at, float z, float r, int H, int W, float az_res) const
+    {
+        const float PI_F = 3.14159265358979323846f;
+        const float c = (PI_F - at) / az_res;                                // model_util.py:234-235 (atan2f is never NaN here)
+        int col = c != c ? 0 : (int)c;
+        const float s = z / r;
+        int row = 0;
+        for (int step = half; step >= 1; step >>= 1) row += !(s >= mid[row + step - 1]) ? step : 0;
+        row = row > H - 1 ? H - 1 : row;
+        col = col < 0 ? 0 : col > W - 1 ? W - 1 : col;
+        return row * W + col;
+    }
+};
+
+// `half` of RowsByBeams for H beams (host): 2 * half = the power of two >= H (H = 1: no midpoint, no step)
+inline int beam_search_half(int H)
+{
+    int half = 0;
+    while (2 * half < H) half = half ? 2 * half : 1;
+    return H == 1 ? 0 : half;
+}
+
+// the workgroup stages RowsByBeams' `mid` (ELO_MAX_BEAMS floats of LDS) from the table; the caller's __syncthreads() follows.  One
+// sinf per thread at most (H <= ELO_MAX_BEAMS = the block size); the same instructions on the same table in every workgroup
+__device__ __forceinline__ void stage_beam_midpoints(float *mid, const float *beam_elev, int H, int half)
+{
+    for (int k = threadIdx.x; k < 2 * half - 1; k += blockDim.x)
+        mid[k] = k < H - 1 ? sinf(0.5f * (beam_elev[k] + beam_elev[k + 1])) : -INFINITY;
+}
+
 // which of a zero point's three possible cells: by atan2f of its signed zeros (0: +-0, 1: pi, 2: -pi)
 __device__ __forceinline__ int zero_kind(float at) { return at > 1.0f ? 1 : at < -1.0f ? 2 : 0; }
 

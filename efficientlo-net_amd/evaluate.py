@@ -36,7 +36,7 @@ def pose_rows(q_n4, t_n3, Tr):
 
 
 def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_size=1, num_points=150000, frames=None,
-                     lanes=0, sensor=None, sweep=None):
+                     lanes=0, sensor=None, sweep=None, fit=None):
     """Run the network over samples `frames` (default: all scans found) of sequence `seq`; returns (q (n,4), t (n,3))
     = the l0 pose of every sample, in sample order.  Batches are padded by repeating the last sample
     (main.py:497-509 keeps stale rows instead; either way the padding rows are dropped).
@@ -48,7 +48,11 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     `sweep` (sensor.Sweep): the scans are NOT motion-compensated; the input stage de-skews both scans of every pair with a
     constant-velocity guess -- the l0 pose of the previous chunk's last pair, handed over on the device as a pose
     (`motion_is_pose`), the identity for the first chunk.  Sequential path only: with `lanes` the pairs in flight do not wait for
-    one another's poses (NotImplementedError)."""
+    one another's poses (NotImplementedError).
+    `fit` (sensor.PoseFit): every l0 pose is also fitted on its pair's range images (elo_pose_fit) and the returned poses are the
+    fit's `pose_out` -- the net's own with iters = 0, the polished ones otherwise (a flagged sample keeps the net's); a third
+    value comes back, (n,24) float64 rows [count, rms, status, the 21 entries of the upper triangle of info, row-major].  On both
+    paths.  Without it: the two values of before."""
     if sweep is not None and lanes > 0:
         raise NotImplementedError("de-skewing feeds each chunk the previous chunk's pose: the lanes run chunks concurrently")
     if sensor is not None and sensor != net.sensor:
@@ -60,13 +64,13 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     frames = list(frames)
     dev = net.device
     if lanes > 0:
-        return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes)
+        return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit)
     eye = torch.eye(4, dtype=torch.float32, device=dev).repeat(batch_size, 1, 1)      # main.py:308-309: no augmentation
-    qs, ts = [], []
-    skew = {}
+    qs, ts, fits = [], [], []
+    skew = {} if fit is None else {"fit": fit}
     if sweep is not None:
         identity = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], device=dev).repeat(batch_size, 1)
-        skew = dict(sweep=sweep, motion=identity, motion_is_pose=True)
+        skew.update(sweep=sweep, motion=identity, motion_is_pose=True)
     for start in range(0, len(frames), batch_size):
         chunk = frames[start:start + batch_size]
         cloud = np.zeros((batch_size, 2 * num_points, 3), np.float32)
@@ -79,22 +83,44 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
         if sweep is not None:                                # [q_norm | t] of this chunk's last pair, for every pair of the next
             last = len(chunk) - 1
             skew["motion"] = torch.cat([out[0][last].reshape(4), out[1][last].reshape(3)]).repeat(batch_size, 1).contiguous()
+        if fit is not None:
+            pose = out[-1].pose[:len(chunk)].cpu().numpy()
+            qs.append(pose[:, :4].copy())
+            ts.append(pose[:, 4:].copy())
+            fits.append(fit_rows(out[-1], len(chunk)))
+            continue
         qs.append(out[0][:len(chunk)].reshape(-1, 4).cpu().numpy())
         ts.append(out[1][:len(chunk)].reshape(-1, 3).cpu().numpy())
+    if fit is not None:
+        return np.concatenate(qs), np.concatenate(ts), np.concatenate(fits)
     return np.concatenate(qs), np.concatenate(ts)
 
 
-def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes):
+_TRIU = np.triu_indices(6)
+
+
+def fit_rows(result, n):
+    """(n,24) float64: [count, rms, status | the upper triangle of info, row-major] of the first n images of a PoseFitResult."""
+    stats = result.stats[:n].cpu().numpy().astype(np.float64)
+    info = result.info[:n].cpu().numpy().astype(np.float64)
+    return np.concatenate([stats[:, [0, 2, 3]], info[:, _TRIU[0], _TRIU[1]]], 1)
+
+
+def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit=None):
     dev = net.device
-    net.capture(batch_size, H_input, W_input, lanes=lanes, num_points=num_points)
+    net.capture(batch_size, H_input, W_input, lanes=lanes, num_points=num_points, fit=fit)
     chunks = [frames[s:s + batch_size] for s in range(0, len(frames), batch_size)]
-    qs, ts = [None] * len(chunks), [None] * len(chunks)
+    qs, ts, fits = [None] * len(chunks), [None] * len(chunks), [None] * len(chunks)
     pinned = [torch.empty((batch_size, 2 * num_points, 3), dtype=torch.float32).pin_memory() for _ in range(lanes)]
 
     def collect(ci):                                         # the lane's stream has finished chunk ci
         lane = ci % lanes
         net.lane_stream(lane).synchronize()
-        pose = net.lane_pose(lane)[:len(chunks[ci])].cpu().numpy()        # (b,7) = [q_norm | t] of l0
+        if fit is not None:
+            res = net.lane_fit(lane, fit)
+            pose, fits[ci] = res.pose[:len(chunks[ci])].cpu().numpy(), fit_rows(res, len(chunks[ci]))
+        else:
+            pose = net.lane_pose(lane)[:len(chunks[ci])].cpu().numpy()    # (b,7) = [q_norm | t] of l0
         qs[ci], ts[ci] = pose[:, :4].copy(), pose[:, 4:].copy()
 
     for ci, chunk in enumerate(chunks):
@@ -108,19 +134,25 @@ def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size
         net.submit_points(lane, pinned[lane])                # async H2D into the lane's cloud buffer + one replay
     for ci in range(max(0, len(chunks) - lanes), len(chunks)):
         collect(ci)
+    if fit is not None:
+        return np.concatenate(qs), np.concatenate(ts), np.concatenate(fits)
     return np.concatenate(qs), np.concatenate(ts)
 
 
 def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
     """predict_sequence -> pose_rows -> `<out_dir>/<seq>_pred.txt` (main.py:574-583) -> KITTI errors against
     `poses_gt` ((n,12) absolute camera poses, e.g. ground_truth_pose/<seq>.txt) if given.
-    Returns (rows (n,12), (t_rel %, r_rel deg/100m) or None)."""
-    q, t = predict_sequence(net, root, seq, T_diff, **kw)
+    Returns (rows (n,12), (t_rel %, r_rel deg/100m) or None).
+    `fit=PoseFit(...)` (predict_sequence): the trajectory is built from the fit's poses and `<out_dir>/<seq>_fit.txt` holds one row
+    per sample: count, rms, status and the 21 unique entries of the information matrix."""
+    q, t, *fit_out = predict_sequence(net, root, seq, T_diff, **kw)
     Tr = kitti.read_calib(os.path.join(root, seq, "calib.txt"))["Tr"]
     rows = pose_rows(q, t, Tr)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         kitti.write_pred_txt(os.path.join(out_dir, "%s_pred.txt" % seq), rows)
+        if fit_out:
+            np.savetxt(os.path.join(out_dir, "%s_fit.txt" % seq), fit_out[0], fmt="%.9e")
     score = None
     if poses_gt is not None:
         score = kitti.overall(kitti.sequence_errors(np.asarray(poses_gt)[:len(rows)], rows))

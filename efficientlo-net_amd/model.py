@@ -98,8 +98,13 @@ class PWCLONet:
         self._captured_at = None          # (store.generation, perms.generation) the graphs were recorded under
 
     # -- eager ---------------------------------------------------------------
-    def forward(self, xyz_f1_proj, xyz_f2_proj, is_training=False, bn_decay=None, pose_out=None):
-        """get_model_from_projection under this net's variables and permutations."""
+    def forward(self, xyz_f1_proj, xyz_f2_proj, is_training=False, bn_decay=None, pose_out=None, fit=None):
+        """get_model_from_projection under this net's variables and permutations.
+        `fit` (sensor.PoseFit): the tuple gains one more entry, the _ops.PoseFitResult of the l0 pose on the pair's own range images
+        (elo_pose_fit, by this net's sensor / beam table); the other outputs are what they are without it."""
+        if fit is not None:
+            out = self.forward(xyz_f1_proj, xyz_f2_proj, is_training, bn_decay, pose_out)
+            return out + (self._fit_l0(xyz_f1_proj, xyz_f2_proj, out, None if is_training else pose_out, fit),)
         with tf_util.default_store(self.store), perm.default_perm_source(self.perms), fused.storage(self.feature_dtype):
             if is_training:
                 if self.feature_dtype != torch.float32:
@@ -108,10 +113,33 @@ class PWCLONet:
             with torch.no_grad():
                 return pwclo_model.get_model_from_projection(xyz_f1_proj, xyz_f2_proj, False, bn_decay, pose_out, sensor=self.sensor)
 
+    def _fit_l0(self, xyz_f1_proj, xyz_f2_proj, out, pose7, fit):
+        """elo_pose_fit of a forward's l0 pose -- the (B,7) row block the l0 pose head wrote (`pose7`), else [l0_q | l0_t] put
+        together here -- on the forward's input images."""
+        if isinstance(pose7, _ops.PoseRing):
+            raise ValueError("a pose ring and a pose fit do not combine: the fit reads ONE (B,7) block")
+        with torch.no_grad():
+            if pose7 is None:
+                pose7 = torch.cat([out[0].detach().reshape(-1, 4), out[1].detach().reshape(-1, 3)], -1).contiguous()
+            return _ops.pose_fit(xyz_f1_proj.detach().contiguous(), xyz_f2_proj.detach().contiguous(), pose7, fit, sensor=self.sensor,
+                                 beam_elev=self.beam_elev)
+
     def forward_points(self, point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training=False,
-                       bn_decay=None, aug_frame=None, sweep=None, motion=None, motion2=None, motion_is_pose=False):
+                       bn_decay=None, aug_frame=None, sweep=None, motion=None, motion2=None, motion_is_pose=False, fit=None):
         """get_model with the reference's full signature (raw clouds in).  `sweep` / `motion` / `motion2` / `motion_is_pose`: the
-        scans are not motion-compensated and are de-skewed inside the input stage (_ops.input_stage)."""
+        scans are not motion-compensated and are de-skewed inside the input stage (_ops.input_stage).
+        `fit` (sensor.PoseFit): a twelfth entry, the fit of the l0 pose on the range images the input stage wrote (forward())."""
+        if fit is not None:
+            B = point_cloud.shape[0]
+            if aug_frame is None:
+                aug_frame = np.random.choice([1, 2], size=B, replace=True)
+            with torch.no_grad():                                   # pwclo_model.get_model's own first half
+                _pts, both = pwclo_model.input_stage(point_cloud, T_trans, aug_frame, H_input, W_input, sensor=self.sensor,
+                                                     beam_elev=self.beam_elev, sweep=sweep, motion=motion, motion2=motion2,
+                                                     motion_is_pose=motion_is_pose)
+                q_gt, t_gt = pwclo_model.preprocess_gt(T_gt, T_trans, T_trans_inv, aug_frame)
+            out = self.forward(both[:B], both[B:], is_training, bn_decay, fit=fit)
+            return out[:-1] + (q_gt, t_gt, out[-1])
         with tf_util.default_store(self.store), perm.default_perm_source(self.perms), fused.storage(self.feature_dtype):
             ctx = torch.enable_grad() if is_training else torch.no_grad()
             with ctx:
@@ -135,7 +163,7 @@ class PWCLONet:
 
     # -- HIP graph -----------------------------------------------------------
     def capture(self, batch_size, H_input, W_input, warmup=3, lanes=1, num_points=None, point_stride=3, pose_ring=0, sample=None,
-                fresh_orders=0, check_every=0, sweep=None, motion_is_pose=False):
+                fresh_orders=0, check_every=0, sweep=None, motion_is_pose=False, fit=None):
         """Record the inference forward into `lanes` independent hipGraphs (torch.cuda.CUDAGraph on ROCm).
         With `num_points` the graph starts from RAW clouds: a lane owns a (B, 2*num_points, point_stride) cloud buffer
         and records the input stage (model_util.input_stage: the sensor's crop + both projections, no augmentation) in front
@@ -172,8 +200,20 @@ class PWCLONet:
 
         `pose_ring=R` (>= 2): a lane's pose output is a ring of R rows blocks instead of one (B,7) block -- replay r of the
         lane writes slot r % R (the l0 pose-head kernel keeps the cursor on the device), so a stream of pairs is not
-        followed by one copy-out launch per pair: `lane_poses(lane)` returns the rows written since `reset_poses(lane)`."""
+        followed by one copy-out launch per pair: `lane_poses(lane)` returns the rows written since `reset_poses(lane)`.
+
+        `fit` (sensor.PoseFit): every lane records elo_pose_fit behind the l0 pose head -- it reads the lane's pose row and its
+        stacked range images (with `num_points`: the input stage's output) when the graph RUNS -- into buffers the lane owns:
+        `lane_fit(lane)`.  With `check_every` both graphs record it.  It does not combine with `pose_ring` (the fit reads one
+        (B,7) block).  None: exactly the graph recorded without this argument."""
         dev = self.device
+        if fit is not None:
+            if not isinstance(fit, sensor_mod.PoseFit):
+                raise TypeError("fit is a PoseFit or None (got %r)" % (type(fit).__name__,))
+            if pose_ring:
+                raise ValueError("capture(pose_ring=..., fit=...): a pose fit reads the lane's ONE (B,7) pose block, a ring spreads "
+                                 "the rows over slots -- record one or the other")
+        with_fit = {} if fit is None else {"fit": fit}
         if sweep is not None and num_points is None:
             raise ValueError("a sweep de-skews raw clouds: capture(..., num_points=N, sweep=...)")
         if sweep is None and motion_is_pose:
@@ -193,6 +233,8 @@ class PWCLONet:
             probe = zeros()
             for _ in range(warmup):                 # creates variables, folded weights, caches, hipBLASLt plans
                 self.forward(probe[:batch_size], probe[batch_size:])
+            if fit is not None:                     # ... and the fit's kernels
+                self.forward(probe[:batch_size], probe[batch_size:], **with_fit)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self._lanes = []
@@ -230,9 +272,11 @@ class PWCLONet:
                 if num_points is not None:
                     _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
                                                           beam_elev=self.beam_elev, **skew(lane))
-                    lane["out"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"])
+                    lane["out"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"], **with_fit)
                 else:
-                    lane["out"] = self.forward(*lane["in"], pose_out=lane["pose"])
+                    lane["out"] = self.forward(*lane["in"], pose_out=lane["pose"], **with_fit)
+            if fit is not None:
+                lane["out"], lane["fit"] = lane["out"][:-1], lane["out"][-1]
             if check_every:                           # the same forward on the checked kernel instances, same buffers
                 from . import _lib
                 lane["graph_checked"], lane["check_every"] = torch.cuda.CUDAGraph(), int(check_every)
@@ -251,9 +295,12 @@ class PWCLONet:
                         if num_points is not None:
                             _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
                                                                   beam_elev=self.beam_elev, **skew(lane))
-                            lane["out_checked"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"])
+                            lane["out_checked"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"],
+                                                               **with_fit)
                         else:
-                            lane["out_checked"] = self.forward(*lane["in"], pose_out=lane["pose"])
+                            lane["out_checked"] = self.forward(*lane["in"], pose_out=lane["pose"], **with_fit)
+                    if fit is not None:
+                        lane["out_checked"], lane["fit_checked"] = lane["out_checked"][:-1], lane["out_checked"][-1]
                 finally:
                     _lib.range_check(bool(prev))
                     _lib.set_range_counter(prev_counter)
@@ -268,6 +315,7 @@ class PWCLONet:
         self._graph, self._static_in, self._static_out = (self._lanes[0]["graph"], self._lanes[0]["in"],
                                                           self._lanes[0]["out"])
         self._captured_at = (self.store.generation, self.perms.generation, tuning.digest())
+        self.captured_fit = fit                            # the PoseFit the graphs have baked in (lane_fit checks a caller's against it)
         self._tuning_seen = tuning.version()
         self.captured_tuning = tuning.snapshot()           # the forms this graph has baked in (bench.py: config.tuning)
         return self
@@ -324,6 +372,7 @@ class PWCLONet:
         checked = n and lane["total"] % n == 0
         (lane["graph_checked"] if checked else lane["graph"]).replay()
         lane["replays"] += 1
+        lane["last_checked"] = bool(checked)
         return lane["out_checked"] if checked else lane["out"]
 
     def range_violations(self, lane_index=None):
@@ -424,6 +473,7 @@ class PWCLONet:
                 _lib.check(native["submit"](native["exec_checked"] if checked else native["exec"], native["stream"], native["dst"], src, nbytes,
                                             producer, event, native["device"]))
                 lane["replays"] += 1
+                lane["last_checked"] = bool(checked)
                 return lane["out_checked"] if checked else lane["out"]
         self._order_lane(lane, ready, xyz_f1_proj, xyz_f2_proj)
         with torch.cuda.stream(lane["stream"]):
@@ -468,6 +518,18 @@ class PWCLONet:
         if "motion" not in lane:
             raise RuntimeError("this lane was captured without a sweep: it has no motion buffer")
         return lane["motion"]
+
+    def lane_fit(self, lane_index, fit=None):
+        """The _ops.PoseFitResult of the lane's last replay (capture(..., fit=PoseFit(...))): buffers the lane owns, written by
+        the fit launches behind the l0 pose head; valid once the lane's stream has been synchronised or waited on.  `fit`: the
+        PoseFit the caller expects the graphs to hold -- another one than capture() recorded is an error, not a silent mismatch."""
+        lane = self._lanes[lane_index]
+        if "fit" not in lane:
+            raise RuntimeError("this lane was captured without a pose fit: capture(..., fit=PoseFit(...))")
+        if fit is not None and fit != self.captured_fit:
+            raise RuntimeError("the captured graphs hold %r, not %r: a graph keeps the fit of its capture -- call capture() again"
+                               % (self.captured_fit, fit))
+        return lane["fit_checked"] if lane.get("last_checked") and "fit_checked" in lane else lane["fit"]
 
     def lane_pose(self, lane_index):
         """The lane's (B,7) [l0_q_norm | l0_t] block, written by the l0 pose-head kernel of its last replay

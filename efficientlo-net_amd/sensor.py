@@ -10,6 +10,9 @@ so every laser has its own row whatever the spacing of the blocks it is built fr
 `Sweep` is the other half of a real spinning sensor: its scans are not one instant.  It says where the acquisition phase of a point
 is found and which instant the input stage carries the points to, given the sensor's motion during the sweep
 (elo_input_stage_deskew).  It is a value of its own: `Sensor` does not change.
+
+`PoseFit` asks for the geometric fit of a relative pose on the pair's own range images (elo_pose_fit): residual, information
+matrix and, with iters > 0, Gauss-Newton steps on them.
 """
 import math
 
@@ -119,6 +122,54 @@ class Sweep:
 
     def __repr__(self):
         return "Sweep(phase=%r, phase_ref=%r)" % (self.phase, self.phase_ref)
+
+
+class PoseFit:
+    """PoseFit(iters=0, gate=1.0, huber=0.1, jump_rel=0.1, min_count=50, damping=0.0): the point-to-plane fit of a pose on the two
+    range images of its pair (elo_pose_fit, include/elo.h).  Frozen and hashable.
+    iters: Gauss-Newton steps on the pose (0: only measure it); gate (m): a frame-1 point further than this from the point of the
+    frame-2 cell it falls in gives no term; huber (m): residuals beyond it are weighted huber / |r|; jump_rel: a normal is taken
+    only where the four neighbours' ranges lie within jump_rel * r of the cell's range r; min_count: an image with fewer terms is
+    flagged and its pose left alone; damping: Levenberg factor on the diagonal of the normal matrix."""
+    __slots__ = ("iters", "gate", "huber", "jump_rel", "min_count", "damping")
+
+    def __init__(self, iters=0, gate=1.0, huber=0.1, jump_rel=0.1, min_count=50, damping=0.0):
+        for name, value in (("iters", iters), ("min_count", min_count)):
+            if isinstance(value, bool) or not hasattr(value, "__index__"):
+                raise ValueError("%s is an integer (got %r)" % (name, value))
+        iters, min_count = iters.__index__(), min_count.__index__()
+        if iters < 0 or iters > 64:
+            raise ValueError("iters is 0 .. 64 (got %d)" % iters)
+        if min_count < 0 or min_count >= 2 ** 31:
+            raise ValueError("min_count is a non-negative 32-bit count (got %d)" % min_count)
+        gate, huber, jump_rel, damping = float(gate), float(huber), float(jump_rel), float(damping)
+        for name, value in (("gate", gate), ("huber", huber)):
+            if not (math.isfinite(value) and value > 0):
+                raise ValueError("%s must be positive and finite (got %r)" % (name, value))
+        for name, value in (("jump_rel", jump_rel), ("damping", damping)):
+            if not (math.isfinite(value) and value >= 0):
+                raise ValueError("%s must be finite and >= 0 (got %r)" % (name, value))
+        for name, value in (("iters", iters), ("gate", gate), ("huber", huber), ("jump_rel", jump_rel), ("min_count", min_count),
+                            ("damping", damping)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("PoseFit is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("PoseFit is immutable")
+
+    def _key(self):
+        return (self.iters, self.gate, self.huber, self.jump_rel, self.min_count, self.damping)
+
+    def __eq__(self, other):
+        return isinstance(other, PoseFit) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "PoseFit(iters=%r, gate=%r, huber=%r, jump_rel=%r, min_count=%r, damping=%r)" % self._key()
 
 
 def resolve(sensor):

@@ -503,6 +503,68 @@ int elo_preprocess_gt(const elo_preprocess_gt_args *a, elo_stream_t stream);
  * the third launch is the projection's scatter.  w->q / w->t are ignored (the pose is a->q, a->t); w->warped is required. */
 int elo_pose_head_warp(const elo_pose_head_args *a, const elo_warp_project_args *w, elo_stream_t stream);
 
+/* POSE FIT on the two range images of a pair (csrc/elo_posefit.hip): how well a relative pose registers them, the 6x6
+ * information matrix of that pose, and -- on request -- a few Gauss-Newton steps on it ("polish").
+ * pose_in: (batch,7) [q | t], frame 1 -> frame 2, p' = R(q) p + t: the layout and convention of elo_pose_head_args.pose7.  q is
+ * normalised in the kernel.  xyz1 / xyz2: (batch,H,W,3) range images as the input stage writes them; an all-zero cell is empty.
+ * ONE EVALUATION at a pose (R, t):
+ *   normal of a frame-2 cell (h,w):  n = normalise((x[h,w+1] - x[h,w-1]) x (x[h+1,w] - x[h-1,w])), columns wrap (the cylinder's
+ *     seam); invalid in rows 0 and H-1, where the cell or one of the four neighbours is empty, where a neighbour's range differs
+ *     from the cell's range r by more than jump_rel * r, and where the cross product has no length; oriented towards the sensor
+ *     (n . x <= 0).  Computed on the fly at the matched cell.
+ *   term of a non-empty frame-1 cell p1:  p = R p1 + t;  m = the cell of p in frame 2 -- cell_of_point at (az_res, vert_res,
+ *     vert_off), exactly as elo_warp_project takes it, or (beam_elev != NULL) the beam-table row of elo_input_stage_beams --;
+ *     p2 = xyz2[m].  No term where p2 is empty, its normal is invalid or |p - p2| > gate.  Else
+ *       r = n . (p - p2),   J = [p x n | n]  (left perturbation: rotation first, then translation),
+ *       w = 1 where |r| <= huber, else huber / |r|
+ *   sums per image:  A = sum w J J^T,  b = sum w J r,  cost = sum w r^2,  sum w,  count (an integer).
+ * ARITHMETIC: the geometry of a term (p, the normal, r, J, w and their products) is double precision from the float32 inputs --
+ * r is a difference of nearby points, which float32 would leave with a relative error of |p| / |r| ulps --; the cell of p is taken
+ * from p rounded to float32, by the float32 rule the projections use.  Each product is rounded to float32 ONCE and summed in
+ * float32 in a FIXED order: a thread over its strip of cells, a wave by DPP, the four waves of a workgroup through LDS; the
+ * workgroup stores one partial row.  The partial rows of an image are then added in a fixed order, in double.  No floating-point atomic:
+ * two runs, and an eager run and a graph replay, agree bit for bit.  The grid is a fixed function of (batch, H, W).
+ * SOLVE (a second, one-workgroup-per-image launch after an evaluation): (A + damping * diag(A)) d = -b by Cholesky in double, one
+ * thread; d = (omega, v);  q <- dq(omega) (x) q, normalised,  t <- R(dq) t + v.  Where count < min_count (ELO_FIT_FEW) or the
+ * factorisation fails / d is not finite (ELO_FIT_SINGULAR) the image is FLAGGED: its pose_out row is pose_in's, every bit, from
+ * then on (later steps do not move it), and the status says why.  No NaN leaves these kernels.
+ * iters = 0: one evaluation at pose_in; pose_out = pose_in (bits).  iters = k: k times (evaluate, solve), then one evaluation at
+ * the updated pose.  The sums of the LAST evaluation are added up and written by the solve kernel in its report form (no pose
+ * update; count < min_count there sets ELO_FIT_FEW_FINAL and leaves pose_out alone): 2 (k + 1) launches, all enqueued by this
+ * one call, capturable.
+ * OUT: pose_out (batch,7); info (batch,6,6) = A at pose_out (all 36 entries, symmetric); grad (batch,6) = b;
+ *      stats (batch,4) = [count, cost, rms = sqrt(cost / sum w) (0 where count = 0), status], float32 roundings of the doubles.
+ * scratch: elo_pose_fit_scratch_words(batch, H, W) 32-bit device words (ask: the host does not restate the launch geometry).
+ * ELO_ERR_ARG (nothing is launched): a NULL image / pose / output / scratch, H < 3, W < 1, gate or huber not positive, a negative
+ * or NaN jump_rel or damping, H > ELO_MAX_BEAMS with a table, iters < 0, batch * H * W beyond 2^31.
+ * LIFETIME: the launches read pose_in, the images and beam_elev when they RUN: a captured graph sees at every replay the row the
+ * pose head has just written; every buffer named here stays alive for as long as a graph recorded with it may be replayed.
+ * pose_out must not alias pose_in.  Additive to ABI 26: no existing struct changes. */
+#define ELO_FIT_FEW 1            /* status bits: a solve step met count < min_count */
+#define ELO_FIT_SINGULAR 2       /*   a solve step's factorisation failed */
+#define ELO_FIT_FEW_FINAL 4      /*   the last evaluation (the one reported) has count < min_count */
+typedef struct elo_pose_fit_args {
+    int batch, H, W;
+    float az_res, vert_res, vert_off;   /* as in elo_warp_project_args (vert_res / vert_off: only with beam_elev == NULL) */
+    const float *xyz1, *xyz2;     /* (batch,H,W,3) */
+    const float *pose_in;         /* (batch,7) [q | t] */
+    const float *beam_elev;       /* NULL: the uniform row formula; else (H) radians, strictly descending, H <= ELO_MAX_BEAMS */
+    int iters;                    /* Gauss-Newton steps, >= 0 */
+    float gate;                   /* m: no term beyond this distance to the matched point */
+    float huber;                  /* m */
+    float jump_rel;               /* a normal's neighbours lie within jump_rel * range of its cell's range */
+    int min_count;
+    float damping;                /* Levenberg factor on diag(A), >= 0 */
+    float *pose_out;              /* (batch,7) OUT */
+    float *info;                  /* (batch,6,6) OUT */
+    float *grad;                  /* (batch,6) OUT */
+    float *stats;                 /* (batch,4) OUT */
+    unsigned *scratch;
+} elo_pose_fit_args;
+long elo_pose_fit_scratch_words(int batch, int H, int W);   /* < 0: sizes the entry refuses */
+int elo_pose_fit_parts(int H, int W);                       /* partial rows (workgroups) per image of an evaluation */
+int elo_pose_fit(const elo_pose_fit_args *a, elo_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * Backward passes of the feature kernels above, for TRAINING (csrc/elo_backward.hip).
  * The reference trains through TensorFlow's autodiff of its stock ops (main.py:171-176): gather_nd -> scatter-add of
