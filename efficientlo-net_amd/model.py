@@ -14,7 +14,7 @@ import numpy as np
 
 import torch
 
-from . import _ops, fused, model_util, perm, pwclo_model, tf_util, tuning
+from . import _lib, _ops, fused, model_util, perm, pwclo_model, tf_util, tuning
 from . import sensor as sensor_mod
 
 
@@ -71,9 +71,53 @@ def _cached_tensors():
     """Every tensor the host-side caches hold right now (strided / all-pixel index grids, centre tables, decoded
     visiting orders): what a graph captured just before may point at."""
     from . import pointnet_util
-    keep = list(model_util._sel_cache.values()) + list(pointnet_util._hw_cache.values()) + \
+    return list(model_util._sel_cache.values()) + list(pointnet_util._hw_cache.values()) + \
         list(pointnet_util._centre_hw_cache.values()) + list(fused._DECODED.values()) + list(fused._HW.values())
-    return keep
+
+
+class Lane:
+    """One captured forward and everything it owns: the stream it replays on, its static input / output buffers, its graph --
+    with capture(check_every=N) a second one on the range-checked kernels -- and the host's count of its replays.  What a feature
+    adds (`cloud`, `motion`, `fit`, the `*_checked` recordings, `range_counter`, `native`) is None / 0 / False while the feature is off."""
+    __slots__ = ("stream", "order", "pair", "inputs", "cloud", "motion", "motion_is_pose", "pose", "graph", "out", "fit", "graph_checked",
+                 "out_checked", "fit_checked", "check_every", "range_counter", "keep", "native", "total", "replays", "base", "last_checked", "tainted")
+
+    def __init__(self, **fields):
+        start = dict.fromkeys(self.__slots__)         # None: the feature is off, or capture() has not come to it yet
+        start.update(motion_is_pose=False, check_every=0, total=0, replays=0, base=0, last_checked=False, tainted=0)
+        for name, value in {**start, **fields}.items():
+            setattr(self, name, value)
+
+    def take(self):
+        """Count one replay and say what it runs: (graph, outputs) -- every `check_every`-th time of the checked recording."""
+        self.total += 1
+        self.replays += 1
+        self.last_checked = bool(self.check_every) and self.total % self.check_every == 0
+        return (self.graph_checked, self.out_checked) if self.last_checked else (self.graph, self.out)
+
+    def fit_result(self):
+        """The PoseFitResult the last replay wrote."""
+        return self.fit_checked if self.last_checked and self.fit_checked is not None else self.fit
+
+    # the pose ring's window: `replays` rows from slot `base` on (the device-side cursor never stops; the host remembers where it stood)
+    def last_pose(self):
+        ring = self.pose                            # (or the one (B,7) block of a lane without a ring)
+        return ring if isinstance(ring, torch.Tensor) else ring.rows[(self.base + self.replays - 1) % ring.slots]
+
+    def poses(self):
+        ring, n, base = self.pose, self.replays, self.base
+        if n > ring.slots:
+            raise RuntimeError("%d replays since reset_poses() on a ring of %d slots: rows were overwritten" % (n, ring.slots))
+        if base + n <= ring.slots:
+            return ring.rows[base:base + n]
+        return torch.cat([ring.rows[base:], ring.rows[:base + n - ring.slots]], 0)        # (wrapped: a copy, on the current stream)
+
+    def mark(self):
+        self.base = (self.base + self.replays) % self.pose.slots
+        self.replays = 0
+
+    def reset(self):
+        self.replays = self.base = 0
 
 
 class PWCLONet:
@@ -91,10 +135,7 @@ class PWCLONet:
         self.feature_dtype = feature_dtype
         self.store = tf_util.VariableStore(self.device, seed=seed)
         self.perms = perm_source if perm_source is not None else perm.PermSource(seed=seed)
-        self._graph = None
-        self._static_in = None
-        self._static_out = None
-        self._lanes = []
+        self._lanes = []                  # Lane per captured graph; empty: nothing captured
         self._captured_at = None          # (store.generation, perms.generation) the graphs were recorded under
 
     # -- eager ---------------------------------------------------------------
@@ -152,7 +193,6 @@ class PWCLONet:
         matrix-core operands -- gathered inputs and layer outputs -- at or beyond the fp16 range (|x| >= 65504, or NaN),
         where the hi/lo split saturates instead of representing the value.  0 for any sane checkpoint and scan; capture()
         runs it on its `sample` so that a captured graph (which replays the unchecked kernels) was vetted on real data."""
-        from . import _lib
         prev = _lib.range_check(True)
         try:
             _lib.range_violations(xyz_f1_proj)                       # reset the counter
@@ -207,118 +247,115 @@ class PWCLONet:
         `lane_fit(lane)`.  With `check_every` both graphs record it.  It does not combine with `pose_ring` (the fit reads one
         (B,7) block).  None: exactly the graph recorded without this argument."""
         dev = self.device
-        if fit is not None:
-            if not isinstance(fit, sensor_mod.PoseFit):
-                raise TypeError("fit is a PoseFit or None (got %r)" % (type(fit).__name__,))
-            if pose_ring:
-                raise ValueError("capture(pose_ring=..., fit=...): a pose fit reads the lane's ONE (B,7) pose block, a ring spreads "
-                                 "the rows over slots -- record one or the other")
-        with_fit = {} if fit is None else {"fit": fit}
-        if sweep is not None and num_points is None:
-            raise ValueError("a sweep de-skews raw clouds: capture(..., num_points=N, sweep=...)")
-        if sweep is None and motion_is_pose:
-            raise ValueError("motion_is_pose says how a sweep's motion is given: capture(..., sweep=...)")
-        skew = lambda lane: dict(sweep=sweep, motion=lane["motion"], motion_is_pose=motion_is_pose) if sweep is not None else {}
+        self._lanes = []                             # (a capture that raises leaves the net without lanes, not with half of them)
+        self._check_capture_args(num_points, pose_ring, sweep, motion_is_pose, fit)
         if sample is not None:                       # a representative (2B,H,W,3) pair: vet the operand ranges on it
             bad = self.check_range(sample[:batch_size], sample[batch_size:])
             if bad:
                 raise RuntimeError("%d matrix-core operands of this forward lie at or beyond the fp16 range (|x| >= 65504): the "
                                    "fused kernels' hi/lo split would saturate them -- rescale the inputs / weights or run the "
                                    "fp32-MFMA build (ELO_DENSE_F32=1)" % bad)
+        shape = (2 * batch_size, H_input, W_input, 3)    # both frames in one allocation: the Siamese pyramid then runs as one 2B batch
+        cloud_shape = None if num_points is None else (batch_size, 2 * num_points, point_stride)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        def zeros():          # both frames in one allocation: the Siamese pyramid then runs as one 2B batch
-            return torch.zeros((2 * batch_size, H_input, W_input, 3), device=dev)
         with torch.cuda.stream(side):
-            probe = zeros()
+            probe = torch.zeros(shape, device=dev)
             for _ in range(warmup):                 # creates variables, folded weights, caches, hipBLASLt plans
                 self.forward(probe[:batch_size], probe[batch_size:])
             if fit is not None:                     # ... and the fit's kernels
-                self.forward(probe[:batch_size], probe[batch_size:], **with_fit)
+                self.forward(probe[:batch_size], probe[batch_size:], fit=fit)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        self._lanes = []
         if fresh_orders:
             self.perms.enable_pool(int(fresh_orders), lanes, dev)       # (the warm-up forwards above created every order tensor)
         streams = distinct_queue_streams(dev, lanes)
-        if num_points is not None:                   # warm the input stage's allocations up as well
+        if cloud_shape is not None:                  # warm the input stage's allocations up as well
             with torch.cuda.stream(side):
-                model_util.input_stage(torch.zeros((batch_size, 2 * num_points, point_stride), device=dev), None, None,
-                                       H_input, W_input, sensor=self.sensor, beam_elev=self.beam_elev,
-                                       **skew({"motion": torch.zeros((batch_size, 7), device=dev)}))
+                model_util.input_stage(torch.zeros(cloud_shape, device=dev), None, None, H_input, W_input, sensor=self.sensor,
+                                       beam_elev=self.beam_elev, sweep=sweep, motion_is_pose=motion_is_pose,
+                                       motion=None if sweep is None else torch.zeros((batch_size, 7), device=dev))
             torch.cuda.synchronize(dev)
-        for i in range(lanes):
-            both = zeros()
-            lane = {"stream": streams[i % len(streams)], "pair": both, "in": (both[:batch_size], both[batch_size:]),
-                    "graph": torch.cuda.CUDAGraph(), "replays": 0,
-                    "pose": _ops.PoseRing(pose_ring, batch_size, dev) if pose_ring else torch.zeros((batch_size, 7), device=dev)}
-            lane["order"] = torch.cuda.Event()        # submit()'s producer ordering: recorded on the caller's stream, waited on by the lane's
-            with torch.cuda.stream(side):
-                lane["order"].record()                # (materialises the hipEvent_t: elo_graph_submit gets the raw handle)
-            if num_points is not None:
-                lane["cloud"] = torch.zeros((batch_size, 2 * num_points, point_stride), device=dev)
-            if sweep is not None:
-                with torch.cuda.stream(side):
-                    lane["motion"] = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], device=dev).repeat(batch_size, 1).contiguous()
-                    lane["motion_is_pose"] = bool(motion_is_pose)
-                torch.cuda.synchronize(dev)
-            if fresh_orders:                          # this lane's order buffers; caches keyed on them filled before the capture
-                self.perms.active_lane, self.perms.tail_armed = i, False
-                with torch.cuda.stream(side):
-                    self.forward(both[:batch_size], both[batch_size:])
-                torch.cuda.synchronize(dev)
-            self.perms.tail_armed = bool(fresh_orders)    # the recorded forward's last launch loads the NEXT replay's orders
-            with graph_capture(lane["graph"]):
-                if num_points is not None:
-                    _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
-                                                          beam_elev=self.beam_elev, **skew(lane))
-                    lane["out"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"], **with_fit)
-                else:
-                    lane["out"] = self.forward(*lane["in"], pose_out=lane["pose"], **with_fit)
-            if fit is not None:
-                lane["out"], lane["fit"] = lane["out"][:-1], lane["out"][-1]
-            if check_every:                           # the same forward on the checked kernel instances, same buffers
-                from . import _lib
-                lane["graph_checked"], lane["check_every"] = torch.cuda.CUDAGraph(), int(check_every)
-                # the lane's OWN violation word: its address goes into the kernel arguments of the checked graph (ABI 26), so a
-                # saturated operand is counted for the lane whose forward met it -- not for every lane, as one process-wide word did
-                lane["range_counter"] = torch.zeros((1,), dtype=torch.int64, device=dev)
-                prev = _lib.range_check(True)
-                prev_counter = _lib.set_range_counter(lane["range_counter"].data_ptr())
-                try:
-                    self.perms.tail_armed = False     # (the warm-up below must not advance the lane's order cursor)
-                    with torch.cuda.stream(side):     # the checked path's own allocations / caches, before its capture
-                        self.forward(*lane["in"])
-                    torch.cuda.synchronize(dev)
-                    self.perms.tail_armed = bool(fresh_orders)
-                    with graph_capture(lane["graph_checked"]):
-                        if num_points is not None:
-                            _pts, staged = model_util.input_stage(lane["cloud"], None, None, H_input, W_input, sensor=self.sensor,
-                                                                  beam_elev=self.beam_elev, **skew(lane))
-                            lane["out_checked"] = self.forward(staged[:batch_size], staged[batch_size:], pose_out=lane["pose"],
-                                                               **with_fit)
-                        else:
-                            lane["out_checked"] = self.forward(*lane["in"], pose_out=lane["pose"], **with_fit)
-                    if fit is not None:
-                        lane["out_checked"], lane["fit_checked"] = lane["out_checked"][:-1], lane["out_checked"][-1]
-                finally:
-                    _lib.range_check(bool(prev))
-                    _lib.set_range_counter(prev_counter)
-                lane["range_counter"].zero_()         # (the warm-up forward counted too)
-            # the graph holds raw device pointers into the module-level index / decoded-order caches; those caches evict
-            # (clear()) when they grow: the lane keeps the tensors alive for as long as its graph exists
-            lane["keep"] = _cached_tensors()
-            lane["native"] = self._native_submit(lane, dev)
-            self._lanes.append(lane)
+        self._lanes = [self._capture_lane(i, streams[i % len(streams)], side, shape, cloud_shape, pose_ring, fresh_orders, check_every,
+                                          sweep, motion_is_pose, fit) for i in range(lanes)]
         self.perms.active_lane, self.perms.tail_armed = 0, False
         torch.cuda.synchronize(dev)
-        self._graph, self._static_in, self._static_out = (self._lanes[0]["graph"], self._lanes[0]["in"],
-                                                          self._lanes[0]["out"])
         self._captured_at = (self.store.generation, self.perms.generation, tuning.digest())
         self.captured_fit = fit                            # the PoseFit the graphs have baked in (lane_fit checks a caller's against it)
         self._tuning_seen = tuning.version()
         self.captured_tuning = tuning.snapshot()           # the forms this graph has baked in (bench.py: config.tuning)
         return self
+
+    @staticmethod
+    def _check_capture_args(num_points, pose_ring, sweep, motion_is_pose, fit):
+        if fit is not None and not isinstance(fit, sensor_mod.PoseFit):
+            raise TypeError("fit is a PoseFit or None (got %r)" % (type(fit).__name__,))
+        if fit is not None and pose_ring:
+            raise ValueError("capture(pose_ring=..., fit=...): a pose fit reads the lane's ONE (B,7) pose block, a ring spreads "
+                             "the rows over slots -- record one or the other")
+        if sweep is not None and num_points is None:
+            raise ValueError("a sweep de-skews raw clouds: capture(..., num_points=N, sweep=...)")
+        if sweep is None and motion_is_pose:
+            raise ValueError("motion_is_pose says how a sweep's motion is given: capture(..., sweep=...)")
+
+    def _record(self, lane, sweep, fit):
+        """What a lane's graph holds -- called with a capture open: the input stage, if the lane starts from raw clouds, and the forward
+        into the lane's pose block with the fit behind it.  -> (outputs, the PoseFitResult or None)"""
+        f1, f2 = lane.inputs
+        if lane.cloud is not None:
+            _pts, staged = model_util.input_stage(lane.cloud, None, None, f1.shape[1], f1.shape[2], sensor=self.sensor, beam_elev=self.beam_elev,
+                                                  sweep=sweep, motion=lane.motion, motion_is_pose=lane.motion_is_pose)
+            f1, f2 = staged[:len(f1)], staged[len(f1):]
+        out = self.forward(f1, f2, pose_out=lane.pose, fit=fit)
+        return (out, None) if fit is None else (out[:-1], out[-1])
+
+    def _capture_lane(self, i, stream, side, shape, cloud_shape, pose_ring, fresh_orders, check_every, sweep, motion_is_pose, fit):
+        """Lane i: its buffers, then its graph(s) recorded on them."""
+        dev, batch_size = self.device, shape[0] // 2
+        both = torch.zeros(shape, device=dev)
+        lane = Lane(stream=stream, pair=both, inputs=(both[:batch_size], both[batch_size:]), graph=torch.cuda.CUDAGraph(),
+                    pose=_ops.PoseRing(pose_ring, batch_size, dev) if pose_ring else torch.zeros((batch_size, 7), device=dev),
+                    cloud=None if cloud_shape is None else torch.zeros(cloud_shape, device=dev),
+                    order=torch.cuda.Event(),         # submit()'s producer ordering: recorded on the caller's stream, waited on by the lane's
+                    check_every=int(check_every), motion_is_pose=bool(motion_is_pose))
+        with torch.cuda.stream(side):
+            lane.order.record()                       # (materialises the hipEvent_t: elo_graph_submit gets the raw handle)
+        if sweep is not None:
+            with torch.cuda.stream(side):
+                lane.motion = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], device=dev).repeat(batch_size, 1).contiguous()
+            torch.cuda.synchronize(dev)
+        def warm():                                   # an eager forward on the lane's buffers: its allocations and caches, ahead of a capture
+            with torch.cuda.stream(side):
+                self.forward(*lane.inputs)
+            torch.cuda.synchronize(dev)
+        if fresh_orders:                              # this lane's order buffers; caches keyed on them filled before the capture
+            self.perms.active_lane, self.perms.tail_armed = i, False
+            warm()
+        self.perms.tail_armed = bool(fresh_orders)    # the recorded forward's last launch loads the NEXT replay's orders
+        with graph_capture(lane.graph):
+            lane.out, lane.fit = self._record(lane, sweep, fit)
+        if check_every:                               # the same forward on the checked kernel instances, same buffers
+            lane.graph_checked = torch.cuda.CUDAGraph()
+            # the lane's OWN violation word: its address goes into the kernel arguments of the checked graph (ABI 26), so a
+            # saturated operand is counted for the lane whose forward met it -- not for every lane, as one process-wide word did
+            lane.range_counter = torch.zeros((1,), dtype=torch.int64, device=dev)
+            prev = _lib.range_check(True)
+            prev_counter = _lib.set_range_counter(lane.range_counter.data_ptr())
+            try:
+                self.perms.tail_armed = False         # (the warm-up below must not advance the lane's order cursor)
+                warm()                                # (the checked path's own)
+                self.perms.tail_armed = bool(fresh_orders)
+                with graph_capture(lane.graph_checked):
+                    lane.out_checked, lane.fit_checked = self._record(lane, sweep, fit)
+            finally:
+                _lib.range_check(bool(prev))
+                _lib.set_range_counter(prev_counter)
+            lane.range_counter.zero_()                # (the warm-up forward counted too)
+        # the graph holds raw device pointers into the module-level index / decoded-order caches; those caches evict
+        # (clear()) when they grow: the lane keeps the tensors alive for as long as its graph exists
+        lane.keep = _cached_tensors()
+        lane.native = self._native_submit(lane, dev)
+        return lane
 
     @staticmethod
     def _native_submit(lane, dev):
@@ -329,22 +366,20 @@ class PWCLONet:
         numbers (dropout is off, visiting orders are explicit inputs: perm.PermSource), so nothing is registered."""
         if not tuning.get("native_submit"):
             return None
-        from . import _lib
+        import ctypes
         try:
-            execs = [lane[k].raw_cuda_graph_exec() if k in lane else None for k in ("graph", "graph_checked")]
+            execs = {g: ctypes.c_void_p(g.raw_cuda_graph_exec()) for g in (lane.graph, lane.graph_checked) if g is not None}
         except (AttributeError, RuntimeError):
             return None
-        import ctypes
-        pair = lane["pair"]
-        return {"submit": _lib.lib().elo_graph_submit, "exec": ctypes.c_void_p(execs[0]), "exec_checked": ctypes.c_void_p(execs[1] or execs[0]),
-                "stream": ctypes.c_void_p(lane["stream"].cuda_stream), "dst": ctypes.c_void_p(pair.data_ptr()),
-                "nbytes": pair.numel() * pair.element_size(), "event": ctypes.c_void_p(lane["order"].cuda_event), "device": int(dev.index)}
+        return {"submit": _lib.lib().elo_graph_submit, "exec": execs, "stream": ctypes.c_void_p(lane.stream.cuda_stream),
+                "dst": ctypes.c_void_p(lane.pair.data_ptr()), "nbytes": lane.pair.numel() * lane.pair.element_size(),
+                "event": ctypes.c_void_p(lane.order.cuda_event), "device": int(dev.index)}
 
     def _check_fresh(self):
         """A captured graph holds raw device pointers to the folded / packed inference weights and to the decoded
         visiting orders.  VariableStore.invalidate() (load_state_dict, tf_checkpoint.load_into, a training step) and
         PermSource.reshuffle() drop those tensors: replaying would read stale weights or recycled memory, silently."""
-        if self._graph is None:
+        if not self._lanes:
             raise RuntimeError("no captured graph: call capture() first")
         if self._captured_at[:2] != (self.store.generation, self.perms.generation):
             raise RuntimeError("the captured graph is stale: the variables or the visiting orders changed after capture() "
@@ -358,8 +393,8 @@ class PWCLONet:
                                "%s, now %s" % (self.captured_tuning, tuning.snapshot()))
 
     def load_inputs(self, xyz_f1_proj, xyz_f2_proj):
-        self._static_in[0].copy_(xyz_f1_proj, non_blocking=True)
-        self._static_in[1].copy_(xyz_f2_proj, non_blocking=True)
+        self._lanes[0].inputs[0].copy_(xyz_f1_proj, non_blocking=True)
+        self._lanes[0].inputs[1].copy_(xyz_f2_proj, non_blocking=True)
 
     def replay(self):
         self._check_fresh()
@@ -367,13 +402,9 @@ class PWCLONet:
 
     def _replay_lane(self, lane):
         """Replay the lane's graph -- every `check_every`-th time the one recorded on the range-checked kernels."""
-        n = lane.get("check_every", 0)
-        lane["total"] = lane.get("total", 0) + 1
-        checked = n and lane["total"] % n == 0
-        (lane["graph_checked"] if checked else lane["graph"]).replay()
-        lane["replays"] += 1
-        lane["last_checked"] = bool(checked)
-        return lane["out_checked"] if checked else lane["out"]
+        graph, out = lane.take()
+        graph.replay()
+        return out
 
     def range_violations(self, lane_index=None):
         """Matrix-core operands at or beyond the fp16 range (|x| >= 65504, or NaN) seen by the checked replays since the last
@@ -383,13 +414,10 @@ class PWCLONet:
         lanes = self._lanes if lane_index is None else [self._lanes[lane_index]]
         total = 0
         for lane in lanes:
-            word = lane.get("range_counter")
-            if word is None:
-                continue
-            bad = int(word.item())
+            bad = 0 if lane.range_counter is None else int(lane.range_counter.item())
             if bad:
-                word.zero_()
-                lane["tainted"] = lane.get("tainted", 0) + bad
+                lane.range_counter.zero_()
+                lane.tainted += bad
                 total += bad
         return total
 
@@ -397,22 +425,22 @@ class PWCLONet:
         """lane_poses(lane_index) for a lane whose work is DONE: synchronises the lane's stream, and raises if a checked
         replay saw an operand outside the fp16 range (the poses since the last collection are then not to be trusted)."""
         lane = self._lanes[lane_index]
-        lane["stream"].synchronize()
-        if lane.get("check_every"):
+        lane.stream.synchronize()
+        if lane.check_every:
             self.range_violations(lane_index)        # this lane's own word
-            bad = lane.pop("tainted", 0)
+            bad, lane.tainted = lane.tainted, 0
             if bad:
                 raise RuntimeError("%d matrix-core operands at or beyond the fp16 range (|x| >= 65504 or NaN) since the last "
                                    "collection: the hi/lo split of the fused kernels saturated them -- rescale the inputs / "
                                    "weights or run the fp32-MFMA build (ELO_DENSE_F32=1)" % bad)
-        return self.lane_poses(lane_index) if isinstance(lane["pose"], _ops.PoseRing) else self.lane_pose(lane_index)
+        return lane.last_pose() if isinstance(lane.pose, torch.Tensor) else lane.poses()
 
     def lane_input(self, lane_index):
         """The lane's input buffer, (2B,H,W,3) = [frame 1 | frame 2]: a producer (a data loader, elo_input_stage, the previous
         stage of a pipeline) that writes its range images HERE -- on the lane's stream, or ordered before the submit -- needs no
         copy: submit(lane_index) then replays on what the buffer holds."""
         self._check_fresh()
-        return self._lanes[lane_index]["pair"]
+        return self._lanes[lane_index].pair
 
     def _order_lane(self, lane, ready, *inputs):
         """submit()'s producer ordering on the torch path: the lane's stream waits for `ready` (an event the caller recorded behind
@@ -420,12 +448,12 @@ class PWCLONet:
         stream (record_stream: the caching allocator must not hand their memory out before the lane's copy has run)."""
         if ready is False:
             return
-        stream = lane["stream"]
+        stream = lane.stream
         if ready is None or ready is True:
             cur = torch.cuda.current_stream(self.device)
             if cur != stream and not cur.query():         # (an idle producer has nothing to wait for: no cross-queue barrier)
-                lane["order"].record(cur)
-                stream.wait_event(lane["order"])
+                lane.order.record(cur)
+                stream.wait_event(lane.order)
         else:
             stream.wait_event(ready)
         for x in inputs:
@@ -446,46 +474,31 @@ class PWCLONet:
         synchronised -- bench.py's pool -- or produced on the lane's own stream)."""
         self._check_fresh()
         lane = self._lanes[lane_index]
-        native = lane.get("native")
-        if native is not None and xyz_f2_proj is None and (ready is None or isinstance(ready, bool)):
+        native, pair = lane.native, lane.pair
+        if (native is not None and xyz_f2_proj is None and (ready is None or isinstance(ready, bool)) and
+                (xyz_f1_proj is None or (xyz_f1_proj.shape == pair.shape and xyz_f1_proj.dtype == pair.dtype
+                                         and xyz_f1_proj.device == pair.device and xyz_f1_proj.is_contiguous()))):
             # the host runtime's own submit (csrc/elo_host.cpp elo_graph_submit): the ordering, the copy and the graph launch as ONE
-            # native call on the lane's stream -- 16 us of host time instead of 29 through torch (tools/submit_native_probe.py)
-            pair = lane["pair"]
-            if xyz_f1_proj is None:
-                src, nbytes = None, 0
+            # native call on the lane's stream -- 16 us of host time instead of 29 through torch (tools/submit_native_probe.py); a pair
+            # that needs a conversion on its way in takes torch's copy_ below
+            src, nbytes = (None, 0) if xyz_f1_proj is None else (xyz_f1_proj.data_ptr(), native["nbytes"])
+            if ready is False:
+                producer = event = None
             else:
-                if (xyz_f1_proj.shape != pair.shape or xyz_f1_proj.dtype != pair.dtype or xyz_f1_proj.device != pair.device
-                        or not xyz_f1_proj.is_contiguous()):
-                    native = None                     # (a conversion is needed: torch's copy_ below does it)
-                else:
-                    src, nbytes = xyz_f1_proj.data_ptr(), native["nbytes"]
-            if native is not None:
-                n = lane.get("check_every", 0)
-                lane["total"] = lane.get("total", 0) + 1
-                checked = n and lane["total"] % n == 0
-                from . import _lib
-                if ready is False:
-                    producer = event = None
-                else:
-                    producer, event = torch.cuda.current_stream(self.device).cuda_stream, native["event"]
-                    if xyz_f1_proj is not None:
-                        xyz_f1_proj.record_stream(lane["stream"])
-                _lib.check(native["submit"](native["exec_checked"] if checked else native["exec"], native["stream"], native["dst"], src, nbytes,
-                                            producer, event, native["device"]))
-                lane["replays"] += 1
-                lane["last_checked"] = bool(checked)
-                return lane["out_checked"] if checked else lane["out"]
+                producer, event = torch.cuda.current_stream(self.device).cuda_stream, native["event"]
+                if xyz_f1_proj is not None:
+                    xyz_f1_proj.record_stream(lane.stream)
+            graph, out = lane.take()
+            _lib.check(native["submit"](native["exec"][graph], native["stream"], native["dst"], src, nbytes, producer, event, native["device"]))
+            return out
         self._order_lane(lane, ready, xyz_f1_proj, xyz_f2_proj)
-        with torch.cuda.stream(lane["stream"]):
-            if xyz_f1_proj is None:
-                pass
-            elif xyz_f2_proj is None:
-                lane["pair"].copy_(xyz_f1_proj, non_blocking=True)
-            else:
-                lane["in"][0].copy_(xyz_f1_proj, non_blocking=True)
-                lane["in"][1].copy_(xyz_f2_proj, non_blocking=True)
-            out = self._replay_lane(lane)
-        return out
+        with torch.cuda.stream(lane.stream):
+            if xyz_f2_proj is not None:
+                lane.inputs[0].copy_(xyz_f1_proj, non_blocking=True)
+                lane.inputs[1].copy_(xyz_f2_proj, non_blocking=True)
+            elif xyz_f1_proj is not None:
+                lane.pair.copy_(xyz_f1_proj, non_blocking=True)
+            return self._replay_lane(lane)
 
     def submit_points(self, lane_index, point_cloud, ready=None, motion=None, motion_is_pose=None):
         """Enqueue one forward from raw clouds (B, 2N, stride) on a lane captured with `num_points`.  `ready`: as submit().
@@ -495,83 +508,68 @@ class PWCLONet:
         given -- it is recorded in the graph and cannot change per submit."""
         self._check_fresh()
         lane = self._lanes[lane_index]
-        if "motion" not in lane:
+        if lane.motion is None:
             if motion is not None or motion_is_pose:
                 raise RuntimeError("this lane was captured without a sweep: capture(..., num_points=N, sweep=Sweep(...))")
-        elif motion_is_pose is not None and bool(motion_is_pose) != lane["motion_is_pose"]:
-            raise RuntimeError("motion_is_pose=%r was recorded into this lane's graph at capture()" % lane["motion_is_pose"])
+        elif motion_is_pose is not None and bool(motion_is_pose) != lane.motion_is_pose:
+            raise RuntimeError("motion_is_pose=%r was recorded into this lane's graph at capture()" % lane.motion_is_pose)
         if motion is not None and not isinstance(motion, torch.Tensor):
             motion = torch.from_numpy(np.ascontiguousarray(np.asarray(motion, dtype=np.float32)))
         self._order_lane(lane, ready, point_cloud, motion)
-        with torch.cuda.stream(lane["stream"]):
-            lane["cloud"].copy_(point_cloud, non_blocking=True)
+        with torch.cuda.stream(lane.stream):
+            lane.cloud.copy_(point_cloud, non_blocking=True)
             if motion is not None:
-                lane["motion"].copy_(motion.reshape(lane["motion"].shape), non_blocking=True)
-            out = self._replay_lane(lane)
-        return out
+                lane.motion.copy_(motion.reshape(lane.motion.shape), non_blocking=True)
+            return self._replay_lane(lane)
 
     def lane_motion(self, lane_index):
         """The (B,7) motion buffer of a lane captured with `sweep`: rows [q | t], read by the lane's input stage when its graph
         RUNS.  A producer on the device (the pose head of the previous pair, a filter) writes here -- on the lane's stream, or
         ordered before the submit -- and submit_points(lane, cloud) then de-skews with what it holds."""
-        lane = self._lanes[lane_index]
-        if "motion" not in lane:
+        if self._lanes[lane_index].motion is None:
             raise RuntimeError("this lane was captured without a sweep: it has no motion buffer")
-        return lane["motion"]
+        return self._lanes[lane_index].motion
 
     def lane_fit(self, lane_index, fit=None):
         """The _ops.PoseFitResult of the lane's last replay (capture(..., fit=PoseFit(...))): buffers the lane owns, written by
         the fit launches behind the l0 pose head; valid once the lane's stream has been synchronised or waited on.  `fit`: the
         PoseFit the caller expects the graphs to hold -- another one than capture() recorded is an error, not a silent mismatch."""
         lane = self._lanes[lane_index]
-        if "fit" not in lane:
+        if lane.fit is None:
             raise RuntimeError("this lane was captured without a pose fit: capture(..., fit=PoseFit(...))")
         if fit is not None and fit != self.captured_fit:
             raise RuntimeError("the captured graphs hold %r, not %r: a graph keeps the fit of its capture -- call capture() again"
                                % (self.captured_fit, fit))
-        return lane["fit_checked"] if lane.get("last_checked") and "fit_checked" in lane else lane["fit"]
+        return lane.fit_result()
 
     def lane_pose(self, lane_index):
         """The lane's (B,7) [l0_q_norm | l0_t] block, written by the l0 pose-head kernel of its last replay
         (capture(..., pose_ring=R): the slot of the last replay)."""
-        lane = self._lanes[lane_index]
-        pose = lane["pose"]
-        if isinstance(pose, _ops.PoseRing):
-            return pose.rows[(lane.get("base", 0) + lane["replays"] - 1) % pose.slots]
-        return pose
+        return self._lanes[lane_index].last_pose()
 
     def reset_poses(self, lane_index):
         """Pose ring of the lane back to slot 0 (one small launch, enqueued on the lane's stream)."""
         lane = self._lanes[lane_index]
-        with torch.cuda.stream(lane["stream"]):
-            lane["pose"].reset()
-        lane["replays"], lane["base"] = 0, 0
+        with torch.cuda.stream(lane.stream):
+            lane.pose.reset()
+        lane.reset()
 
     def mark_poses(self, lane_index):
         """Start a new collection WITHOUT touching the device: lane_poses() then returns the rows of the replays from here
         on (the device-side cursor keeps running; the host remembers which slot the next replay writes).  No launch -- a
         stream of short collections (bench.py's 20-step repeats) paid one reset launch per lane and collection before."""
-        lane = self._lanes[lane_index]
-        ring = lane["pose"]
-        lane["base"] = (lane.get("base", 0) + lane["replays"]) % ring.slots
-        lane["replays"] = 0
+        self._lanes[lane_index].mark()
 
     def lane_poses(self, lane_index):
         """(n,B,7): the rows of the lane's replays since reset_poses (n <= R, oldest first); a view of the ring, valid
         once the lane's stream has been synchronised or waited on."""
-        lane = self._lanes[lane_index]
-        ring, n, base = lane["pose"], lane["replays"], lane.get("base", 0)
-        if n > ring.slots:
-            raise RuntimeError("%d replays since reset_poses() on a ring of %d slots: rows were overwritten" % (n, ring.slots))
-        if base + n <= ring.slots:
-            return ring.rows[base:base + n]
-        return torch.cat([ring.rows[base:], ring.rows[:base + n - ring.slots]], 0)        # (wrapped: a copy, on the current stream)
+        return self._lanes[lane_index].poses()
 
     def lane_stream(self, lane_index):
-        return self._lanes[lane_index]["stream"]
+        return self._lanes[lane_index].stream
 
     def __call__(self, xyz_f1_proj, xyz_f2_proj):
-        if self._graph is None:
+        if not self._lanes:
             return self.forward(xyz_f1_proj, xyz_f2_proj)
         self.load_inputs(xyz_f1_proj, xyz_f2_proj)
         return self.replay()

@@ -54,7 +54,7 @@ def main():
         mine.submit_points(0, cloud, motion_is_pose=True)
     # a capture without a sweep is today's: no motion buffer
     mine.capture(1, H, W, num_points=N, point_stride=4, warmup=1)
-    assert "motion" not in mine._lanes[0]
+    assert mine._lanes[0].motion is None
     with pytest.raises(RuntimeError, match="without a sweep"):
         mine.lane_motion(0)
     with pytest.raises(RuntimeError, match="without a sweep"):

@@ -85,7 +85,7 @@ def main():
     net.capture(1, H, W, warmup=1)
     rep = net.submit(0, pair)
     torch.cuda.synchronize()
-    assert all(torch.equal(bits(r), bits(w)) for r, w in zip(rep, plain)) and "fit" not in net._lanes[0] and net.captured_fit is None
+    assert all(torch.equal(bits(r), bits(w)) for r, w in zip(rep, plain)) and net._lanes[0].fit is None and net.captured_fit is None
     with pytest.raises(RuntimeError, match="without a pose fit"):
         net.lane_fit(0)
 

@@ -229,7 +229,7 @@ def test_the_native_submit_replays_what_torch_replays():
         with tuning.override(native_submit=native):
             net = model.PWCLONet(DEV, seed=3)
             net.capture(1, 64, 1800, lanes=2, check_every=2)
-            assert (net._lanes[0]["native"] is not None) == native
+            assert (net._lanes[0].native is not None) == native
             rows = []
             for i, p in enumerate(pairs):
                 out = net.submit(i % 2, p)
@@ -261,7 +261,7 @@ def test_submit_waits_for_the_producer_of_its_input(native):
     with tuning.override(native_submit=native):
         net = model.PWCLONet(DEV, seed=3)
         net.capture(1, 64, 1800, lanes=2)
-        assert (net._lanes[0]["native"] is not None) == native
+        assert (net._lanes[0].native is not None) == native
         flat = lambda out: torch.cat([out[0].reshape(-1), out[1].reshape(-1)]).clone()
         out = net.submit(0, real)
         torch.cuda.synchronize()

@@ -27,7 +27,7 @@ pair = torch.cat([torch.from_numpy(f1), torch.from_numpy(f2)], 0).to(dev)
 def bench(stream_ids, steps=600):
     net = model.PWCLONet(dev, seed=0)
     net.capture(1, 64, 1800, lanes=len(stream_ids))
-    for lane, sid in zip(net._lanes, stream_ids): lane["stream"] = pool[sid]
+    for lane, sid in zip(net._lanes, stream_ids): lane.stream = pool[sid]
     n = len(stream_ids)
     for i in range(2 * n): net.submit(i % n, pair)
     torch.cuda.synchronize(); t0 = time.perf_counter()

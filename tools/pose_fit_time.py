@@ -157,7 +157,7 @@ if not args.no_net:
             with torch.cuda.stream(s):
                 a.record()
                 for _ in range(reps):
-                    net._lanes[0]["graph"].replay()
+                    net._lanes[0].graph.replay()
                 b.record()
             b.synchronize()
             return a.elapsed_time(b) * 1e3 / reps

@@ -27,7 +27,7 @@ for start in range(0, args.pairs, args.lanes):
         net.submit(lane, pairs[i])
     torch.cuda.synchronize()
     for lane, i in enumerate(chunk):
-        o = net._lanes[lane]["out"]
+        o = net._lanes[lane].out
         got = torch.cat([o[0].reshape(-1), o[1].reshape(-1)])
         if not torch.equal(got, want[i]):
             bad += 1

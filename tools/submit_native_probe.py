@@ -18,11 +18,11 @@ hip.hipGraphLaunch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
 L = net._lanes
 try:
-    execs = [l["graph"].raw_cuda_graph_exec() for l in L]
+    execs = [l.graph.raw_cuda_graph_exec() for l in L]
     print("exec handles:", [hex(e) for e in execs[:2]])
 except Exception as e:
     print("raw_cuda_graph_exec failed:", repr(e)); execs = None
-streams = [l["stream"].cuda_stream for l in L]
+streams = [l.stream.cuda_stream for l in L]
 nbytes = pair.numel() * 4
 def timed(name, fn, n=20, reps=3):
     for _ in range(reps):
@@ -33,15 +33,15 @@ def timed(name, fn, n=20, reps=3):
 timed("net.submit(lane, pair)", lambda i: net.submit(i % lanes, pair))
 timed("net.submit(lane) (no copy)", lambda i: net.submit(i % lanes))
 def torch_copy(i):
-    with torch.cuda.stream(L[i % lanes]["stream"]): L[i % lanes]["pair"].copy_(pair, non_blocking=True)
+    with torch.cuda.stream(L[i % lanes].stream): L[i % lanes].pair.copy_(pair, non_blocking=True)
 timed("torch copy_ only", torch_copy)
 def torch_replay(i):
-    with torch.cuda.stream(L[i % lanes]["stream"]): L[i % lanes]["graph"].replay()
+    with torch.cuda.stream(L[i % lanes].stream): L[i % lanes].graph.replay()
 timed("torch replay only", torch_replay)
 if execs:
     def raw(i):
         k = i % lanes
-        hip.hipMemcpyAsync(L[k]["pair"].data_ptr(), pair.data_ptr(), nbytes, 3, streams[k])
+        hip.hipMemcpyAsync(L[k].pair.data_ptr(), pair.data_ptr(), nbytes, 3, streams[k])
         hip.hipGraphLaunch(execs[k], streams[k])
     timed("ctypes memcpyAsync + graphLaunch", raw)
     timed("ctypes graphLaunch only", lambda i: hip.hipGraphLaunch(execs[i % lanes], streams[i % lanes]))
