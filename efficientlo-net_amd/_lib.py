@@ -47,6 +47,10 @@ SoftmaxPoolArgs = _struct("elo_softmax_pool_args", [
     ("batch", _i), ("npoints", _i), ("K", _i), ("C", _i), ("logits", _vp), ("values", _vp),
     ("values_stride", _i), ("mask", _vp), ("out", _vp), ("dtype", _i)])
 ELO_F32, ELO_F16 = 0, 1
+# what the elo_*_form queries answer (the ELO_ENCODE1_* / ELO_ENCODE2_* / ELO_POOL_* enumerators), by value
+ENCODE1_FORMS = ("scalar", "vec32", "vec64", "vec128", "col64", "col128", "staged128", "staged64")
+ENCODE2_FORMS = ("scalar", "vec32", "vec64", "vec128")
+POOL_FORMS = ("scalar", "vec6", "vec4", "wave1", "wave2", "wave4", "wave8")
 SoftmaxValidArgs = _struct("elo_softmax_valid_args", [
     ("batch", _i), ("npoints", _i), ("C", _i), ("feature", _vp), ("weight", _vp), ("xyz", _vp), ("out", _vp),
     ("scratch", _vp), ("stats", _vp)])
@@ -194,6 +198,9 @@ SYMBOLS = [
     ("elo_cv_encode1", ctypes.c_int, [ctypes.POINTER(CvEncode1Args), _vp]),
     ("elo_cv_encode2", ctypes.c_int, [ctypes.POINTER(CvEncode2Args), _vp]),
     ("elo_masked_softmax_pool", ctypes.c_int, [ctypes.POINTER(SoftmaxPoolArgs), _vp]),
+    ("elo_cv_encode1_form", ctypes.c_int, [ctypes.POINTER(CvEncode1Args)]),
+    ("elo_cv_encode2_form", ctypes.c_int, [ctypes.POINTER(CvEncode2Args)]),
+    ("elo_masked_softmax_pool_form", ctypes.c_int, [ctypes.POINTER(SoftmaxPoolArgs)]),
     ("elo_softmax_valid", ctypes.c_int, [ctypes.POINTER(SoftmaxValidArgs), _vp]),
     ("elo_pose_head", ctypes.c_int, [ctypes.POINTER(PoseHeadArgs), _vp]),
     ("elo_warp_project", ctypes.c_int, [ctypes.POINTER(WarpProjectArgs), _vp]),
@@ -307,6 +314,16 @@ def set_tuning(**fields):
     check(lib().elo_set_tuning(ctypes.byref(t)))
     from . import tuning
     tuning.bump()
+
+
+def form(query, args):
+    """The name of the kernel form `query` (an elo_*_form of include/elo.h) answers for `args`; raises where the entry point would
+    refuse them.  Host only: nothing is launched."""
+    names = {"elo_cv_encode1_form": ENCODE1_FORMS, "elo_cv_encode2_form": ENCODE2_FORMS, "elo_masked_softmax_pool_form": POOL_FORMS}[query]
+    rc = getattr(lib(), query)(ctypes.byref(args))
+    if rc < 0:
+        check(rc)
+    return names[rc]
 
 
 def check(rc):

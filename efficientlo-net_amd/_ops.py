@@ -148,7 +148,8 @@ def cv_encode1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask):
     return _cv_encode1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask)
 
 
-def _cv_encode1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask):
+def _cv_encode1_args(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask):
+    """The call's argument block, its output and the (contiguous) tensors the block points into."""
     L.require_gpu(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask)
     xyz1, xyz2_proj, mask = _f32(xyz1, xyz2_proj, mask)
     (feat1, feat2_proj), dt, code = _feature_dtype(feat1, feat2_proj)
@@ -158,8 +159,22 @@ def _cv_encode1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask):
     out = torch.empty((B, N, K, 10 + 2 * C), dtype=dt, device=idx.device)
     a = L.CvEncode1Args(B, N, K, H2, W2, C, xyz1.data_ptr(), feat1.data_ptr(), xyz2_proj.data_ptr(),
                         feat2_proj.data_ptr(), idx.data_ptr(), mask.data_ptr(), out.data_ptr(), code)
+    return a, out, (xyz1, feat1, xyz2_proj, feat2_proj, idx, mask)
+
+
+def _cv_encode1(*tensors):
+    a, out, _alive = _cv_encode1_args(*tensors)
     L.call("elo_cv_encode1", a, out)
     return out
+
+
+def cv_encode1_form(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask):
+    """Which kernel cv_encode1 launches for these tensors (include/elo.h: elo_cv_encode1_form; a name of _lib.ENCODE1_FORMS).
+    Raises where the call would.  Launches nothing, but builds the call's argument block (its output tensor included) to ask.  The form
+    depends on the tensors' addresses: the answer is the call's for tensors that are already contiguous -- of one that is not, the call
+    reads a fresh (16-byte aligned) contiguous copy, and so does this query, each its own.  The same holds for the two queries below."""
+    a, _out, _alive = _cv_encode1_args(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask)
+    return L.form("elo_cv_encode1_form", a)
 
 
 class _CvEncode2(torch.autograd.Function):
@@ -193,7 +208,7 @@ def cv_encode2(xyz1_proj, feat1_proj, cost_proj, idx, mask):
     return _cv_encode2(xyz1_proj, feat1_proj, cost_proj, idx, mask)
 
 
-def _cv_encode2(xyz1_proj, feat1_proj, cost_proj, idx, mask):
+def _cv_encode2_args(xyz1_proj, feat1_proj, cost_proj, idx, mask):
     L.require_gpu(xyz1_proj, feat1_proj, cost_proj, idx, mask)
     xyz1_proj, mask = _f32(xyz1_proj, mask)
     (feat1_proj, cost_proj), dt, code = _feature_dtype(feat1_proj, cost_proj)
@@ -205,8 +220,19 @@ def _cv_encode2(xyz1_proj, feat1_proj, cost_proj, idx, mask):
     rest = torch.empty((B, N, K, C + Cc), dtype=dt, device=idx.device)
     a = L.CvEncode2Args(B, N, K, H, W, C, Cc, xyz1_proj.data_ptr(), feat1_proj.data_ptr(), cost_proj.data_ptr(),
                         idx.data_ptr(), mask.data_ptr(), xyz_cat.data_ptr(), rest.data_ptr(), code)
-    L.call("elo_cv_encode2", a, rest)
-    return xyz_cat, rest
+    return a, (xyz_cat, rest), (xyz1_proj, feat1_proj, cost_proj, idx, mask)
+
+
+def _cv_encode2(*tensors):
+    a, outs, _alive = _cv_encode2_args(*tensors)
+    L.call("elo_cv_encode2", a, outs[1])
+    return outs
+
+
+def cv_encode2_form(xyz1_proj, feat1_proj, cost_proj, idx, mask):
+    """Which kernel cv_encode2 launches for these tensors (elo_cv_encode2_form; a name of _lib.ENCODE2_FORMS).  Launches nothing."""
+    a, _outs, _alive = _cv_encode2_args(xyz1_proj, feat1_proj, cost_proj, idx, mask)
+    return L.form("elo_cv_encode2_form", a)
 
 
 class _MaskedSoftmaxPool(torch.autograd.Function):
@@ -239,7 +265,7 @@ def masked_softmax_pool(logits, values, mask):
     return _masked_softmax_pool(logits, values, mask)
 
 
-def _masked_softmax_pool(logits, values, mask):
+def _masked_softmax_pool_args(logits, values, mask):
     L.require_gpu(logits, values, mask)
     (mask,) = _f32(mask)
     if logits.dtype not in (torch.float32, torch.float16):
@@ -254,8 +280,20 @@ def _masked_softmax_pool(logits, values, mask):
     out = torch.empty((B, N, C), dtype=dt, device=logits.device)
     a = L.SoftmaxPoolArgs(B, N, K, C, logits.data_ptr(), values.data_ptr(), values.stride(2), mask.data_ptr(),
                           out.data_ptr(), code)
+    return a, out, (logits, values, mask)
+
+
+def _masked_softmax_pool(*tensors):
+    a, out, _alive = _masked_softmax_pool_args(*tensors)
     L.call("elo_masked_softmax_pool", a, out)
     return out
+
+
+def masked_softmax_pool_form(logits, values, mask):
+    """Which kernel masked_softmax_pool launches for these tensors under the current tuning (elo_masked_softmax_pool_form; a name of
+    _lib.POOL_FORMS).  Launches nothing."""
+    a, _out, _alive = _masked_softmax_pool_args(logits, values, mask)
+    return L.form("elo_masked_softmax_pool_form", a)
 
 
 class _SoftmaxValid(torch.autograd.Function):

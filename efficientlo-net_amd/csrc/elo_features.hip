@@ -1363,63 +1363,91 @@ extern "C" int elo_masked_maxpool(const elo_masked_maxpool_args *a, elo_stream_t
     return check_launch(who);
 }
 
-extern "C" int elo_cv_encode1(const elo_cv_encode1_args *a, elo_stream_t stream)
+// ---- the dispatch ladders of the three entry points below, each written ONCE: the launcher switches on what its ladder names, and the
+// host-only elo_*_form queries (include/elo.h) answer with the same function -- a query cannot drift from what is launched.  They read
+// the argument block (pointer VALUES for their alignment, never what they point to) and, for the pool, the current tuning.
+static int cv_encode1_form(const elo_cv_encode1_args *a, const char *who)
 {
-    const char *who = "elo_cv_encode1";
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->batch >= 0 && a->npoints > 0 && a->K > 0 && a->H2 > 0 && a->W2 > 0 && a->C > 0, who, "bad sizes");
     ELO_REQUIRE(a->xyz1 && a->feat1 && a->xyz2 && a->feat2 && a->idx && a->mask && a->out, who, "null tensor pointer");
     const long rows = (long)a->batch * a->npoints * a->K;
-    if (rows == 0) return ELO_OK;
+    if (rows == 0) return ELO_ENCODE1_SCALAR;            // (nothing is launched: the entry point answers ELO_OK before it looks at the form)
     ELO_REQUIRE(a->dtype == ELO_F32 || a->dtype == ELO_F16, who, "dtype must be ELO_F32 or ELO_F16");
     const int esz = a->dtype == ELO_F16 ? 2 : 4;
     const bool vec = a->C % 2 == 0 && a->C < 500 && a->K < 32768 &&
                      ((uintptr_t)a->feat1 | (uintptr_t)a->feat2 | (uintptr_t)a->out) % (2 * esz) == 0;
     if (a->dtype == ELO_F16 && !vec) return fail(ELO_ERR_ARG, "%s: fp16 needs an even C < 500 and 4-byte aligned tensors", who);
-    if (vec) {
-        const int per = enc_rows(rows);
-        const FastDiv ds = fast_div(5 + a->C), dk = fast_div(a->K);
-        hipStream_t s = (hipStream_t)stream;
+    if (!vec) return ELO_ENCODE1_SCALAR;
+    const int per = enc_rows(rows);
+    const int rpi = ELO_BLOCK / (5 + a->C), batch_rows = rpi * ENC_BATCH;
+    // The staged form (the tile built in LDS, 16-byte accesses only) where the feature rows are whole 16-byte chunks and the tile fits.
+    // HBM-cold at the 128 x 2048 level shapes, batch 8, fp16 storage: l0 13.3 -> 10.3 us (0.42 -> 0.55 of 8 TB/s), l1 8.9 -> 5.7,
+    // l2_origin 15.7 -> 11.2; fp32 unchanged (15.3 us at l0: 82 MB, bound by its bytes there).  A "pair" form of the column-owner
+    // kernel (two rows per 16-byte slot column) was also measured -- fp32 l0 16.6 -> 15.4 us, fp16 no gain -- and is superseded by
+    // this one.  gpurun_out/r06/cold_levels_*staged.txt, cold_sweep_*_pairs.txt
+    const int per16 = 16 / esz;
+    if (ELO_ENCODE1_STAGED && a->C % per16 == 0 && rows >= 8192 &&
+        ((uintptr_t)a->feat1 | (uintptr_t)a->feat2 | (uintptr_t)a->out) % 16 == 0) {
+        const size_t row_bytes = (size_t)(10 + 2 * a->C) * esz;
+        const int R = 128 * row_bytes <= 40 * 1024 ? 128 : 64;
+        if (R * row_bytes <= 40 * 1024) return R == 128 ? ELO_ENCODE1_STAGED128 : ELO_ENCODE1_STAGED64;
+    }
+    const bool col_tiles = rpi * (5 + a->C) * 16 >= ELO_BLOCK * 15;      // <= 1/16 of the lanes idle
+    const int cper = per < 64 ? 64 : per;                                 // (the column-owner form keeps its 64-row workgroups on small calls)
+    if (batch_rows <= cper && col_tiles) return cper == 128 ? ELO_ENCODE1_COL128 : ELO_ENCODE1_COL64;
+    return per == 128 ? ELO_ENCODE1_VEC128 : per == 64 ? ELO_ENCODE1_VEC64 : ELO_ENCODE1_VEC32;
+}
+
+extern "C" int elo_cv_encode1_form(const elo_cv_encode1_args *a) { return cv_encode1_form(a, "elo_cv_encode1_form"); }
+
+extern "C" int elo_cv_encode1(const elo_cv_encode1_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_cv_encode1";
+    const int form = cv_encode1_form(a, who);
+    if (form < 0) return form;
+    const long rows = (long)a->batch * a->npoints * a->K;
+    if (rows == 0) return ELO_OK;
+    const bool f16 = a->dtype == ELO_F16;
+    const int esz = f16 ? 2 : 4;
+    const FastDiv ds = fast_div(5 + a->C), dk = fast_div(a->K);
+    hipStream_t s = (hipStream_t)stream;
+    switch (form) {
+    case ELO_ENCODE1_STAGED128:
+    case ELO_ENCODE1_STAGED64: {
+        const int R = form == ELO_ENCODE1_STAGED128 ? 128 : 64;
+        const size_t lds = R * (size_t)(10 + 2 * a->C) * esz;
+        const dim3 sgrid((unsigned)((rows + R - 1) / R));
+        if (f16) {
+            if (R == 128) hipLaunchKernelGGL((cv_encode1_staged_kernel<128, half_t>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
+            else hipLaunchKernelGGL((cv_encode1_staged_kernel<64, half_t>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
+        } else {
+            if (R == 128) hipLaunchKernelGGL((cv_encode1_staged_kernel<128, float>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
+            else hipLaunchKernelGGL((cv_encode1_staged_kernel<64, float>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
+        }
+        break;
+    }
+    case ELO_ENCODE1_COL128:
+    case ELO_ENCODE1_COL64: {
+        const int cper = form == ELO_ENCODE1_COL128 ? 128 : 64;
         const int rpi = ELO_BLOCK / (5 + a->C), batch_rows = rpi * ENC_BATCH;
-        // The staged form (the tile built in LDS, 16-byte accesses only) where the feature rows are whole 16-byte chunks and the tile fits.
-        // HBM-cold at the 128 x 2048 level shapes, batch 8, fp16 storage: l0 13.3 -> 10.3 us (0.42 -> 0.55 of 8 TB/s), l1 8.9 -> 5.7,
-        // l2_origin 15.7 -> 11.2; fp32 unchanged (15.3 us at l0: 82 MB, bound by its bytes there).  A "pair" form of the column-owner
-        // kernel (two rows per 16-byte slot column) was also measured -- fp32 l0 16.6 -> 15.4 us, fp16 no gain -- and is superseded by
-        // this one.  gpurun_out/r06/cold_levels_*staged.txt, cold_sweep_*_pairs.txt
-        const int per16 = 16 / esz;
-        if (ELO_ENCODE1_STAGED && a->C % per16 == 0 && rows >= 8192 &&
-            ((uintptr_t)a->feat1 | (uintptr_t)a->feat2 | (uintptr_t)a->out) % 16 == 0) {
-            const size_t row_bytes = (size_t)(10 + 2 * a->C) * esz;
-            const int R = 128 * row_bytes <= 40 * 1024 ? 128 : 64;
-            if (R * row_bytes <= 40 * 1024) {
-                const dim3 sgrid((unsigned)((rows + R - 1) / R));
-                const size_t lds = R * row_bytes;
-                if (a->dtype == ELO_F16) {
-                    if (R == 128) hipLaunchKernelGGL((cv_encode1_staged_kernel<128, half_t>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
-                    else hipLaunchKernelGGL((cv_encode1_staged_kernel<64, half_t>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
-                } else {
-                    if (R == 128) hipLaunchKernelGGL((cv_encode1_staged_kernel<128, float>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
-                    else hipLaunchKernelGGL((cv_encode1_staged_kernel<64, float>), sgrid, dim3(ELO_BLOCK), lds, s, *a, rows, dk);
-                }
-                return check_launch(who);
-            }
+        const int span = cper / batch_rows * batch_rows;
+        const dim3 cgrid((unsigned)((rows + span - 1) / span));
+        if (f16) {
+            if (cper == 128) hipLaunchKernelGGL((cv_encode1_col_kernel<128, half_t>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
+            else hipLaunchKernelGGL((cv_encode1_col_kernel<64, half_t>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
+        } else {
+            if (cper == 128) hipLaunchKernelGGL((cv_encode1_col_kernel<128, float>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
+            else hipLaunchKernelGGL((cv_encode1_col_kernel<64, float>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
         }
-        const bool col_tiles = rpi * (5 + a->C) * 16 >= ELO_BLOCK * 15;      // <= 1/16 of the lanes idle
-        const int cper = per < 64 ? 64 : per;                                 // (the column-owner form keeps its 64-row workgroups on small calls)
-        if (batch_rows <= cper && col_tiles) {
-            const int span = cper / batch_rows * batch_rows;
-            const dim3 cgrid((unsigned)((rows + span - 1) / span));
-            if (a->dtype == ELO_F16) {
-                if (cper == 128) hipLaunchKernelGGL((cv_encode1_col_kernel<128, half_t>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
-                else hipLaunchKernelGGL((cv_encode1_col_kernel<64, half_t>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
-            } else {
-                if (cper == 128) hipLaunchKernelGGL((cv_encode1_col_kernel<128, float>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
-                else hipLaunchKernelGGL((cv_encode1_col_kernel<64, float>), cgrid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk, rpi, span);
-            }
-            return check_launch(who);
-        }
+        break;
+    }
+    case ELO_ENCODE1_VEC128:
+    case ELO_ENCODE1_VEC64:
+    case ELO_ENCODE1_VEC32: {
+        const int per = form == ELO_ENCODE1_VEC128 ? 128 : form == ELO_ENCODE1_VEC64 ? 64 : 32;
         const dim3 grid((unsigned)((rows + per - 1) / per));
-        if (a->dtype == ELO_F16) {
+        if (f16) {
             if (per == 128) hipLaunchKernelGGL((cv_encode1_vec_kernel<128, half_t>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
             else if (per == 64) hipLaunchKernelGGL((cv_encode1_vec_kernel<64, half_t>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
             else hipLaunchKernelGGL((cv_encode1_vec_kernel<32, half_t>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
@@ -1428,32 +1456,51 @@ extern "C" int elo_cv_encode1(const elo_cv_encode1_args *a, elo_stream_t stream)
             else if (per == 64) hipLaunchKernelGGL((cv_encode1_vec_kernel<64, float>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
             else hipLaunchKernelGGL((cv_encode1_vec_kernel<32, float>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
         }
-        return check_launch(who);
+        break;
     }
-    hipLaunchKernelGGL(cv_encode1_kernel, dim3(grid_for_stage(rows)), dim3(ELO_BLOCK), sizeof(float) * (STAGE_ROWS * (10 + 2 * a->C) + 1) + STAGE_META_BYTES,
-                       (hipStream_t)stream, *a, rows);
+    default:                                             // ELO_ENCODE1_SCALAR
+        hipLaunchKernelGGL(cv_encode1_kernel, dim3(grid_for_stage(rows)), dim3(ELO_BLOCK), sizeof(float) * (STAGE_ROWS * (10 + 2 * a->C) + 1) + STAGE_META_BYTES,
+                           s, *a, rows);
+    }
     return check_launch(who);
 }
 
-extern "C" int elo_cv_encode2(const elo_cv_encode2_args *a, elo_stream_t stream)
+static int cv_encode2_form(const elo_cv_encode2_args *a, const char *who)
 {
-    const char *who = "elo_cv_encode2";
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->batch >= 0 && a->npoints > 0 && a->K > 0 && a->H > 0 && a->W > 0 && a->C > 0 && a->Cc > 0, who, "bad sizes");
     ELO_REQUIRE(a->npoints == a->H * a->W, who, "npoints must equal H*W (every pixel is a centre)");
     ELO_REQUIRE(a->xyz1 && a->feat1 && a->cost && a->idx && a->mask && a->xyz_cat && a->rest, who, "null tensor pointer");
     const long rows = (long)a->batch * a->npoints * a->K;
-    if (rows == 0) return ELO_OK;
+    if (rows == 0) return ELO_ENCODE2_SCALAR;            // (nothing is launched)
     ELO_REQUIRE(a->dtype == ELO_F32 || a->dtype == ELO_F16, who, "dtype must be ELO_F32 or ELO_F16");
     const int esz = a->dtype == ELO_F16 ? 2 : 4, per16 = 16 / esz;
     const bool vec = a->C % per16 == 0 && a->Cc % per16 == 0 && a->C + a->Cc < 2000 && a->K < 32768 &&
                      ((uintptr_t)a->feat1 | (uintptr_t)a->cost | (uintptr_t)a->rest) % 16 == 0 && (uintptr_t)a->xyz_cat % (2 * esz) == 0;
     if (a->dtype == ELO_F16 && !vec) return fail(ELO_ERR_ARG, "%s: fp16 needs C and Cc multiples of 8 and 16-byte aligned tensors", who);
-    if (vec) {
-        const int per = enc_rows(rows);
+    if (!vec) return ELO_ENCODE2_SCALAR;
+    const int per = enc_rows(rows);
+    return per == 128 ? ELO_ENCODE2_VEC128 : per == 64 ? ELO_ENCODE2_VEC64 : ELO_ENCODE2_VEC32;
+}
+
+extern "C" int elo_cv_encode2_form(const elo_cv_encode2_args *a) { return cv_encode2_form(a, "elo_cv_encode2_form"); }
+
+extern "C" int elo_cv_encode2(const elo_cv_encode2_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_cv_encode2";
+    const int form = cv_encode2_form(a, who);
+    if (form < 0) return form;
+    const long rows = (long)a->batch * a->npoints * a->K;
+    if (rows == 0) return ELO_OK;
+    hipStream_t s = (hipStream_t)stream;
+    switch (form) {
+    case ELO_ENCODE2_VEC128:
+    case ELO_ENCODE2_VEC64:
+    case ELO_ENCODE2_VEC32: {
+        const int per = form == ELO_ENCODE2_VEC128 ? 128 : form == ELO_ENCODE2_VEC64 ? 64 : 32;
+        const int per16 = a->dtype == ELO_F16 ? 8 : 4;
         const dim3 grid((unsigned)((rows + per - 1) / per));
         const FastDiv ds = fast_div((a->C + a->Cc) / per16), dk = fast_div(a->K);
-        hipStream_t s = (hipStream_t)stream;
         if (a->dtype == ELO_F16) {
             if (per == 128) hipLaunchKernelGGL((cv_encode2_vec_kernel<128, half_t>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
             else if (per == 64) hipLaunchKernelGGL((cv_encode2_vec_kernel<64, half_t>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
@@ -1463,56 +1510,79 @@ extern "C" int elo_cv_encode2(const elo_cv_encode2_args *a, elo_stream_t stream)
             else if (per == 64) hipLaunchKernelGGL((cv_encode2_vec_kernel<64, float>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
             else hipLaunchKernelGGL((cv_encode2_vec_kernel<32, float>), grid, dim3(ELO_BLOCK), 0, s, *a, rows, ds, dk);
         }
-        return check_launch(who);
+        break;
     }
-    hipLaunchKernelGGL(cv_encode2_kernel, dim3(grid_for_stage(rows)), dim3(ELO_BLOCK), sizeof(float) * (STAGE_ROWS * (10 + a->C + a->Cc) + 1) + STAGE_META_BYTES,
-                       (hipStream_t)stream, *a, rows);
+    default:                                             // ELO_ENCODE2_SCALAR
+        hipLaunchKernelGGL(cv_encode2_kernel, dim3(grid_for_stage(rows)), dim3(ELO_BLOCK), sizeof(float) * (STAGE_ROWS * (10 + a->C + a->Cc) + 1) + STAGE_META_BYTES,
+                           s, *a, rows);
+    }
     return check_launch(who);
 }
 
-extern "C" int elo_masked_softmax_pool(const elo_softmax_pool_args *a, elo_stream_t stream)
+static int softmax_pool_form(const elo_softmax_pool_args *a, const char *who)
 {
-    const char *who = "elo_masked_softmax_pool";
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->batch >= 0 && a->npoints > 0 && a->K > 0 && a->C > 0 && a->values_stride >= a->C, who, "bad sizes");
     ELO_REQUIRE(a->logits && a->values && a->mask && a->out, who, "null tensor pointer");
     const long rows = (long)a->batch * a->npoints;
-    if (rows == 0) return ELO_OK;
+    if (rows == 0) return ELO_POOL_SCALAR;               // (nothing is launched)
     ELO_REQUIRE(a->dtype == ELO_F32 || a->dtype == ELO_F16, who, "dtype must be ELO_F32 or ELO_F16");
     const int esz = a->dtype == ELO_F16 ? 2 : 4;
     const bool vec = a->C % 4 == 0 && a->C <= 1024 && ELO_BLOCK % (a->C / 4) == 0 && a->values_stride % 4 == 0 &&
                      ((uintptr_t)a->logits | (uintptr_t)a->values | (uintptr_t)a->out) % (4 * esz) == 0;
     if (a->dtype == ELO_F16 && !vec) return fail(ELO_ERR_ARG, "%s: fp16 needs C % 4 == 0 and 8-byte aligned tensors", who);
+    if (!vec) return ELO_POOL_SCALAR;
     // (fp32 storage only: in fp16 a point is 768 bytes per tensor -- even at two points per wave the form is instruction-bound,
     //  31.9 us against the quarter-wave form's 23.5 at the 128 x 2048 l0 shape, batch 8: gpurun_out/r06/cold_sweep_f16_pw1d.txt)
-    if (vec && a->dtype == ELO_F32 && a->C == 64 && a->K <= 32 && a->values_stride % (16 / esz) == 0 &&
+    if (a->dtype == ELO_F32 && a->C == 64 && a->K <= 32 && a->values_stride % (16 / esz) == 0 &&
         ((uintptr_t)a->logits | (uintptr_t)a->values | (uintptr_t)a->out) % 16 == 0 && tuning().pool_wave) {   // wave per point (round 6): 16-byte loads, many light waves
+        const int J = (a->K + 3) / 4;                                            // neighbour rows per lane group
+        return J == 1 ? ELO_POOL_WAVE1 : J == 2 ? ELO_POOL_WAVE2 : J <= 4 ? ELO_POOL_WAVE4 : ELO_POOL_WAVE8;
+    }
+    return a->K % 6 == 0 ? ELO_POOL_VEC6 : ELO_POOL_VEC4;
+}
+
+extern "C" int elo_masked_softmax_pool_form(const elo_softmax_pool_args *a) { return softmax_pool_form(a, "elo_masked_softmax_pool_form"); }
+
+extern "C" int elo_masked_softmax_pool(const elo_softmax_pool_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_masked_softmax_pool";
+    const int form = softmax_pool_form(a, who);
+    if (form < 0) return form;
+    const long rows = (long)a->batch * a->npoints;
+    if (rows == 0) return ELO_OK;
+    hipStream_t s = (hipStream_t)stream;
+    switch (form) {
+    case ELO_POOL_WAVE1:
+    case ELO_POOL_WAVE2:
+    case ELO_POOL_WAVE4:
+    case ELO_POOL_WAVE8: {
         const long ppb = ELO_BLOCK / 64;                                         // points per workgroup
         const dim3 grid((unsigned)((rows + ppb - 1) / ppb));
-        hipStream_t s = (hipStream_t)stream;
-        const int J = (a->K + 3) / 4;                                            // neighbour rows per lane group
 #define ELO_POOL_WAVE(J_) hipLaunchKernelGGL((softmax_pool_wave_kernel<float, J_>), grid, dim3(ELO_BLOCK), 0, s, *a, rows)
-        if (J == 1) ELO_POOL_WAVE(1);
-        else if (J == 2) ELO_POOL_WAVE(2);
-        else if (J <= 4) ELO_POOL_WAVE(4);
+        if (form == ELO_POOL_WAVE1) ELO_POOL_WAVE(1);
+        else if (form == ELO_POOL_WAVE2) ELO_POOL_WAVE(2);
+        else if (form == ELO_POOL_WAVE4) ELO_POOL_WAVE(4);
         else ELO_POOL_WAVE(8);
 #undef ELO_POOL_WAVE
-        return check_launch(who);
+        break;
     }
-    if (vec) {
+    case ELO_POOL_VEC6:
+    case ELO_POOL_VEC4: {
         const int rows_per_block = ELO_BLOCK / (a->C / 4);
         const dim3 grid((unsigned)((rows + rows_per_block - 1) / rows_per_block));
-        hipStream_t s = (hipStream_t)stream;
-        if (a->K % 6 == 0) {
+        if (form == ELO_POOL_VEC6) {
             if (a->dtype == ELO_F16) hipLaunchKernelGGL((softmax_pool_vec_kernel<half_t, 6, true>), grid, dim3(ELO_BLOCK), 0, s, *a, rows);
             else hipLaunchKernelGGL((softmax_pool_vec_kernel<float, 6>), grid, dim3(ELO_BLOCK), 0, s, *a, rows);
         } else {
             if (a->dtype == ELO_F16) hipLaunchKernelGGL((softmax_pool_vec_kernel<half_t, 4, true>), grid, dim3(ELO_BLOCK), 0, s, *a, rows);
             else hipLaunchKernelGGL((softmax_pool_vec_kernel<float, 4>), grid, dim3(ELO_BLOCK), 0, s, *a, rows);
         }
-        return check_launch(who);
+        break;
     }
-    hipLaunchKernelGGL(softmax_pool_kernel, dim3(grid_for_rows(rows)), dim3(ELO_BLOCK), 0, (hipStream_t)stream, *a, rows);
+    default:                                             // ELO_POOL_SCALAR
+        hipLaunchKernelGGL(softmax_pool_kernel, dim3(grid_for_rows(rows)), dim3(ELO_BLOCK), 0, s, *a, rows);
+    }
     return check_launch(who);
 }
 

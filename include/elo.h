@@ -250,6 +250,31 @@ typedef struct elo_softmax_pool_args {
 } elo_softmax_pool_args;
 int elo_masked_softmax_pool(const elo_softmax_pool_args *a, elo_stream_t stream);
 
+/* WHICH KERNEL the three entry points above launch for an argument block (host-only queries: nothing is launched, no tensor pointer is
+ * dereferenced -- only the pointers' VALUES are read, for their alignment -- and elo_masked_softmax_pool_form also reads the current
+ * elo_tuning.pool_wave).  Each entry point switches on the same function, so the answer is what a launch with these arguments takes.
+ * All forms of an entry point compute the same function; the storage type (fp32 / fp16 instance) is the block's `dtype`.
+ * Return: one of the enumerators below, or the negative elo_status with which the entry point would refuse the block (bad sizes, a
+ * NULL pointer, fp16 storage with a channel count or an alignment its vector forms cannot take: fp16 has no scalar form).
+ * With batch == 0 the entry points launch nothing and the answer is the scalar enumerator.
+ *   elo_cv_encode1: VEC<R> / COL<R> / STAGED<R> work on R-row workgroups (R by the row count batch*npoints*K: 32 below 64 Ki rows,
+ *     64 from there, 128 above 512 Ki).  STAGED (the tile built in LDS, 16-byte accesses): >= 8192 rows, 16-byte aligned feature
+ *     tensors, C a multiple of 16 bytes' worth of elements, and the tile within 40 KB (128 rows, else 64).  COL (a thread owns a slot
+ *     column): where whole rows tile the 256 threads with at most 1/16 of them idle.  VEC otherwise; SCALAR (fp32 only): odd C,
+ *     C >= 500, K >= 32768 or feature tensors off 8-byte alignment.
+ *   elo_cv_encode2: VEC<R> with C and Cc multiples of 16 bytes' worth of elements and 16-byte aligned tensors, else SCALAR (fp32 only).
+ *   elo_masked_softmax_pool: WAVE<J> (fp32, C = 64, K <= 32, 16-byte aligned, pool_wave on; J = 1, 2, 4, 8 >= ceil(K / 4) neighbour rows
+ *     per lane group), VEC6 / VEC4 (C % 4 == 0, 256 % (C / 4) == 0, C <= 1024, values_stride % 4 == 0, tensors aligned to four elements;
+ *     six rows in flight when K % 6 == 0, else four), SCALAR (fp32 only) otherwise. */
+enum { ELO_ENCODE1_SCALAR = 0, ELO_ENCODE1_VEC32 = 1, ELO_ENCODE1_VEC64 = 2, ELO_ENCODE1_VEC128 = 3, ELO_ENCODE1_COL64 = 4,
+       ELO_ENCODE1_COL128 = 5, ELO_ENCODE1_STAGED128 = 6, ELO_ENCODE1_STAGED64 = 7 };
+enum { ELO_ENCODE2_SCALAR = 0, ELO_ENCODE2_VEC32 = 1, ELO_ENCODE2_VEC64 = 2, ELO_ENCODE2_VEC128 = 3 };
+enum { ELO_POOL_SCALAR = 0, ELO_POOL_VEC6 = 1, ELO_POOL_VEC4 = 2, ELO_POOL_WAVE1 = 3, ELO_POOL_WAVE2 = 4, ELO_POOL_WAVE4 = 5,
+       ELO_POOL_WAVE8 = 6 };
+int elo_cv_encode1_form(const elo_cv_encode1_args *a);
+int elo_cv_encode2_form(const elo_cv_encode2_args *a);
+int elo_masked_softmax_pool_form(const elo_softmax_pool_args *a);
+
 /* Fresh visiting orders per replay of a captured forward (tf.random_shuffle inside every operator on every sess.run:
  * utils/pointnet_util.py:45,104,193,270).  All order tensors of a forward are slices of `flat` (their decoded (dh, dw)
  * forms, elo_group_spec.decoded_hw, slices of `decoded`); `pool` holds `versions` pre-drawn contents of `flat`.  One

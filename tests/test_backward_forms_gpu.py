@@ -14,62 +14,19 @@ import torch
 
 import twins_torch as twin
 from backward_check import _boundary_safe_points, _check
-from conftest import expand_prefix, load_pkg
+from conftest import load_pkg
+from forms_inputs import at_offset as _at_offset                   # (4 bytes past a 16-byte boundary: the kernels' scalar forms)
+from forms_inputs import cv_encode1_inputs, cv_encode2_inputs
+from forms_inputs import maxpool_inputs as _maxpool_inputs
+from forms_inputs import slots as _slots
+from forms_inputs import softmax_pool_inputs as _softmax_pool_inputs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
-def _at_offset(x):
-    """x's values in a contiguous tensor 4 bytes past a 16-byte boundary (differentiable): the kernels' scalar forms."""
-    y = torch.cat([x.new_zeros(1), x.reshape(-1)])[1:].view(x.shape)
-    assert y.is_contiguous() and y.data_ptr() % 16 == 4
-    return y
-
-
-def _counts(rng, B, N, K):
-    """valid-slot counts of prefix-ones masks with the edges at fixed points: all masked, one valid slot, all valid."""
-    c = rng.integers(0, K + 1, (B, N))
-    c[:, 0], c[:, 1], c[:, 2] = 0, 1, K
-    return c
-
-
-def _mask(counts, K):
-    return expand_prefix(counts, K)[..., 0]                        # (B, N, K) of 0/1
-
-
-def _slots(rng, B, N, K, H2, W2, masked_at="origin"):
-    """Synthetic neighbour slots [b, h, w] (B,N,K,3) int32 and a prefix-ones mask (B,N,K).  Half of the live slots go to 8 hot cells
-    per image (their atomics pile up); a masked slot points at cell (0,0,0) as the grouping kernels leave it, or anywhere."""
-    mask = _mask(_counts(rng, B, N, K), K)
-    h, w = rng.integers(0, H2, (B, N, K)), rng.integers(0, W2, (B, N, K))
-    hot = rng.random((B, N, K)) < 0.5
-    j = rng.integers(0, 8, (B, N, K))
-    hh, hw = rng.integers(0, H2, 8), rng.integers(0, W2, 8)
-    h, w = np.where(hot, hh[j], h), np.where(hot, hw[j], w)
-    idx = np.stack([np.broadcast_to(np.arange(B)[:, None, None], (B, N, K)), h, w], -1).astype(np.int32)
-    off = mask == 0
-    if masked_at == "origin":
-        idx[off] = 0
-    else:
-        idx[off, 0] = rng.integers(0, B, int(off.sum()))
-    return idx, mask.astype(np.float32)
-
-
 # ---------------------------------------------------------------------------------------------------------------- masked max-pool
-def _maxpool_inputs(rng, B, N, K, C):
-    """Post-ReLU values (about half exact zeros) with ties built in, and a prefix-ones mask."""
-    counts = _counts(rng, B, N, K)
-    if K > 1:
-        counts[:, 3::7] = rng.integers(1, K, counts[:, 3::7].shape)  # ... with at least one masked slot at these points:
-    x = np.maximum(rng.normal(0, 1, (B, N, K, C)), 0).astype(np.float32)
-    x[:, 3::7] = -np.abs(x[:, 3::7]) - 0.25                          # every valid product negative: the masked +-0 wins
-    x[..., 1] = x[..., :1, 1]                                        # channel 1 equal on all K slots: a K-way (or masked) tie
-    x[:, 5::9, -1] = x[:, 5::9, 0]                                   # a duplicated neighbour (flag_copy)
-    return x, _mask(counts, K).astype(np.float32)
-
-
 MAXPOOL_BWD = [pytest.param(K, C, False, id="bwd_vec<%d>-K%d-C%d" % (K, K, C)) for K, C in
                ((4, 16), (4, 128), (8, 32), (8, 64), (16, 64), (16, 16), (32, 128), (32, 32))]
 MAXPOOL_BWD += [pytest.param(K, C, False, id="bwd_scalar-K%d-C%d" % (K, C)) for K, C in
@@ -117,18 +74,6 @@ def test_masked_maxpool_forms_give_the_same_bits(K):
 
 
 # ---------------------------------------------------------------------------------------------------------------- masked softmax pool
-def _softmax_pool_inputs(rng, B, N, K, C, width=None):
-    """Logits with the edges: all-masked points, a single valid slot, masked logits above every valid one, and (every other point)
-    logits spread over ~+-120 so that some exponentials underflow to 0.  Values `width` channels wide (the op reads the first C)."""
-    counts = _counts(rng, B, N, K)
-    m = _mask(counts, K)
-    lg = rng.normal(0, 1, (B, N, K, C))
-    lg[:, 1::2] *= 40.0
-    lg = np.where((m[..., None] == 0) & (rng.random((B, N, 1, 1)) < 0.5), 1e3, lg)
-    v = rng.normal(0, 1, (B, N, K, width or C))
-    return lg.astype(np.float32), v.astype(np.float32), m.astype(np.float32)
-
-
 SOFTMAX_BWD = [pytest.param(K, 64, None, id="bwd_%s<%d>-K%d-C64" % ("vec2" if K > 8 else "vec", K, K)) for K in (4, 6, 8, 16, 32)]
 SOFTMAX_BWD += [pytest.param(K, 64, (96, 32), id="bwd_%s<%d>-K%d-C64-values_wide96[32:96]" % ("vec2" if K > 8 else "vec", K, K))
                 for K in (4, 6, 8, 16, 32)]
@@ -232,17 +177,7 @@ def test_cv_encode1_backward(B, H, W, K, C, wrt):
     the centre (d = 0: the norm's gradient is 0 / 1e-10)."""
     ops = load_pkg("_ops")
     rng = np.random.default_rng(B * 1000 + K + C)
-    N = 2 * H * W
-    idx, m = _slots(rng, B, N, K, H, W, "anywhere" if K == 32 else "origin")
-    xyz1 = rng.normal(0, 5, (B, N, 3)).astype(np.float32)
-    xyz2 = rng.normal(0, 5, (B, H, W, 3)).astype(np.float32)
-    for b in range(B):
-        for n in range(4, N, 5):
-            if m[b, n, 0] == 1:
-                idx[b, n, 0] = (b, n % H, (n // H) % W)
-                xyz2[b, n % H, (n // H) % W] = xyz1[b, n]
-    f1 = rng.normal(0, 1, (B, N, C)).astype(np.float32)
-    f2 = rng.normal(0, 1, (B, H, W, C)).astype(np.float32)
+    xyz1, f1, xyz2, f2, idx, m = cv_encode1_inputs(rng, B, 2 * H * W, H, W, K, C, "anywhere" if K == 32 else "origin")
     _check(ops.cv_encode1, twin.cv_encode1, [t(xyz1), t(f1), t(xyz2), t(f2), t(idx), t(m)], wrt=wrt)
 
 
@@ -251,14 +186,7 @@ def test_cv_encode2_backward(B, H, W, K, C, wrt):
     """cv_encode2_bwd_kernel: centres are the grid's own pixels; the first slot of every 5th pixel is the pixel itself (d = 0)."""
     ops = load_pkg("_ops")
     rng = np.random.default_rng(B * 1000 + K + C + 1)
-    N = H * W
-    idx, m = _slots(rng, B, N, K, H, W, "anywhere" if K == 6 else "origin")
-    for n in range(4, N, 5):
-        live = m[:, n, 0] == 1
-        idx[live, n, 0] = np.stack([np.arange(B), np.full(B, n // W), np.full(B, n % W)], -1)[live]
-    xyz = rng.normal(0, 5, (B, H, W, 3)).astype(np.float32)
-    f1 = rng.normal(0, 1, (B, H, W, C)).astype(np.float32)
-    cost = rng.normal(0, 1, (B, H, W, C)).astype(np.float32)
+    xyz, f1, cost, idx, m = cv_encode2_inputs(rng, B, H, W, K, C, masked_at="anywhere" if K == 6 else "origin")
     _check(ops.cv_encode2, twin.cv_encode2, [t(xyz), t(f1), t(cost), t(idx), t(m)], wrt=wrt)
 
 

@@ -182,3 +182,8 @@ def test_the_rejected_kernel_forms_live_in_a_patch_that_still_applies(tmp_path):
     assert out.returncode == 0, out.stdout + out.stderr
     patched = (tmp_path / "efficientlo-net_amd" / "csrc" / "elo_fused.hip").read_text()
     assert "rowlinear_rr_kernel" in patched and "setconv_tiled_kernel" in patched and "bool PRE = false" in patched
+    # every hunk of elo_features.hip lands too (a hunk with wrong line counts makes patch drop the ones behind it and still exit 0):
+    # the slot-indexed cv_encode1 switch sits in the middle of the file, the pose head's direct launcher at its end
+    features = (tmp_path / "efficientlo-net_amd" / "csrc" / "elo_features.hip").read_text()
+    assert "!tuning().encode1_slots" in features and features.count("a->direct") == 3
+    assert not list(tmp_path.rglob("*.rej"))
