@@ -92,6 +92,10 @@ PoseFitArgs = _struct("elo_pose_fit_args", [
     ("pose_in", _vp), ("beam_elev", _vp), ("iters", _i), ("gate", _f), ("huber", _f), ("jump_rel", _f), ("min_count", _i),
     ("damping", _f), ("pose_out", _vp), ("info", _vp), ("grad", _vp), ("stats", _vp), ("scratch", _vp)])
 FIT_FEW, FIT_SINGULAR, FIT_FEW_FINAL = 1, 2, 4        # ELO_FIT_*
+ModelRenderArgs = _struct("elo_model_render_args", [
+    ("batch", _i), ("K", _i), ("H", _i), ("W", _i), ("az_res", _f), ("vert_res", _f), ("vert_off", _f), ("src", _vp), ("pose", _vp),
+    ("beam_elev", _vp), ("out_xyz", _vp), ("out_src", _vp), ("scratch", _vp)])
+MODEL_MAX_SCANS = 16   # ELO_MODEL_MAX_SCANS
 
 # backward passes (csrc/elo_backward.hip)
 GroupConcatBwdArgs = _struct("elo_group_concat_bwd_args", [
@@ -212,6 +216,8 @@ SYMBOLS = [
     ("elo_pose_fit", ctypes.c_int, [ctypes.POINTER(PoseFitArgs), _vp]),
     ("elo_pose_fit_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
     ("elo_pose_fit_parts", ctypes.c_int, [ctypes.c_int] * 2),
+    ("elo_model_render", ctypes.c_int, [ctypes.POINTER(ModelRenderArgs), _vp]),
+    ("elo_model_render_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),
     ("elo_masked_maxpool_backward", ctypes.c_int, [ctypes.POINTER(MaskedMaxpoolBwdArgs), _vp]),
     ("elo_cv_encode1_backward", ctypes.c_int, [ctypes.POINTER(CvEncode1BwdArgs), _vp]),

@@ -775,6 +775,66 @@ def pose_fit(xyz1, xyz2, pose7, fit, sensor=None, beam_elev=None):
     return res
 
 
+def _check_model_render(src, pose, beam_elev):
+    """What the host can refuse about a model render without a GPU or the library: shapes, dtypes, layout, devices."""
+    for name, t in (("src", src), ("pose", pose)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s is a tensor (got %r)" % (name, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s is float32 (got %s)" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise L.EloError("%s must be contiguous: the launch reads it in place" % name)
+    if src.dim() != 5 or src.shape[-1] != 3:
+        raise L.EloError("src is (B,K,H,W,3): K range images per batch element (got %s)" % (tuple(src.shape),))
+    B, K, H, W, _ = src.shape
+    if K < 1 or K > L.MODEL_MAX_SCANS:
+        raise L.EloError("a model holds 1 .. %d scans (K = %d)" % (L.MODEL_MAX_SCANS, K))
+    if H < 1 or W < 1:
+        raise L.EloError("src has no cells: H, W >= 1 (got %d x %d)" % (H, W))
+    if K * H * W >= 2 ** 31 or B * H * W >= 2 ** 31:
+        raise L.EloError("K*H*W and B*H*W stay below 2^31 (got B, K, H, W = %d, %d, %d, %d)" % (B, K, H, W))
+    if tuple(pose.shape) != (B, K, 7):
+        raise L.EloError("pose is one [q0 q1 q2 q3 | t0 t1 t2] row per source: (%d, %d, 7) (got %s)" % (B, K, tuple(pose.shape)))
+    if pose.device != src.device:
+        raise L.EloError("src and pose live on one device")
+    if isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda:
+        if (beam_elev.device != src.device or beam_elev.dtype != torch.float32 or not beam_elev.is_contiguous()
+                or beam_elev.numel() != H):
+            raise L.EloError("a device beam table is a contiguous float32 tensor of H = %d entries on the images' device" % H)
+    if (beam_elev is not None) and H > L.MAX_BEAMS:
+        raise L.EloError("a beam table has at most %d beams (H = %d)" % (L.MAX_BEAMS, H))
+
+
+def model_render(src, pose, sensor=None, beam_elev=None):
+    """elo_model_render: the K range images src (B,K,H,W,3), each carried by its row of pose (B,K,7) [q | t] (source k -> the
+    model's frame), rendered into one range image by nearest range -> (xyz (B,H,W,3) float32, src_idx (B,H,W) int32: (k*H + h)*W + w
+    of the point each cell holds, -1 where it is empty).  `sensor` / `beam_elev`: the cell rule, as pose_fit takes them.  Inputs
+    are float32, contiguous and used in place: both are read when the launches RUN (a graph that records this call renders what
+    they hold at every replay).  Bad shapes, dtypes or layouts are refused here, before anything is launched."""
+    _check_model_render(src, pose, beam_elev)
+    sensor = _sensor.resolve(sensor)
+    L.require_gpu(src, pose)
+    B, K, H, W, _ = src.shape
+    dev = src.device
+    if beam_elev is None and sensor.beam_elevations_deg is not None:
+        beam_elev = sensor
+    if beam_elev is not None and not (isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda):
+        if torch.cuda.is_current_stream_capturing():
+            raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
+        beam_elev = beam_table(beam_elev, H, dev)
+    words = L.lib().elo_model_render_scratch_words(B, H, W)
+    if words < 0:
+        raise L.EloError("elo_model_render refuses a (%d,%d,%d) batch of images" % (B, H, W))
+    xyz = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    scratch = torch.empty((max(words, 2),), dtype=torch.int32, device=dev)
+    az, vres, voff = projection_constants(H, W, sensor) if H > 1 else (projection_constants(2, W, sensor)[0], 1.0, 0.0)
+    a = L.ModelRenderArgs(B, K, H, W, az, vres, voff, src.data_ptr(), pose.data_ptr(), _ptr(beam_elev), xyz.data_ptr(), idx.data_ptr(),
+                          scratch.data_ptr())
+    L.call("elo_model_render", a, src)
+    return xyz, idx
+
+
 class _WarpProject(torch.autograd.Function):
     """elo_warp_project / elo_warp_project_backward.  The forward's scratch (who won each cell) is kept for the backward."""
 

@@ -14,8 +14,10 @@ import os
 import numpy as np
 import torch
 
-from . import kitti
+from . import kitti, pwclo_model
+from .local_model import ModelTracker
 from .distributed import quat2mat
+from .sensor import LocalModel
 
 
 def pose_rows(q_n4, t_n3, Tr):
@@ -36,7 +38,7 @@ def pose_rows(q_n4, t_n3, Tr):
 
 
 def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_size=1, num_points=150000, frames=None,
-                     lanes=0, sensor=None, sweep=None, fit=None):
+                     lanes=0, sensor=None, sweep=None, fit=None, model=None):
     """Run the network over samples `frames` (default: all scans found) of sequence `seq`; returns (q (n,4), t (n,3))
     = the l0 pose of every sample, in sample order.  Batches are padded by repeating the last sample
     (main.py:497-509 keeps stale rows instead; either way the padding rows are dropped).
@@ -52,7 +54,20 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     `fit` (sensor.PoseFit): every l0 pose is also fitted on its pair's range images (elo_pose_fit) and the returned poses are the
     fit's `pose_out` -- the net's own with iters = 0, the polished ones otherwise (a flagged sample keeps the net's); a third
     value comes back, (n,24) float64 rows [count, rms, status, the 21 entries of the upper triangle of info, row-major].  On both
-    paths.  Without it: the two values of before."""
+    paths.  Without it: the two values of before.
+    `model` (sensor.LocalModel; needs `fit`): the fit of every sample runs against the last `model.scans` scans rendered into one
+    range image (local_model.ModelTracker) instead of against the pair's frame 2.  The net runs per chunk as before; its samples
+    then go through ONE tracker in order, which is reset wherever `frames` does not continue by one.  Sample i is (frame 1, frame
+    2) = (scan i, scan i-1) (kitti.load_pair), so a sample's frame 2 is the frame 1 of the sample before it: what the tracker
+    assumes.  The three return values are those of `fit`.  Sequential path only: the tracker takes the samples one after the other
+    (NotImplementedError with `lanes`).  Without it nothing changes."""
+    if model is not None:
+        if not isinstance(model, LocalModel):
+            raise TypeError("model is a LocalModel or None (got %r)" % (type(model).__name__,))
+        if fit is None:
+            raise ValueError("a local model is what a pose fit runs against: pass fit=PoseFit(...) with model=")
+        if lanes > 0:
+            raise NotImplementedError("the local model takes the samples in order, each after the one before: the lanes run chunks concurrently")
     if sweep is not None and lanes > 0:
         raise NotImplementedError("de-skewing feeds each chunk the previous chunk's pose: the lanes run chunks concurrently")
     if sensor is not None and sensor != net.sensor:
@@ -66,7 +81,7 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     if lanes > 0:
         return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit)
     eye = torch.eye(4, dtype=torch.float32, device=dev).repeat(batch_size, 1, 1)      # main.py:308-309: no augmentation
-    qs, ts, fits = [], [], []
+    qs, ts, fits, tracker = [], [], [], None
     skew = {} if fit is None else {"fit": fit}
     if sweep is not None:
         identity = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], device=dev).repeat(batch_size, 1)
@@ -78,6 +93,28 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
         for j in range(batch_size):
             pos2, pos1, _n2, _n1, T = kitti.load_pair(root, seq, chunk[min(j, len(chunk) - 1)], T_diff, num_points)
             cloud[j, :num_points], cloud[j, num_points:], T_gt[j] = pos2, pos1, T     # main.py:316-320
+        if model is not None:
+            if tracker is None:
+                tracker = ModelTracker(H_input, W_input, model, fit, sensor=net.sensor, beam_elev=net.beam_elev, device=dev)
+            motion = {k: v for k, v in skew.items() if k != "fit"}
+            with torch.no_grad():                            # forward_points(fit=)'s own first half: the range images stay at hand
+                _pts, both = pwclo_model.input_stage(torch.from_numpy(cloud).to(dev), eye, np.ones(batch_size, np.int64), H_input,
+                                                     W_input, sensor=net.sensor, beam_elev=net.beam_elev, **motion)
+            out = net.forward(both[:batch_size], both[batch_size:], False)
+            pose7 = torch.cat([out[0].detach().reshape(-1, 4), out[1].detach().reshape(-1, 3)], -1).contiguous()
+            if sweep is not None:
+                last = len(chunk) - 1
+                skew["motion"] = pose7[last].repeat(batch_size, 1).contiguous()
+            for j in range(len(chunk)):
+                i = start + j
+                if i > 0 and frames[i] != frames[i - 1] + 1:
+                    tracker.reset()
+                res = tracker.step(both[j:j + 1], both[batch_size + j:batch_size + j + 1], pose7[j:j + 1])
+                pose = res.pose.cpu().numpy()
+                qs.append(pose[:, :4].copy())
+                ts.append(pose[:, 4:].copy())
+                fits.append(fit_rows(res, 1))
+            continue
         out = net.forward_points(torch.from_numpy(cloud).to(dev), H_input, W_input, torch.from_numpy(T_gt).to(dev),
                                  eye, eye, is_training=False, aug_frame=np.ones(batch_size, np.int64), **skew)
         if sweep is not None:                                # [q_norm | t] of this chunk's last pair, for every pair of the next

@@ -1,0 +1,113 @@
+"""Frame-to-model pose fit: every scan is fitted against the last few scans, rendered into ONE range image, instead of against the
+last scan alone (sensor.LocalModel; elo_model_render + elo_pose_fit, include/elo.h).
+
+A frame-2 cell gives the pair fit a term only where the cell and its four neighbours hold a point; on sparse scans most do not.
+Several scans carried into one frame fill each other's holes: the model has the normals the single scan lacks.
+
+    tracker = ModelTracker(H, W, LocalModel(scans=4), PoseFit(iters=2))
+    for xyz1, xyz2, pose7 in pairs:            # consecutive pairs of one drive
+        res = tracker.step(xyz1, xyz2, pose7)  # an _ops.PoseFitResult; res.pose: frame 1 -> frame 2, fitted against the model
+
+DIRECTION.  A pair is (frame 1, frame 2) = (scan n, scan n-1) -- kitti.load_pair hands over the current scan first, and the net's
+pose carries frame 1 into frame 2, the running product of evaluate.pose_rows.  So pair n's frame 2 is the scan that was pair
+n-1's frame 1: the tracker keeps its model in the frame of the newest scan it holds, which is the next pair's frame 2.  Where the
+sequence jumps (the next pair's frame 2 is NOT the last frame 1), reset().
+"""
+import torch
+
+from . import _ops
+from . import sensor as _sensor
+
+
+def _qmul(a, b):
+    """Hamilton product of quaternions a (4) and b (n,4) -> (n,4)."""
+    a0, a1, a2, a3 = a.unbind(-1)
+    b0, b1, b2, b3 = b.unbind(-1)
+    return torch.stack([a0 * b0 - a1 * b1 - a2 * b2 - a3 * b3, a0 * b1 + a1 * b0 + a2 * b3 - a3 * b2,
+                        a0 * b2 - a1 * b3 + a2 * b0 + a3 * b1, a0 * b3 + a1 * b2 - a2 * b1 + a3 * b0], -1)
+
+
+def rebase(poses64, T):
+    """The held poses after the model's frame moved by T: every row P_j of poses64 (n,7) [q | t] (scan j -> the OLD model frame)
+    becomes T^-1 o P_j (scan j -> the NEW frame), where T (7) [q | t] carries the new frame into the old one, p_old = R(q) p_new
+    + t -- the pose a fit of (new scan, model) returns.  q_new = conj(q_T) (x) q_j, renormalised; t_new = R(q_T)^T (t_j - t_T).
+    A pure function in float64, on whatever device poses64 lives (array-likes are taken to the CPU): no host synchronisation."""
+    P = torch.as_tensor(poses64)
+    P = P.to(torch.float64).reshape(-1, 7)
+    T = torch.as_tensor(T).to(device=P.device, dtype=torch.float64).reshape(7)
+    q = T[:4] / T[:4].norm()
+    qc = torch.cat([q[:1], -q[1:]])
+    qn = _qmul(qc, P[:, :4] / P[:, :4].norm(dim=1, keepdim=True))
+    qn = qn / qn.norm(dim=1, keepdim=True)
+    # R(conj q) v = v + 2 w (u x v) + 2 u x (u x v), conj q = (w, u)
+    v = P[:, 4:] - T[4:]
+    u = qc[1:].expand_as(v)
+    c = torch.linalg.cross(u, v)
+    tn = v + 2.0 * qc[0] * c + 2.0 * torch.linalg.cross(u, c)
+    return torch.cat([qn, tn], 1)
+
+
+class ModelTracker:
+    """ModelTracker(H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"): the local model of ONE drive.
+    model: sensor.LocalModel; fit: sensor.PoseFit; sensor / beam_elev: the cell rule, as _ops.pose_fit takes them (a sensor with a
+    beam table is uploaded once, here).
+    State, all on the device: `ring` (scans,H,W,3) float32, zeroed -- slot i % scans holds the i-th scan that entered since
+    reset(), an unused slot is all empty cells and gives the render nothing --; `poses64` (scans,7) float64 [q | t], scan of the
+    slot -> the model's frame (the frame of the newest scan held), with the float32 copy `poses32` (1,scans,7) the render reads.
+    step() enqueues launches and device-side float64 torch operators only: the host never waits for the device."""
+
+    def __init__(self, H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"):
+        if not isinstance(model, _sensor.LocalModel):
+            raise TypeError("model is a LocalModel (got %r)" % (type(model).__name__,))
+        if not isinstance(fit, _sensor.PoseFit):
+            raise TypeError("fit is a PoseFit (got %r)" % (type(fit).__name__,))
+        self.H, self.W, self.model, self.fit = int(H), int(W), model, fit
+        if self.H < 3 or self.W < 1:
+            raise ValueError("a pose fit needs H >= 3 and W >= 1 (got %d x %d)" % (self.H, self.W))
+        self.sensor = _sensor.resolve(sensor)
+        self.device = torch.device(device)
+        if beam_elev is None and self.sensor.beam_elevations_deg is not None:
+            beam_elev = self.sensor
+        if beam_elev is not None and not (isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda):
+            beam_elev = _ops.beam_table(beam_elev, self.H, self.device)
+        self.beam_elev = beam_elev
+        K = model.scans
+        self.ring = torch.zeros((K, self.H, self.W, 3), dtype=torch.float32, device=self.device)
+        self._identity = torch.zeros((K, 7), dtype=torch.float64, device=self.device)
+        self._identity[:, 0] = 1.0
+        self.poses64 = self._identity.clone()
+        self.poses32 = torch.empty((1, K, 7), dtype=torch.float32, device=self.device)
+        self.entered = 0                        # scans put in since reset()
+
+    def reset(self):
+        """Forget every scan: the next step() starts a model from its frame 2."""
+        self.ring.zero_()
+        self.poses64.copy_(self._identity)
+        self.entered = 0
+
+    def _enter(self, xyz):
+        """`xyz` (1,H,W,3) defines the model's frame from now on: it enters at the identity, over the oldest scan when all slots are taken."""
+        slot = self.entered % self.model.scans
+        self.ring[slot].copy_(xyz[0])
+        self.poses64[slot].copy_(self._identity[0])
+        self.entered += 1
+
+    def render(self):
+        """The model as it stands -> (xyz (1,H,W,3), src_idx (1,H,W)) of _ops.model_render."""
+        self.poses32.copy_(self.poses64.reshape(1, -1, 7))
+        return _ops.model_render(self.ring.unsqueeze(0), self.poses32, sensor=self.sensor, beam_elev=self.beam_elev)
+
+    def step(self, xyz1, xyz2, pose7):
+        """One pair: xyz1 / xyz2 (1,H,W,3) float32 range images on the tracker's device, pose7 (1,7) [q | t] from frame 1 to frame 2
+        -> the _ops.PoseFitResult of xyz1 against the MODEL at pose7.  Then the model moves into frame 1 by the pose the fit
+        returned (a flagged image's is pose7, by the kernel's own guarantee) and xyz1 enters it."""
+        want = (1, self.H, self.W, 3)
+        if tuple(xyz1.shape) != want or tuple(xyz2.shape) != want:
+            raise ValueError("xyz1 / xyz2 are %s range images (got %s, %s)" % (want, tuple(xyz1.shape), tuple(xyz2.shape)))
+        if self.entered == 0:
+            self._enter(xyz2)
+        model, _src = self.render()
+        res = _ops.pose_fit(xyz1, model, pose7, self.fit, sensor=self.sensor, beam_elev=self.beam_elev)
+        self.poses64.copy_(rebase(self.poses64, res.pose[0]))
+        self._enter(xyz1)
+        return res

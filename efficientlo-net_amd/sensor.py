@@ -12,7 +12,8 @@ is found and which instant the input stage carries the points to, given the sens
 (elo_input_stage_deskew).  It is a value of its own: `Sensor` does not change.
 
 `PoseFit` asks for the geometric fit of a relative pose on the pair's own range images (elo_pose_fit): residual, information
-matrix and, with iters > 0, Gauss-Newton steps on them.
+matrix and, with iters > 0, Gauss-Newton steps on them.  `LocalModel` asks for that fit against the last few scans rendered into
+one range image (elo_model_render; local_model.ModelTracker) instead of against the pair's other scan.
 """
 import math
 
@@ -170,6 +171,36 @@ class PoseFit:
 
     def __repr__(self):
         return "PoseFit(iters=%r, gate=%r, huber=%r, jump_rel=%r, min_count=%r, damping=%r)" % self._key()
+
+
+class LocalModel:
+    """LocalModel(scans=4): fit every scan against the last `scans` scans, rendered into one range image by nearest range
+    (elo_model_render, include/elo.h), instead of against the last scan alone.  Frozen and hashable.
+    scans: how many scans the model holds, an integer in 1 .. 16 (1: the pair fit, through the same path)."""
+    __slots__ = ("scans",)
+
+    def __init__(self, scans=4):
+        if isinstance(scans, bool) or not hasattr(scans, "__index__"):
+            raise ValueError("scans is an integer (got %r)" % (scans,))
+        scans = scans.__index__()
+        if scans < 1 or scans > 16:
+            raise ValueError("scans is 1 .. 16 (got %d)" % scans)
+        object.__setattr__(self, "scans", scans)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("LocalModel is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("LocalModel is immutable")
+
+    def __eq__(self, other):
+        return isinstance(other, LocalModel) and self.scans == other.scans
+
+    def __hash__(self):
+        return hash(("LocalModel", self.scans))
+
+    def __repr__(self):
+        return "LocalModel(scans=%r)" % (self.scans,)
 
 
 def resolve(sensor):

@@ -590,6 +590,47 @@ long elo_pose_fit_scratch_words(int batch, int H, int W);   /* < 0: sizes the en
 int elo_pose_fit_parts(int H, int W);                       /* partial rows (workgroups) per image of an evaluation */
 int elo_pose_fit(const elo_pose_fit_args *a, elo_stream_t stream);
 
+/* LOCAL MODEL for a frame-to-model pose fit (csrc/elo_model.hip): K range images, each carried into ONE frame by its own pose,
+ * rendered into one range image by nearest range -- what elo_pose_fit takes as xyz2 when a scan is fitted against the last K scans
+ * instead of the last one.
+ * src: (batch,K,H,W,3) range images as the input stage writes them; an all-zero cell is empty.  pose: (batch,K,7) [q | t], source
+ * k -> the model's frame, p' = R(q) p + t: the layout and convention of elo_pose_fit_args.pose_in.
+ * ONE POINT: a non-empty source point p is carried in double from the float32 inputs, q normalised in double; each component of p'
+ *   is rounded to float32 ONCE.  A point whose rounded p' has a non-finite component, or is exactly (0,0,0), is dropped (so is
+ *   one whose float32 range below is not positive and finite: components that underflow or overflow in the square).  A source whose
+ *   quaternion has zero or non-finite norm is skipped whole.  No NaN leaves these kernels.
+ *   The cell of p' comes from the ROUNDED point by the float32 sequence of the projections and of elo_pose_fit:
+ *     rf = sqrtf(x*x + y*y + z*z);  m = cell(atan2f(y, x), z, rf) -- cell_of_point at (az_res, vert_res, vert_off), or (beam_elev
+ *     != NULL) the beam-table row of elo_input_stage_beams --, clipped to the image by the rule.  A point the input stage stored in
+ *     cell m therefore lands in cell m again under the identity pose 1 0 0 0 0 0 0, with the bits it had (but for a component
+ *     that is -0.0 beside non-zero ones: the sum returns it as +0.0).
+ * ONE CELL: the winner is the point with the smallest rf (its float32 bits order it: rf is positive); among equal rf the smallest
+ *   source index (k*H + h)*W + w wins.  out_xyz = the winner's rounded p', out_src = its index; a cell nobody reached is zeros and
+ *   -1.  EVERY cell of both outputs is written: the caller need not clear them.
+ * DETERMINISM: one 64-bit integer atomicMin of (rf bits << 32 | index) per surviving point, no floating-point atomic; the point is
+ *   recomputed from the winning index by the same instructions.  Two calls, and an eager call and a graph replay, agree bit for
+ *   bit.  The grid is a fixed function of (batch, K, H, W).
+ * Three launches (clear the keys, splat, resolve), all enqueued by this one call; no host synchronisation; capturable.
+ * scratch: elo_model_render_scratch_words(batch, H, W) 32-bit device words, 8-byte aligned (ask: the host does not restate it).
+ * ELO_ERR_ARG (nothing is launched): a NULL src / pose / output / scratch, K < 1 or K > ELO_MODEL_MAX_SCANS, H < 1, W < 1, H >
+ * ELO_MAX_BEAMS with a table, K*H*W or batch*H*W at or beyond 2^31, out_xyz overlapping src, bad projection constants.
+ * LIFETIME: the launches read pose, src and beam_elev when they RUN: a captured graph renders at every replay what the buffers
+ * hold then; every buffer named here stays alive for as long as a graph recorded with it may be replayed.
+ * Additive to ABI 26: no existing struct changes. */
+#define ELO_MODEL_MAX_SCANS 16
+typedef struct elo_model_render_args {
+    int batch, K, H, W;
+    float az_res, vert_res, vert_off;   /* as elo_pose_fit_args */
+    const float *src;             /* (batch,K,H,W,3) range images; an all-zero cell is empty */
+    const float *pose;            /* (batch,K,7) [q | t]: source k -> the model's frame, p' = R(q) p + t */
+    const float *beam_elev;       /* NULL: the uniform row formula; else (H) radians as in elo_pose_fit */
+    float *out_xyz;               /* (batch,H,W,3) OUT */
+    int *out_src;                 /* (batch,H,W) OUT: (k*H + h)*W + w of the winner, -1 for an empty cell */
+    unsigned *scratch;            /* elo_model_render_scratch_words(batch,H,W) 32-bit words */
+} elo_model_render_args;
+long elo_model_render_scratch_words(int batch, int H, int W);   /* < 0: refused sizes */
+int elo_model_render(const elo_model_render_args *a, elo_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * Backward passes of the feature kernels above, for TRAINING (csrc/elo_backward.hip).
  * The reference trains through TensorFlow's autodiff of its stock ops (main.py:171-176): gather_nd -> scatter-add of
