@@ -96,6 +96,9 @@ ModelRenderArgs = _struct("elo_model_render_args", [
     ("batch", _i), ("K", _i), ("H", _i), ("W", _i), ("az_res", _f), ("vert_res", _f), ("vert_off", _f), ("src", _vp), ("pose", _vp),
     ("beam_elev", _vp), ("out_xyz", _vp), ("out_src", _vp), ("scratch", _vp)])
 MODEL_MAX_SCANS = 16   # ELO_MODEL_MAX_SCANS
+ModelBeginArgs = _struct("elo_model_begin_args", [("K", _i), ("H", _i), ("W", _i), ("ring", _vp), ("state", _vp), ("first", _vp)])
+ModelAdvanceArgs = _struct("elo_model_advance_args", [
+    ("K", _i), ("H", _i), ("W", _i), ("ring", _vp), ("poses64", _vp), ("poses32", _vp), ("state", _vp), ("scan", _vp), ("T", _vp)])
 
 # backward passes (csrc/elo_backward.hip)
 GroupConcatBwdArgs = _struct("elo_group_concat_bwd_args", [
@@ -218,6 +221,8 @@ SYMBOLS = [
     ("elo_pose_fit_parts", ctypes.c_int, [ctypes.c_int] * 2),
     ("elo_model_render", ctypes.c_int, [ctypes.POINTER(ModelRenderArgs), _vp]),
     ("elo_model_render_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
+    ("elo_model_begin", ctypes.c_int, [ctypes.POINTER(ModelBeginArgs), _vp]),
+    ("elo_model_advance", ctypes.c_int, [ctypes.POINTER(ModelAdvanceArgs), _vp]),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),
     ("elo_masked_maxpool_backward", ctypes.c_int, [ctypes.POINTER(MaskedMaxpoolBwdArgs), _vp]),
     ("elo_cv_encode1_backward", ctypes.c_int, [ctypes.POINTER(CvEncode1BwdArgs), _vp]),

@@ -835,6 +835,65 @@ def model_render(src, pose, sensor=None, beam_elev=None):
     return xyz, idx
 
 
+def _check_model_state(ring, state, image, name, poses64=None, poses32=None, T=None):
+    """What the host can refuse about a tracker-state launch without a GPU or the library: types, dtypes, layout, shapes, devices."""
+    given = [("ring", ring, torch.float32), ("state", state, torch.int32), (name, image, torch.float32)]
+    if poses64 is not None or poses32 is not None or T is not None:
+        given += [("poses64", poses64, torch.float64), ("poses32", poses32, torch.float32), ("T", T, torch.float32)]
+    for what, t, dtype in given:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s is a tensor (got %r)" % (what, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError("%s is %s (got %s)" % (what, str(dtype).replace("torch.", ""), t.dtype))
+        if not t.is_contiguous():
+            raise L.EloError("%s must be contiguous: the launch uses it in place" % what)
+    if ring.dim() != 4 or ring.shape[-1] != 3:
+        raise L.EloError("ring is (K,H,W,3): the K scans a model holds (got %s)" % (tuple(ring.shape),))
+    K, H, W, _ = ring.shape
+    if K < 1 or K > L.MODEL_MAX_SCANS:
+        raise L.EloError("a model holds 1 .. %d scans (K = %d)" % (L.MODEL_MAX_SCANS, K))
+    if H < 3 or W < 1:
+        raise L.EloError("a pose fit needs H >= 3 and W >= 1 (got %d x %d)" % (H, W))
+    if K * H * W >= 2 ** 31:
+        raise L.EloError("K*H*W stays below 2^31 (got K, H, W = %d, %d, %d)" % (K, H, W))
+    if tuple(state.shape) != (2,):
+        raise L.EloError("state is the two int32 words {next, held} (got %s)" % (tuple(state.shape),))
+    if tuple(image.shape) != (H, W, 3):
+        raise L.EloError("%s is one (%d,%d,3) range image, as the ring's slots are (got %s)" % (name, H, W, tuple(image.shape)))
+    if len(given) > 3:
+        if tuple(poses64.shape) != (K, 7) or tuple(poses32.shape) != (K, 7):
+            raise L.EloError("poses64 / poses32 are one [q | t] row per slot: (%d, 7) (got %s, %s)"
+                             % (K, tuple(poses64.shape), tuple(poses32.shape)))
+        if tuple(T.shape) not in ((7,), (1, 7)):
+            raise L.EloError("T is one [q0 q1 q2 q3 | t0 t1 t2] row (got %s)" % (tuple(T.shape),))
+    if any(t.device != ring.device for _w, t, _d in given):
+        raise L.EloError("the tracker's state and its images live on one device")
+
+
+def model_begin(ring, state, first):
+    """elo_model_begin: where the tracker state `state` (int32[2] = {next, held}) says the model is empty, the image `first` (H,W,3)
+    -- the pair's frame 2 -- enters slot 0 of `ring` (K,H,W,3); otherwise nothing is written.  One launch that takes its decision
+    from device memory when it RUNS: no host synchronisation, capturable.  Bad types, shapes or layouts are refused here, before
+    anything is launched."""
+    _check_model_state(ring, state, first, "first")
+    L.require_gpu(ring, state, first)
+    K, H, W, _ = ring.shape
+    L.call("elo_model_begin", L.ModelBeginArgs(K, H, W, ring.data_ptr(), state.data_ptr(), first.data_ptr()), ring)
+
+
+def model_advance(ring, poses64, poses32, state, scan, T):
+    """elo_model_advance: the image `scan` (H,W,3) enters the slot of `ring` (K,H,W,3) the state names; every row of `poses64` (K,7)
+    double is re-based by T^-1 (`T`: (7) or (1,7) float32 [q | t], the fit's pose of `scan` against the model), the entered row becomes
+    the identity, `poses32` (K,7) becomes poses64 rounded to float32 and `state` moves on.  Two launches that take their decisions
+    from device memory when they RUN: no host synchronisation, capturable.  Refusals as model_begin."""
+    _check_model_state(ring, state, scan, "scan", poses64, poses32, T)
+    L.require_gpu(ring, state, scan, poses64, poses32, T)
+    K, H, W, _ = ring.shape
+    a = L.ModelAdvanceArgs(K, H, W, ring.data_ptr(), poses64.data_ptr(), poses32.data_ptr(), state.data_ptr(), scan.data_ptr(),
+                           T.data_ptr())
+    L.call("elo_model_advance", a, ring)
+
+
 class _WarpProject(torch.autograd.Function):
     """elo_warp_project / elo_warp_project_backward.  The forward's scratch (who won each cell) is kept for the backward."""
 

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import kitti, pwclo_model
-from .local_model import ModelTracker
+from .local_model import DeviceTracker, ModelTracker
 from .distributed import quat2mat
 from .sensor import LocalModel
 
@@ -59,15 +59,20 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     range image (local_model.ModelTracker) instead of against the pair's frame 2.  The net runs per chunk as before; its samples
     then go through ONE tracker in order, which is reset wherever `frames` does not continue by one.  Sample i is (frame 1, frame
     2) = (scan i, scan i-1) (kitti.load_pair), so a sample's frame 2 is the frame 1 of the sample before it: what the tracker
-    assumes.  The three return values are those of `fit`.  Sequential path only: the tracker takes the samples one after the other
-    (NotImplementedError with `lanes`).  Without it nothing changes."""
+    assumes.  The three return values are those of `fit`.  The host-driven tracker is for the sequential path only: it takes the
+    samples one after the other (NotImplementedError with `lanes`).  `model.resident`: the tracker's state machine lives on the
+    device (local_model.DeviceTracker) and a sample is one replay of its recorded step -- on the sequential path, and with `lanes`:
+    the lanes are then captured WITHOUT a fit, chunks are collected in order as before, and every sample of a collected chunk steps
+    the one tracker on the range images of the lane's clouds and the lane's pose row; its result is on the host before the lane is
+    submitted again.  Without `model` nothing changes."""
     if model is not None:
         if not isinstance(model, LocalModel):
             raise TypeError("model is a LocalModel or None (got %r)" % (type(model).__name__,))
         if fit is None:
             raise ValueError("a local model is what a pose fit runs against: pass fit=PoseFit(...) with model=")
-        if lanes > 0:
-            raise NotImplementedError("the local model takes the samples in order, each after the one before: the lanes run chunks concurrently")
+        if lanes > 0 and not model.resident:
+            raise NotImplementedError("the host-driven local model takes the samples in order, each after the one before: the lanes run "
+                                      "chunks concurrently -- LocalModel(resident=True) steps a device tracker behind them")
     if sweep is not None and lanes > 0:
         raise NotImplementedError("de-skewing feeds each chunk the previous chunk's pose: the lanes run chunks concurrently")
     if sensor is not None and sensor != net.sensor:
@@ -79,7 +84,7 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     frames = list(frames)
     dev = net.device
     if lanes > 0:
-        return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit)
+        return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit, model)
     eye = torch.eye(4, dtype=torch.float32, device=dev).repeat(batch_size, 1, 1)      # main.py:308-309: no augmentation
     qs, ts, fits, tracker = [], [], [], None
     skew = {} if fit is None else {"fit": fit}
@@ -95,7 +100,7 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
             cloud[j, :num_points], cloud[j, num_points:], T_gt[j] = pos2, pos1, T     # main.py:316-320
         if model is not None:
             if tracker is None:
-                tracker = ModelTracker(H_input, W_input, model, fit, sensor=net.sensor, beam_elev=net.beam_elev, device=dev)
+                tracker = _tracker(net, H_input, W_input, model, fit)
             motion = {k: v for k, v in skew.items() if k != "fit"}
             with torch.no_grad():                            # forward_points(fit=)'s own first half: the range images stay at hand
                 _pts, both = pwclo_model.input_stage(torch.from_numpy(cloud).to(dev), eye, np.ones(batch_size, np.int64), H_input,
@@ -143,9 +148,18 @@ def fit_rows(result, n):
     return np.concatenate([stats[:, [0, 2, 3]], info[:, _TRIU[0], _TRIU[1]]], 1)
 
 
-def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit=None):
+def _tracker(net, H_input, W_input, model, fit):
+    """The tracker `model` asks for: the host-driven one, or the device's with its step recorded."""
+    kw = dict(sensor=net.sensor, beam_elev=net.beam_elev, device=net.device)
+    if model.resident:
+        return DeviceTracker(H_input, W_input, model, fit, **kw).capture()
+    return ModelTracker(H_input, W_input, model, fit, **kw)
+
+
+def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit=None, model=None):
     dev = net.device
-    net.capture(batch_size, H_input, W_input, lanes=lanes, num_points=num_points, fit=fit)
+    net.capture(batch_size, H_input, W_input, lanes=lanes, num_points=num_points, fit=fit if model is None else None)
+    tracker = None if model is None else _tracker(net, H_input, W_input, model, fit)      # (recorded while no lane is in flight)
     chunks = [frames[s:s + batch_size] for s in range(0, len(frames), batch_size)]
     qs, ts, fits = [None] * len(chunks), [None] * len(chunks), [None] * len(chunks)
     pinned = [torch.empty((batch_size, 2 * num_points, 3), dtype=torch.float32).pin_memory() for _ in range(lanes)]
@@ -153,7 +167,24 @@ def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size
     def collect(ci):                                         # the lane's stream has finished chunk ci
         lane = ci % lanes
         net.lane_stream(lane).synchronize()
-        if fit is not None:
+        if tracker is not None:
+            # the range images of the lane's clouds: a lane that starts from raw clouds keeps them inside its graph (lane_input() is
+            # the buffer of a lane fed with range images), so the input stage runs once more on the cloud buffer -- the same launches on
+            # the same bytes.  Every result is on the host (.cpu()) before the next step overwrites it and before the lane's buffers
+            # are written again.
+            with torch.no_grad():
+                _pts, both = pwclo_model.input_stage(net.lane_cloud(lane), None, None, H_input, W_input, sensor=net.sensor,
+                                                     beam_elev=net.beam_elev)
+            pose7, rows, poses = net.lane_pose(lane), [], []
+            for j in range(len(chunks[ci])):
+                i = ci * batch_size + j
+                if i > 0 and frames[i] != frames[i - 1] + 1:
+                    tracker.reset()
+                res = tracker.step(both[j:j + 1], both[batch_size + j:batch_size + j + 1], pose7[j:j + 1])
+                poses.append(res.pose.cpu().numpy())
+                rows.append(fit_rows(res, 1))
+            pose, fits[ci] = np.concatenate(poses), np.concatenate(rows)
+        elif fit is not None:
             res = net.lane_fit(lane, fit)
             pose, fits[ci] = res.pose[:len(chunks[ci])].cpu().numpy(), fit_rows(res, len(chunks[ci]))
         else:

@@ -522,6 +522,13 @@ class PWCLONet:
                 lane.motion.copy_(motion.reshape(lane.motion.shape), non_blocking=True)
             return self._replay_lane(lane)
 
+    def lane_cloud(self, lane_index):
+        """The (B, 2N, stride) cloud buffer of a lane captured with `num_points`: what submit_points() copied in, and what the lane's
+        recorded input stage read at its last replay -- valid to read once the lane's stream has been synchronised or waited on."""
+        if self._lanes[lane_index].cloud is None:
+            raise RuntimeError("this lane was captured from range images: it has no cloud buffer (lane_input() is its input)")
+        return self._lanes[lane_index].cloud
+
     def lane_motion(self, lane_index):
         """The (B,7) motion buffer of a lane captured with `sweep`: rows [q | t], read by the lane's input stage when its graph
         RUNS.  A producer on the device (the pose head of the previous pair, a filter) writes here -- on the lane's stream, or

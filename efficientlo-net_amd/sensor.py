@@ -174,18 +174,23 @@ class PoseFit:
 
 
 class LocalModel:
-    """LocalModel(scans=4): fit every scan against the last `scans` scans, rendered into one range image by nearest range
-    (elo_model_render, include/elo.h), instead of against the last scan alone.  Frozen and hashable.
-    scans: how many scans the model holds, an integer in 1 .. 16 (1: the pair fit, through the same path)."""
-    __slots__ = ("scans",)
+    """LocalModel(scans=4, resident=False): fit every scan against the last `scans` scans, rendered into one range image by nearest
+    range (elo_model_render, include/elo.h), instead of against the last scan alone.  Frozen and hashable.
+    scans: how many scans the model holds, an integer in 1 .. 16 (1: the pair fit, through the same path).
+    resident: the tracker's state machine lives on the device (local_model.DeviceTracker: elo_model_begin / elo_model_advance) and a
+    step is one hipGraph replay; False: local_model.ModelTracker, whose cursor is the host's."""
+    __slots__ = ("scans", "resident")
 
-    def __init__(self, scans=4):
+    def __init__(self, scans=4, resident=False):
         if isinstance(scans, bool) or not hasattr(scans, "__index__"):
             raise ValueError("scans is an integer (got %r)" % (scans,))
         scans = scans.__index__()
         if scans < 1 or scans > 16:
             raise ValueError("scans is 1 .. 16 (got %d)" % scans)
+        if not isinstance(resident, bool):
+            raise ValueError("resident is True or False (got %r)" % (resident,))
         object.__setattr__(self, "scans", scans)
+        object.__setattr__(self, "resident", resident)
 
     def __setattr__(self, name, value):
         raise AttributeError("LocalModel is immutable")
@@ -194,12 +199,14 @@ class LocalModel:
         raise AttributeError("LocalModel is immutable")
 
     def __eq__(self, other):
-        return isinstance(other, LocalModel) and self.scans == other.scans
+        return isinstance(other, LocalModel) and (self.scans, self.resident) == (other.scans, other.resident)
 
     def __hash__(self):
-        return hash(("LocalModel", self.scans))
+        return hash(("LocalModel", self.scans, self.resident))
 
     def __repr__(self):
+        if self.resident:
+            return "LocalModel(scans=%r, resident=True)" % (self.scans,)
         return "LocalModel(scans=%r)" % (self.scans,)
 
 

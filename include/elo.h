@@ -631,6 +631,58 @@ typedef struct elo_model_render_args {
 long elo_model_render_scratch_words(int batch, int H, int W);   /* < 0: refused sizes */
 int elo_model_render(const elo_model_render_args *a, elo_stream_t stream);
 
+/* TRACKER STATE on the device (csrc/elo_model_state.hip): the state machine of a frame-to-model tracker -- which slot of the ring
+ * a scan enters, whether the first frame 2 enters, the re-basing of the held poses -- as launches that read their decisions from
+ * device memory, so that one tracker step (begin, elo_model_render, elo_pose_fit, advance) is a FIXED launch sequence: a hipGraph
+ * records it once and replays it per scan.
+ * STATE of one tracker, four device buffers the caller owns:
+ *   ring    (K,H,W,3) float32: the held scans; an unused slot is all empty cells (zeros) and gives the render nothing;
+ *   poses64 (K,7) double [q | t]: scan of the slot -> the model's frame (the frame of the newest scan held);
+ *   poses32 (K,7) float32: every component of poses64 rounded to float32 once -- what elo_model_render takes as `pose`;
+ *   state   int32[2] = {next in 0 .. K-1: the slot the next scan enters;  held in 0 .. K: how many scans the ring holds}.
+ *   RESET (the caller's, by device-side fills): ring zero, every pose row 1 0 0 0 0 0 0 in both copies, state {0, 0}.
+ * elo_model_begin, ONE launch: where held == 0 the image `first` (H,W,3) -- the pair's frame 2, which starts an empty model at the
+ *   identity -- is copied into slot 0; otherwise nothing is written.  It reads `state` and never writes it.
+ * elo_model_advance, TWO launches, in this order; (next', held') = held == 0 ? (1 % K, 1) : (next, held) -- an empty model has just
+ *   taken its frame 2 in slot 0 --:
+ *   1. enter: the image `scan` (H,W,3) is copied into slot next'.  It only reads `state`.
+ *   2. update, one workgroup: every row P_j <- T^-1 o P_j, where T (7) float32 [q | t] carries the NEW model frame (that of `scan`)
+ *      into the old one, p_old = R(q) p_new + t -- the pose_out row of the fit of `scan` against the model --:
+ *        q_new = conj(q_T) (x) q_j, renormalised;  t_new = R(q_T)^T (t_j - t_T);  q_T normalised where it is used; all in double
+ *        from the float32 T and the double rows;
+ *      then row next' <- the identity 1 0 0 0 0 0 0, exactly; poses32 <- every component of poses64 rounded to float32 once;
+ *      state <- {(next' + 1) % K, min(held' + 1, K)}.  Only this launch writes `state`, and it is ordered after every launch that
+ *      reads it.
+ *   A non-finite T is not special-cased: the re-based rows become non-finite, elo_model_render skips such sources, and a reset
+ *   recovers.  A `state` outside its domain (memory nobody reset) makes all three launches write nothing.
+ * COPIES: 16-byte accesses where H * W is a multiple of 4 and ring and the image are 16-byte aligned; one float at a time
+ *   otherwise.  Empty cells stay the zeros they are.  No atomic anywhere; two runs, and an eager run and a graph replay, agree bit
+ *   for bit.  The grids are fixed functions of (H, W).
+ * No host synchronisation; capturable.  The launches read `state`, `T` and the images when they RUN: a captured graph acts at every
+ *   replay on what the buffers hold then; every buffer named here stays alive for as long as a graph recorded with it may be
+ *   replayed.
+ * ELO_ERR_ARG (nothing is launched): a NULL pointer, K < 1 or K > ELO_MODEL_MAX_SCANS, H < 3, W < 1, H * W or K * H * W at or
+ *   beyond 2^31 (the bounds of elo_pose_fit on an image and of elo_model_render on the ring), `first` / `scan` overlapping `ring`,
+ *   poses64 not 8-byte aligned.
+ * Additive to ABI 26: no existing struct changes. */
+typedef struct elo_model_begin_args {
+    int K, H, W;
+    float *ring;                  /* (K,H,W,3) IN/OUT: slot 0 <- first where the model is empty */
+    const int *state;             /* int32[2] {next, held}: read only */
+    const float *first;           /* (H,W,3): the pair's frame 2; must not overlap ring */
+} elo_model_begin_args;
+int elo_model_begin(const elo_model_begin_args *a, elo_stream_t stream);
+typedef struct elo_model_advance_args {
+    int K, H, W;
+    float *ring;                  /* (K,H,W,3) IN/OUT: slot next' <- scan */
+    double *poses64;              /* (K,7) IN/OUT */
+    float *poses32;               /* (K,7) OUT */
+    int *state;                   /* int32[2] {next, held} IN/OUT */
+    const float *scan;            /* (H,W,3): the scan that enters (the pair's frame 1); must not overlap ring */
+    const float *T;               /* (7) [q | t]: elo_pose_fit's pose_out row of scan against the model */
+} elo_model_advance_args;
+int elo_model_advance(const elo_model_advance_args *a, elo_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * Backward passes of the feature kernels above, for TRAINING (csrc/elo_backward.hip).
  * The reference trains through TensorFlow's autodiff of its stock ops (main.py:171-176): gather_nd -> scatter-add of
