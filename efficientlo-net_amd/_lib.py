@@ -51,6 +51,18 @@ ELO_F32, ELO_F16 = 0, 1
 ENCODE1_FORMS = ("scalar", "vec32", "vec64", "vec128", "col64", "col128", "staged128", "staged64")
 ENCODE2_FORMS = ("scalar", "vec32", "vec64", "vec128")
 POOL_FORMS = ("scalar", "vec6", "vec4", "wave1", "wave2", "wave4", "wave8")
+# ... and the fused entry points' queries: ELO_FUSED_FORM(family, rows, products) of the ELO_FUSED_* enumerators, by value
+FUSED_FAMILIES = ("tile", "chain", "narrow_mfma", "narrow_valu", "sv_ride")
+FUSED_PRODUCTS = ("split", "half", "checked")
+FUSED_QUERIES = ("elo_setconv_fused_form", "elo_mlp_fused_form", "elo_cv_stage1_form", "elo_cv_stage2_form")
+
+
+def fused_form_name(value):
+    """ELO_FUSED_FORM as '<family><rows>/<products>' (rows only where the family has a tile): 'tile16/split', 'chain/half'."""
+    family, rows, products = value & 15, value >> 4 & 255, value >> 12 & 15
+    return "%s%s/%s" % (FUSED_FAMILIES[family], rows or "", FUSED_PRODUCTS[products])
+
+
 SoftmaxValidArgs = _struct("elo_softmax_valid_args", [
     ("batch", _i), ("npoints", _i), ("C", _i), ("feature", _vp), ("weight", _vp), ("xyz", _vp), ("out", _vp),
     ("scratch", _vp), ("stats", _vp)])
@@ -264,6 +276,10 @@ SYMBOLS = [
     ("elo_cv_stage2_upconv_form", ctypes.c_int, [ctypes.POINTER(Cv2Args), ctypes.POINTER(MlpArgs), ctypes.POINTER(MlpArgs)]),
     ("elo_cv_stage2_upconv_fused", ctypes.c_int, [ctypes.POINTER(Cv2Args), ctypes.POINTER(MlpArgs), ctypes.POINTER(MlpArgs), _vp]),
     ("elo_cv_stage1_setconv_fused", ctypes.c_int, [ctypes.POINTER(Cv1Args), ctypes.POINTER(SetconvArgs), ctypes.POINTER(SetconvArgs), _vp]),
+    ("elo_setconv_fused_form", ctypes.c_int, [ctypes.POINTER(SetconvArgs), ctypes.POINTER(SetconvArgs)]),
+    ("elo_mlp_fused_form", ctypes.c_int, [ctypes.POINTER(MlpArgs), ctypes.POINTER(MlpArgs)]),
+    ("elo_cv_stage1_form", ctypes.c_int, [ctypes.POINTER(Cv1Args)]),
+    ("elo_cv_stage2_form", ctypes.c_int, [ctypes.POINTER(Cv2Args)]),
 ]
 
 _lib = None
@@ -335,6 +351,19 @@ def form(query, args):
     if rc < 0:
         check(rc)
     return names[rc]
+
+
+def fused_form(query, a, b=None):
+    """What `query` (one of FUSED_QUERIES) answers for the argument block(s), as fused_form_name spells it; raises where the
+    entry point would refuse them.  `b`: the second job of a paired set-conv / MLP launch.  Host only: nothing is launched."""
+    fn = getattr(lib(), query)
+    if query in ("elo_setconv_fused_form", "elo_mlp_fused_form"):
+        rc = fn(ctypes.byref(a), ctypes.byref(b) if b is not None else None)
+    else:
+        rc = fn(ctypes.byref(a))
+    if rc < 0:
+        check(rc)
+    return fused_form_name(rc)
 
 
 def check(rc):

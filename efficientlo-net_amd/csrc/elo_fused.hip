@@ -741,7 +741,6 @@ __device__ __forceinline__ void group_tile(const TileMeta &m, int *lds_off, unsi
     __syncthreads();
 }
 
-
 // ---- staging a tile's rows: vector loads, ALL requested before the first LDS write --------------------------
 // A segment = W consecutive elements of one global feature row per tile row (fp32: W % 4 == 0, fp16: W % 8 == 0,
 // rows 16-byte aligned), written to the tile's columns [col0, col0 + W) in operand format where the row's mask says so,
@@ -1047,7 +1046,6 @@ __global__ __launch_bounds__(FUSED_BLOCK, TILE == 32 ? ELO_TILE32_WAVES : ELO_TI
     extern __shared__ __align__(16) float lds[];
     setconv_tile<TILE, MODE>(jobs.job[blockIdx.y], S, lds, blockIdx.x, gridDim.x);
 }
-
 
 // ================================================================ set-conv with a narrow MLP (widths <= 32, K == 32)
 // The first two set-conv layers (6->8->8->16 and 19->16->16->32 on 7200 / 1808 centres) are far too small for
@@ -2946,6 +2944,18 @@ static int check_setconv(const elo_setconv_args *a, const char *who)
 
 // how a tile kernel is launched: LDS row stride, tile height, workgroups (per job), LDS bytes, products mode
 struct TilePlan { int S; bool t16; long units; size_t lds; int mode; };
+// ... against the 64 KiB of dynamic LDS a workgroup may ask for (include/elo.h "The LDS limit"): refused on the host, before any HIP call
+static int check_tile_lds(size_t lds, bool t16, int S, const char *who)
+{
+    if (lds <= 64 * 1024) return ELO_OK;
+    return fail(ELO_ERR_LIMIT, "%s: a tile of %d rows x %d words needs %zu bytes of LDS (limit 65536): input or layer too wide", who, t16 ? 16 : 32, S, lds);
+}
+// What the elo_*_form queries answer (include/elo.h ELO_FUSED_FORM).  Each launcher below is ONE function with a flag `ask`: it takes
+// every decision of a launch and, where it would launch, answers the form instead -- the ladder is written once.
+static_assert(ELO_FUSED_SPLIT == MODE_SPLIT && ELO_FUSED_HALF == MODE_HALF && ELO_FUSED_CHECKED == MODE_CHECKED, "ELO_FUSED_* products = MODE_*");
+static int tile_form(bool t16, int mode) { return ELO_FUSED_FORM(ELO_FUSED_TILE, t16 ? 16 : 32, mode); }
+static const int FORM_NOTHING = ELO_FUSED_FORM(ELO_FUSED_TILE, 32, ELO_FUSED_SPLIT);     // no points / rows: nothing is launched
+static int setconv_launch(const elo_setconv_args *a, const elo_setconv_args *b, elo_stream_t stream, const bool ask, const char *who);
 
 // tile height and workgroups per job for `points` centres of K rows each, `jobs` same-shape jobs sharing the grid
 static void plan_tiles(TilePlan *p, long points, int K, int jobs = 1)
@@ -2976,7 +2986,8 @@ static int plan_setconv(const elo_setconv_args *a, const elo_setconv_args *b, Ti
     plan_tiles(p, (long)a->batch * a->npoints, a->K, b ? 2 : 1);
     const int KT = a->group.random_hw ? a->group.kernel_h * a->group.kernel_w : 0;
     p->lds = tile_lds_bytes(p->t16 ? 16 : 32, p->S, KT, false);
-    return check_group(a->group, a->H2, a->W2, p->lds, who);
+    if (int rc = check_group(a->group, a->H2, a->W2, p->lds, who)) return rc;
+    return check_tile_lds(p->lds, p->t16, p->S, who);                     // (pre-grouped calls: check_group has nothing to say)
 }
 
 extern "C" int elo_dense_f32(void)
@@ -3130,6 +3141,11 @@ static bool cv_chain(int C, int mode)
 extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_args *b, elo_stream_t stream)
 {
     const char *who = "elo_setconv_fused";
+    return setconv_launch(a, b, stream, false, who);
+}
+extern "C" int elo_setconv_fused_form(const elo_setconv_args *a, const elo_setconv_args *b) { return setconv_launch(a, b, nullptr, true, "elo_setconv_fused_form"); }
+static int setconv_launch(const elo_setconv_args *a, const elo_setconv_args *b, elo_stream_t stream, const bool ask, const char *who)
+{
     if (int rc = check_setconv(a, who)) return rc;
     if (b) {
         if (int rc = check_setconv(b, who)) return rc;
@@ -3137,7 +3153,7 @@ extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_a
     }
     if (int rc = check_points(a->batch, a->npoints, who)) return rc;
     const long points = (long)a->batch * a->npoints;
-    if (points == 0) return ELO_OK;
+    if (points == 0) return ask ? FORM_NOTHING : ELO_OK;
     hipStream_t s = (hipStream_t)stream;
     if (narrow_chain(a, b) && a->group.random_hw && a->layers[2].relu &&
         a->group.kernel_h * a->group.kernel_w <= SMALL_STEPS * 32) {   // narrow chains: wave-per-point VALU kernel
@@ -3150,6 +3166,7 @@ extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_a
             // (the 6 -> 8 -> 8 -> 16 layer stays on the VALU kernel: on the matrix cores it measured 64 us against 36.5 us at batch 8 --
             //  240 FMAs per row, the kernel is the latency chain of its grouping times its occupancy: profiles/r04_ab_narrow.txt)
             if (cin == 19 && n1 == 16 && n2 == 16 && n3 == 32) {
+                if (ask) return ELO_FUSED_FORM(ELO_FUSED_NARROW_MFMA, 0, checked ? ELO_FUSED_CHECKED : ELO_FUSED_SPLIT);
                 if (checked) hipLaunchKernelGGL((setconv_narrow_kernel<19, 16, 16, 32, MODE_CHECKED>), dim3(grid), dim3(ELO_BLOCK), 0, s, *a);
                 else hipLaunchKernelGGL((setconv_narrow_kernel<19, 16, 16, 32, MODE_SPLIT>), dim3(grid), dim3(ELO_BLOCK), 0, s, *a);
                 ++g_narrow_launches[0];
@@ -3157,13 +3174,11 @@ extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_a
             }
         }
 #endif
-        if (cin == 6 && n1 == 8 && n2 == 8 && n3 == 16) {
-            hipLaunchKernelGGL((setconv_small_kernel<6, 8, 8, 16>), dim3(grid), dim3(ELO_BLOCK), 0, s, *a);
-            ++g_narrow_launches[1];
-            return check_launch(who);
-        }
-        if (cin == 19 && n1 == 16 && n2 == 16 && n3 == 32) {
-            hipLaunchKernelGGL((setconv_small_kernel<19, 16, 16, 32>), dim3(grid), dim3(ELO_BLOCK), 0, s, *a);
+        const bool small6 = cin == 6 && n1 == 8 && n2 == 8 && n3 == 16, small19 = cin == 19 && n1 == 16 && n2 == 16 && n3 == 32;
+        if (ask && (small6 || small19)) return ELO_FUSED_FORM(ELO_FUSED_NARROW_VALU, 0, ELO_FUSED_SPLIT);   // (fp32 arithmetic whatever the layers say)
+        if (small6) hipLaunchKernelGGL((setconv_small_kernel<6, 8, 8, 16>), dim3(grid), dim3(ELO_BLOCK), 0, s, *a);
+        else if (small19) hipLaunchKernelGGL((setconv_small_kernel<19, 16, 16, 32>), dim3(grid), dim3(ELO_BLOCK), 0, s, *a);
+        if (small6 || small19) {
             ++g_narrow_launches[1];
             return check_launch(who);
         }
@@ -3175,6 +3190,7 @@ extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_a
     pair.job[1] = b ? *b : *a;
 #ifndef ELO_DENSE_F32
     if (const int shape = setconv_chain_shape(a, b, plan.mode)) {   // the register-resident form (setconv_rr_kernel)
+        if (ask) return ELO_FUSED_FORM(ELO_FUSED_CHAIN, 0, plan.mode);
         const int P = RR_ROWS / a->K;
         const dim3 rgrid((unsigned)((points + P - 1) / P), b ? 2u : 1u);
         const bool f16 = a->feat_dtype == ELO_F16;
@@ -3190,16 +3206,13 @@ extern "C" int elo_setconv_fused2(const elo_setconv_args *a, const elo_setconv_a
     const dim3 grid((unsigned)plan.units, b ? 2u : 1u);
     const size_t lds = plan.lds;
     const int S = plan.S;
+    if (ask) return tile_form(plan.t16, plan.mode);
 #define CALL(k) hipLaunchKernelGGL(k, grid, dim3(FUSED_BLOCK), lds, s, pair, S)
     ELO_PICK(setconv_kernel, plan.t16, plan.mode, CALL);
 #undef CALL
     return check_launch(who);
 }
-
-extern "C" int elo_setconv_fused(const elo_setconv_args *a, elo_stream_t stream)
-{
-    return elo_setconv_fused2(a, nullptr, stream);
-}
+extern "C" int elo_setconv_fused(const elo_setconv_args *a, elo_stream_t stream) { return elo_setconv_fused2(a, nullptr, stream); }
 
 static int check_mlp(const elo_mlp_args *a, const char *who, int *in_width)
 {
@@ -3261,7 +3274,7 @@ static bool mlp_chain_regime(long rows, bool pair, int batch_hint, int mode)
 
 // everything elo_mlp_fused2 decides before it launches
 // sv_tiles: row tiles per batch element of the softmax_valid ride (0: none), sv_lds: mlp_sv_kernel's dynamic LDS bytes for it
-struct MlpPlan { int S, mode, C; bool t16, chain; int sv_tiles; size_t sv_lds; };
+struct MlpPlan { int S, mode, C; bool t16, chain; int sv_tiles; size_t sv_lds, lds; };      // lds: the plain tile launch's dynamic LDS bytes
 
 static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, const char *who)
 {
@@ -3320,7 +3333,9 @@ static int plan_mlp(const elo_mlp_args *a, const elo_mlp_args *b, MlpPlan *p, co
             p->t16 = t16;
         }
     }
-    return ELO_OK;
+    // the plain tile launch (a ride within its own 64 KiB above leaves a plain tile within them too; the chain kernel's LDS is fixed)
+    p->lds = tile_lds_bytes(p->t16 ? 16 : 32, p->S);
+    return p->chain || a->rows == 0 ? ELO_OK : check_tile_lds(p->lds, p->t16, p->S, who);   // (no rows: nothing is launched, as before)
 }
 
 extern "C" int elo_mlp_sv_parts(const elo_mlp_args *a, const elo_mlp_args *b)
@@ -3330,13 +3345,12 @@ extern "C" int elo_mlp_sv_parts(const elo_mlp_args *a, const elo_mlp_args *b)
     return p.sv_tiles;
 }
 
-extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_stream_t stream)
+static int mlp_launch(const elo_mlp_args *a, const elo_mlp_args *b, elo_stream_t stream, const bool ask, const char *who)
 {
-    const char *who = "elo_mlp_fused";
     MlpPlan plan;
     if (int rc = plan_mlp(a, b, &plan, who)) return rc;
     if (a->rows == 0)
-        return a->clear_scratch || a->sv_scratch ? fail(ELO_ERR_ARG, "%s: a clear_* / sv_* side job needs rows to ride on", who) : ELO_OK;
+        return a->clear_scratch || a->sv_scratch ? fail(ELO_ERR_ARG, "%s: a clear_* / sv_* side job needs rows to ride on", who) : ask ? FORM_NOTHING : ELO_OK;
     const int S = plan.S, mode = plan.mode;
     const bool t16 = plan.t16;
     const long u32 = (a->rows + 31) / 32, u16 = (a->rows + 15) / 16;
@@ -3351,6 +3365,7 @@ extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_
         if ((b != nullptr) == (a->sv_feature != nullptr))
             return fail(ELO_ERR_ARG, "%s: a paired launch takes its features from job b (sv_feature NULL), a single launch from sv_feature", who);
         if (!b && ((uintptr_t)a->sv_feature & 15)) return fail(ELO_ERR_ARG, "%s: unaligned sv_feature", who);
+        if (ask) return ELO_FUSED_FORM(ELO_FUSED_SV_RIDE, t16 ? 16 : 32, mode);
         const size_t lds = plan.sv_lds;
         const dim3 grid((unsigned)(a->rows / a->sv_npoints) * (unsigned)plan.sv_tiles);
         hipStream_t s = (hipStream_t)stream;
@@ -3366,9 +3381,10 @@ extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_
         ++g_sv_ride_launches;
         return check_launch(who);
     }
-    const size_t lds = tile_lds_bytes(t16 ? 16 : 32, S);
+    const size_t lds = plan.lds;
 #ifndef ELO_DENSE_F32
     if (plan.chain) {
+        if (ask) return ELO_FUSED_FORM(ELO_FUSED_CHAIN, 0, mode);
         const dim3 rgrid((unsigned)((a->rows + RR_ROWS - 1) / RR_ROWS), b ? 2u : 1u);
         const bool f16 = a->feat_dtype == ELO_F16;
 #define CALL(k) ELO_LAUNCH_RR(k, rgrid, (hipStream_t)stream, pair)
@@ -3378,6 +3394,7 @@ extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_
         return check_launch(who);
     }
 #endif
+    if (ask) return tile_form(t16, mode);
     const dim3 grid((unsigned)(t16 ? u16 : u32), b ? 2u : 1u);
     hipStream_t s = (hipStream_t)stream;
 #define CALL(k) hipLaunchKernelGGL(k, grid, dim3(FUSED_BLOCK), lds, s, pair, S)
@@ -3385,7 +3402,8 @@ extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_
 #undef CALL
     return check_launch(who);
 }
-
+extern "C" int elo_mlp_fused_form(const elo_mlp_args *a, const elo_mlp_args *b) { return mlp_launch(a, b, nullptr, true, "elo_mlp_fused_form"); }
+extern "C" int elo_mlp_fused2(const elo_mlp_args *a, const elo_mlp_args *b, elo_stream_t s) { return mlp_launch(a, b, s, false, "elo_mlp_fused"); }
 extern "C" int elo_mlp_fused(const elo_mlp_args *a, elo_stream_t stream) { return elo_mlp_fused2(a, nullptr, stream); }
 
 // vector gathers only: channel counts must be whole 16-byte items, tensors 16-byte aligned
@@ -3428,14 +3446,14 @@ static int plan_cv1(const elo_cv1_args *a, TilePlan *p, const char *who)
     return check_group(a->group, a->H2, a->W2, p->lds, who);
 }
 
-extern "C" int elo_cv_stage1_fused(const elo_cv1_args *a, elo_stream_t stream)
+static int cv1_launch(const elo_cv1_args *a, elo_stream_t stream, const bool ask, const char *who)
 {
-    const char *who = "elo_cv_stage1_fused";
     TilePlan plan;
     if (int rc = plan_cv1(a, &plan, who)) return rc;
-    if ((long)a->batch * a->npoints == 0) return ELO_OK;
+    if ((long)a->batch * a->npoints == 0) return ask ? FORM_NOTHING : ELO_OK;
 #ifndef ELO_DENSE_F32
     if (!a->group.random_hw && cv_chain(a->C, plan.mode)) {
+        if (ask) return ELO_FUSED_FORM(ELO_FUSED_CHAIN, 0, plan.mode);
         const int P = RR_ROWS / a->K;                              // points per workgroup (128 rows)
         const dim3 grid((unsigned)(((long)a->batch * a->npoints + P - 1) / P));
         hipStream_t s = (hipStream_t)stream;
@@ -3451,6 +3469,7 @@ extern "C" int elo_cv_stage1_fused(const elo_cv1_args *a, elo_stream_t stream)
     const dim3 grid((unsigned)plan.units);
     const size_t lds = plan.lds;
     const int S = plan.S;
+    if (ask) return tile_form(plan.t16, plan.mode);
     hipStream_t s = (hipStream_t)stream;
 #define CALL(k) hipLaunchKernelGGL(k, grid, dim3(FUSED_BLOCK), lds, s, *a, S)
     if (a->group.random_hw) ELO_PICK(cv1_kernel, plan.t16, plan.mode, CALL);
@@ -3458,7 +3477,8 @@ extern "C" int elo_cv_stage1_fused(const elo_cv1_args *a, elo_stream_t stream)
 #undef CALL
     return check_launch(who);
 }
-
+extern "C" int elo_cv_stage1_form(const elo_cv1_args *a) { return cv1_launch(a, nullptr, true, "elo_cv_stage1_form"); }
+extern "C" int elo_cv_stage1_fused(const elo_cv1_args *a, elo_stream_t stream) { return cv1_launch(a, stream, false, "elo_cv_stage1_fused"); }
 
 extern "C" int elo_cv_stage1_setconv_fused(const elo_cv1_args *a, const elo_setconv_args *ja, const elo_setconv_args *jb,
                                            elo_stream_t stream)
@@ -3584,18 +3604,18 @@ static int plan_cv2(const elo_cv2_args *a, TilePlan *p, const char *who)
     return check_group(a->group, a->H, a->W, p->lds, who);
 }
 
-extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream)
+static int cv2_launch(const elo_cv2_args *a, elo_stream_t stream, const bool ask, const char *who)
 {
-    const char *who = "elo_cv_stage2_fused";
     TilePlan plan;
     if (int rc = plan_cv2(a, &plan, who)) return rc;
-    if (plan.units == 0) return ELO_OK;
+    if (plan.units == 0) return ask ? FORM_NOTHING : ELO_OK;
     const int S = plan.S, mode = plan.mode;
     const bool t16 = plan.t16;
     const size_t lds = plan.lds;
     hipStream_t s = (hipStream_t)stream;
 #ifndef ELO_DENSE_F32
     if (!a->group.random_hw && cv_chain(a->C, mode)) {
+        if (ask) return ELO_FUSED_FORM(ELO_FUSED_CHAIN, 0, mode);
         const int P = RR_ROWS / a->K;                              // points per workgroup (128 rows)
         const dim3 rgrid((unsigned)(((long)a->batch * a->npoints + P - 1) / P));
         const bool f16 = a->feat_dtype == ELO_F16;
@@ -3607,11 +3627,14 @@ extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream)
     }
 #endif
     const dim3 grid((unsigned)plan.units);
+    if (ask) return tile_form(t16, mode);
 #define CALL(k) hipLaunchKernelGGL(k, grid, dim3(FUSED_BLOCK), lds, s, *a, S)
     ELO_PICK(cv2_kernel, t16, mode, CALL);
 #undef CALL
     return check_launch(who);
 }
+extern "C" int elo_cv_stage2_form(const elo_cv2_args *a) { return cv2_launch(a, nullptr, true, "elo_cv_stage2_form"); }
+extern "C" int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream) { return cv2_launch(a, stream, false, "elo_cv_stage2_fused"); }
 
 // Cost-volume stage 2 (tile kernel) and the level's two set-upconv stage-2 MLPs (stage-1-only elo_mlp_args: n_layers2 = 0, no
 // clear_* / sv_* side jobs) in ONE launch (cv2_upconv_kernel): the bits of elo_cv_stage2_fused + elo_mlp_fused2(ja, jb).  Taken

@@ -294,6 +294,14 @@ def setconv_pair(job_a, job_b):
     return (ja[1], ja[2]), (jb[1], jb[2])
 
 
+def setconv_form(job_a, job_b=None):
+    """Which kernel setconv(**job_a) / setconv_pair(job_a, job_b) launches ('tile16/split', 'chain/half', ...: _lib.fused_form_name);
+    raises where the launch would be refused.  Host only: nothing is launched."""
+    ja = _setconv_args(**job_a)
+    jb = _setconv_args(**job_b) if job_b is not None else None
+    return L.fused_form("elo_setconv_fused_form", ja[0], jb[0] if jb is not None else None)
+
+
 def _mlp_args(sources, layers):
     L.require_gpu(*sources)
     batch_hint = sources[0].shape[0] if sources[0].dim() >= 3 else 0      # (B, N, C) inputs: the launcher's regime switch
@@ -401,6 +409,21 @@ def mlp2_pair(job_a, job_b, clear=None, sv=None):
     return (shape(out_a), shape(out2_a)), (shape(out_b), shape(out2_b))
 
 
+def mlp2(sources, layers, before, after, layers2):
+    """ONE job of two chained row-wise MLPs (mlp2_pair's job) in one launch; returns (out, out2)."""
+    a, out, out2, _keep = _mlp2_args(sources, layers, before, after, layers2)
+    L.call("elo_mlp_fused", a, out)
+    lead = sources[0].shape[:-1]
+    return out.reshape(lead + (out.shape[-1],)), out2.reshape(lead + (out2.shape[-1],))
+
+
+def mlp_form(job_a, job_b=None):
+    """Which kernel the row-wise MLP launch of one or two jobs takes (_lib.fused_form_name).  A job is a dict of mlp() arguments
+    (sources, layers) or of mlp2_pair's (sources, layers, before, after, layers2).  Host only: nothing is launched."""
+    args = [(_mlp2_args(**j) if "layers2" in j else _mlp_args(**j)) if j is not None else None for j in (job_a, job_b)]
+    return L.fused_form("elo_mlp_fused_form", args[0][0], args[1][0] if args[1] is not None else None)
+
+
 THROUGHPUT_BATCH = 4    # from this batch on a forward keeps the GPU busy by itself and the chain kernels win at every level
 
 
@@ -501,7 +524,7 @@ def _record(stage, args, kwargs):
 
 
 def cv_stage1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group=None, K=None,
-              side=None, side_chain=False):
+              side=None, side_chain=False, form_only=False):
     """Cost-volume stage 1 in one launch.  `side`: one or two set-conv jobs (dicts of setconv() keyword arguments, same
     shape) that only share inputs with the cost volume -- run INSIDE this launch (elo_cv_stage1_setconv_fused); the call
     then returns (out, [(out_a, new_xyz_a), ...]).
@@ -510,7 +533,7 @@ def cv_stage1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_x
     cost volume runs alone -- in whatever form its size asks for -- and the call returns (out, None): the caller launches
     the set-convs itself."""
     L.require_gpu(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask)
-    if _RECORD is not None:
+    if _RECORD is not None and not form_only:
         _record(1, (xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1), dict(group=group, K=K, side=side))
     xyz1, xyz2_proj = _f32c(xyz1), _f32c(xyz2_proj)
     (feat1, feat2_proj), dt, code = _features(feat1, feat2_proj)
@@ -546,8 +569,16 @@ def cv_stage1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_x
         jobs = [_setconv_args(**job) for job in side]                  # (args, out, new_xyz, keep-alive)
         L.call3("elo_cv_stage1_setconv_fused", a, jobs[0][0], jobs[1][0] if len(jobs) > 1 else None, out)
         return out, [(j[1], j[2]) for j in jobs]
+    if form_only:                                            # the argument block of the launch below, asked instead of launched
+        return L.fused_form("elo_cv_stage1_form", a)
     L.call("elo_cv_stage1_fused", a, out)
     return out
+
+
+def cv_stage1_form(*args, **kwargs):
+    """Which kernel cv_stage1 with these arguments (no side jobs) launches: _lib.fused_form_name of elo_cv_stage1_form on the very
+    argument block cv_stage1 builds -- behind its grouping pre-pass, where it takes one.  Nothing of the cost volume is launched."""
+    return cv_stage1(*args, form_only=True, **kwargs)
 
 
 def cv_stage1_alone(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group, K):
@@ -560,13 +591,14 @@ def cv_stage1_alone(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2
         _RECORD = keep
 
 
-def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group=None, K=None, side=None):
+def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group=None, K=None, side=None,
+              form_only=False):
     """Cost-volume stage 2 in one launch.  `side`: the two set-upconv stage-2 MLPs of the level (dicts of mlp() arguments:
     sources, layers; same shape) -- run INSIDE this launch where both are tile kernels (below THROUGHPUT_BATCH, in-kernel
     grouping, the pair below the chain kernel's rows: elo_cv_stage2_upconv_fused); the call then returns (out, [out_a, out_b]),
     or (out, None) where they cannot ride and the caller runs them itself."""
     L.require_gpu(xyz1_proj, feat1_proj, cost_proj, idx, mask)
-    if _RECORD is not None:
+    if _RECORD is not None and not form_only:
         _record(2, (xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1), dict(group=group, K=K, side=side))
     xyz1_proj = _f32c(xyz1_proj)
     (feat1_proj, cost_proj), dt, code = _features(feat1_proj, cost_proj)
@@ -591,5 +623,12 @@ def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, s
                 return out, [j[1].reshape(job["sources"][0].shape[:-1] + (j[1].shape[-1],)) for j, job in zip(jobs, side)]
         L.call("elo_cv_stage2_fused", a, out)
         return out, None
+    if form_only:                                            # the argument block of the launch below, asked instead of launched
+        return L.fused_form("elo_cv_stage2_form", a)
     L.call("elo_cv_stage2_fused", a, out)
     return out
+
+
+def cv_stage2_form(*args, **kwargs):
+    """Which kernel cv_stage2 with these arguments (no side jobs) launches, asked of elo_cv_stage2_form on cv_stage2's own argument block."""
+    return cv_stage2(*args, form_only=True, **kwargs)

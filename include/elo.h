@@ -955,6 +955,14 @@ int elo_pose_loss(const elo_pose_loss_args *a, elo_stream_t stream);
  * Masks are 0/1 by contract: `x * mask` is implemented as a select.
  *
  * Operands beyond the fp16 range saturate: elo_range_check() above counts them in a debugging run.
+ *
+ * The LDS limit.  A tile launch keeps `rows` (16 or 32) tile rows of S words in dynamic LDS, S = the widest of the call's
+ * concatenated input and its layer widths, each rounded up to 16 columns (plus a few words of bank padding), beside 768
+ * bytes of per-row metadata and, with in-kernel grouping, the visiting order.  A call whose tile would need more than
+ * 64 KiB -- a row-wise MLP or a set-conv over a concatenation of more than 496 columns (32-row tile; 992 where the launcher
+ * takes the 16-row tile) -- is refused with ELO_ERR_LIMIT before any HIP call, pre-grouped calls included.  The elo_*_form
+ * queries below answer the same code; for such a row-wise MLP elo_mlp_sv_parts and elo_cv_stage2_upconv_form answer 0 (it cannot be
+ * launched, so nothing can ride on it).  A call without rows or points launches nothing and is ELO_OK whatever its widths.
  * ------------------------------------------------------------------------- */
 enum { ELO_PRODUCTS_SPLIT = 0,      /* fp32-class: hi/lo split operands, three fp16 MFMA products (default)     */
        ELO_PRODUCTS_HALF = 1 };     /* fp16 arithmetic: operands rounded to nearest fp16, ONE product, fp32 accumulate;
@@ -1172,6 +1180,29 @@ int elo_cv_stage2_fused(const elo_cv2_args *a, elo_stream_t stream);
  * elo_cv_stage2_upconv_form: 1 when the launch takes them (else the separate entry points).  Same results bit for bit. */
 int elo_cv_stage2_upconv_form(const elo_cv2_args *a, const elo_mlp_args *ja, const elo_mlp_args *jb);
 int elo_cv_stage2_upconv_fused(const elo_cv2_args *a, const elo_mlp_args *ja, const elo_mlp_args *jb, elo_stream_t stream);
+
+/* WHICH KERNEL elo_setconv_fused2 / elo_mlp_fused2 / elo_cv_stage1_fused / elo_cv_stage2_fused launch for an argument block
+ * (b may be NULL: a single job).  Host-only queries: nothing is launched and no tensor is dereferenced -- only the pointers'
+ * VALUES are read (NULL or not, alignment) -- and the current elo_tuning is read as the launcher reads it.  Each entry point
+ * switches on the same function, so the answer is what a launch with these arguments takes.
+ * Return: ELO_FUSED_FORM(family, rows, products) of the enumerators below, or the negative elo_status with which the entry
+ * point would refuse the block (the LDS limit above included).  With no points / rows the entry points launch nothing and the
+ * answer is ELO_FUSED_FORM(ELO_FUSED_TILE, 32, ELO_FUSED_SPLIT).
+ *   family:   TILE (setconv_kernel, mlp_kernel, cv1_kernel / cv1_meta_kernel, cv2_kernel), CHAIN (the register-resident kernels),
+ *             NARROW_MFMA / NARROW_VALU (the wave-per-point set-conv kernels), SV_RIDE (mlp_sv_kernel: sv_scratch is set);
+ *   rows:     16 or 32, the tile height (TILE and SV_RIDE; 0 for the other families, which have no tile of their own);
+ *   products: SPLIT, HALF, or CHECKED (the split instances that also count out-of-range operands: elo_range_check).  The narrow
+ *             VALU kernel computes in fp32 whatever the layers say: it answers SPLIT. */
+enum { ELO_FUSED_TILE = 0, ELO_FUSED_CHAIN = 1, ELO_FUSED_NARROW_MFMA = 2, ELO_FUSED_NARROW_VALU = 3, ELO_FUSED_SV_RIDE = 4 };
+enum { ELO_FUSED_SPLIT = 0, ELO_FUSED_HALF = 1, ELO_FUSED_CHECKED = 2 };
+#define ELO_FUSED_FORM(family, rows, products) ((family) | (rows) << 4 | (products) << 12)
+#define ELO_FUSED_FAMILY(form) ((form) & 15)
+#define ELO_FUSED_ROWS(form) ((form) >> 4 & 255)
+#define ELO_FUSED_PRODUCTS(form) ((form) >> 12 & 15)
+int elo_setconv_fused_form(const elo_setconv_args *a, const elo_setconv_args *b);
+int elo_mlp_fused_form(const elo_mlp_args *a, const elo_mlp_args *b);
+int elo_cv_stage1_form(const elo_cv1_args *a);
+int elo_cv_stage2_form(const elo_cv2_args *a);
 
 #ifdef __cplusplus
 }
