@@ -63,6 +63,19 @@ def fused_form_name(value):
     return "%s%s/%s" % (FUSED_FAMILIES[family], rows or "", FUSED_PRODUCTS[products])
 
 
+# ... and the pose tail's: ELO_TAIL_FORM(partials, merge, head, wide, warp, parts) of the ELO_TAIL_* enumerators, by value
+TAIL_PARTIALS = ("ready", "f32", "f16")
+TAIL_MERGES = ("trips16", "trips32")
+TAIL_HEADS = ("model", "generic")
+
+
+def tail_form_name(value):
+    """ELO_TAIL_FORM as '<partials>x<parts>/<merge>/<head>[+wide][+warp]': 'f32x4/trips16/model', 'readyx129/trips32/model+warp'."""
+    partials, merge, head, wide, warp, parts = value & 3, value >> 2 & 1, value >> 3 & 1, value >> 4 & 1, value >> 5 & 1, value >> 8
+    return "%sx%d/%s/%s%s%s" % (TAIL_PARTIALS[partials], parts, TAIL_MERGES[merge], TAIL_HEADS[head], "+wide" if wide else "",
+                                "+warp" if warp else "")
+
+
 SoftmaxValidArgs = _struct("elo_softmax_valid_args", [
     ("batch", _i), ("npoints", _i), ("C", _i), ("feature", _vp), ("weight", _vp), ("xyz", _vp), ("out", _vp),
     ("scratch", _vp), ("stats", _vp)])
@@ -280,6 +293,8 @@ SYMBOLS = [
     ("elo_mlp_fused_form", ctypes.c_int, [ctypes.POINTER(MlpArgs), ctypes.POINTER(MlpArgs)]),
     ("elo_cv_stage1_form", ctypes.c_int, [ctypes.POINTER(Cv1Args)]),
     ("elo_cv_stage2_form", ctypes.c_int, [ctypes.POINTER(Cv2Args)]),
+    ("elo_softmax_valid_parts", ctypes.c_int, [ctypes.c_int]),
+    ("elo_pose_head_form", ctypes.c_int, [ctypes.POINTER(PoseHeadArgs), ctypes.POINTER(WarpProjectArgs)]),
 ]
 
 _lib = None
@@ -364,6 +379,15 @@ def fused_form(query, a, b=None):
     if rc < 0:
         check(rc)
     return fused_form_name(rc)
+
+
+def tail_form(a, w=None):
+    """What elo_pose_head_form answers for the pose head's argument block (and the warp's, w), as tail_form_name spells it; raises
+    where elo_pose_head / elo_pose_head_warp would refuse them.  Host only: nothing is launched."""
+    rc = lib().elo_pose_head_form(ctypes.byref(a), ctypes.byref(w) if w is not None else None)
+    if rc < 0:
+        check(rc)
+    return tail_form_name(rc)
 
 
 def check(rc):

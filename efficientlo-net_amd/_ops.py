@@ -459,7 +459,7 @@ class PoseRing:
 
 
 def pose_head(feature_bnc, weight_bnc, xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t, q_coarse=None, t_coarse=None, pose7=None,
-              clear=None, warp=None, next_orders=None, partials=None, sensor=None):
+              clear=None, warp=None, next_orders=None, partials=None, sensor=None, form_only=False):
     """softmax_valid -> conv1d(256) -> q,t heads -> normalise -> compose with the coarse pose, two launches.
     pwclo_model.py:194-208 / :262-280.  Returns (q (B,4), t (B,3), q_norm (B,4)); `pose7` (B,7), if given, also receives [q_norm | t].
     `next_orders`: an elo_perm_refresh_args (perm.PermSource.refresh_args): the next pooled set of visiting orders is
@@ -520,13 +520,28 @@ def pose_head(feature_bnc, weight_bnc, xyz_bn3, W_big, b_big, W_q, b_q, W_t, b_t
         az, vres, voff = projection_constants(Hw, Ww, sensor)
         w = L.WarpProjectArgs(Bw, Nw, Cw, Hw, Ww, az, vres, voff, xyz_w.data_ptr(), ptr(feat_w), None, None,
                               warped.data_ptr(), clear.out_xyz.data_ptr(), ptr(clear.out_feat), clear.scratch.data_ptr(), 1, fcode)
+        if form_only:                                        # the argument blocks of the launch below, asked instead of launched
+            return L.tail_form(a, w)
         L.call2("elo_pose_head_warp", a, w, q)
         clear.result = (warped, clear.out_xyz, clear.out_feat)
         return q, t, q_norm
+    if form_only:
+        return L.tail_form(a)
     L.call("elo_pose_head", a, q)
     if clear is not None:
         clear.cleared = True
     return q, t, q_norm
+
+
+def pose_head_form(*args, **kwargs):
+    """What pose_head with these arguments launches (elo_pose_head_form on pose_head's own argument blocks; _lib.tail_form_name:
+    'f32x4/trips16/model', 'readyx129/trips32/model+warp', ...); raises where the call would be refused.  Launches nothing."""
+    return pose_head(*args, form_only=True, **kwargs)
+
+
+def softmax_valid_parts(npoints):
+    """Slices per batch element of the partial-sums launch over `npoints` points (elo_softmax_valid_parts)."""
+    return L.lib().elo_softmax_valid_parts(int(npoints))
 
 
 def _aug_frame_dev(aug_frame, B, dev):

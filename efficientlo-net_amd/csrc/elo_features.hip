@@ -771,6 +771,13 @@ __global__ __launch_bounds__(ELO_BLOCK) void softmax_valid_partial_kernel(const 
     }
 }
 
+// The pose tail's two launch-uniform decisions, written once: pose_head_kernel branches on them and elo_pose_head_form
+// (include/elo.h ELO_TAIL_FORM) answers them.
+//   the in-head merge: one trip of 16 slices per thread up to 64 slices, trips of 32 above (the row tiles of an MLP launch);
+//   the model's head: C = 64 pooled channels and one hidden unit per thread, weights requested before the merge.
+__host__ __device__ __forceinline__ bool sv_merge_trips16(int parts) { return parts <= 64; }
+__host__ __device__ __forceinline__ bool pose_model_head(int C, int hidden, int block) { return C == 64 && hidden == block; }
+
 // merged softmax-pooled feature of channel c of batch element b (0 when no point is valid)
 __device__ __forceinline__ float sv_merge(const SvPartials &s, int b, int c, int C, int parts)
 {
@@ -927,7 +934,7 @@ __global__ __launch_bounds__(BLOCK) void pose_head_kernel(const elo_pose_head_ar
     // W_q / W_t do not depend on anything computed here -- requested now, they arrive while the slices are merged
     // (otherwise four dependent batches of 16 loads sit between the merge and the heads).
     constexpr int HEAD_C = 64;
-    const bool model_head = a.C == HEAD_C && a.hidden == BLOCK;
+    const bool model_head = pose_model_head(a.C, a.hidden, BLOCK);
     float wb[HEAD_C], wq[4], wt[3], bias_big = 0.0f;
     auto request_weights = [&]() {
         const int j = tid;                              // this thread owns hidden unit `tid`
@@ -969,7 +976,7 @@ __global__ __launch_bounds__(BLOCK) void pose_head_kernel(const elo_pose_head_ar
                 }
             }
         };
-        if (parts <= 64) trips(std::integral_constant<int, 16>());
+        if (sv_merge_trips16(parts)) trips(std::integral_constant<int, 16>());
         else trips(std::integral_constant<int, 32>());
     }
     POSE_STAMP(1);                                     // this thread's slices merged (the partial sums have landed)
@@ -1596,9 +1603,11 @@ extern "C" int elo_debug_pose_clock(unsigned long long *out33)
 static int sv_parts(int npoints)
 {
     constexpr int SV_MAX_SLICES = 64;                // (the scratch layout has room for ELO_SV_MAX_PARTS: the row tiles of elo_mlp_args.sv_*)
-    int parts = (npoints + 63) / 64;                 // >= 64 points (16 per wave) per block
+    int parts = npoints / 64 + (npoints % 64 != 0);  // >= 64 points (16 per wave) per block ((npoints + 63) / 64 without its overflow)
     return parts < 1 ? 1 : parts > SV_MAX_SLICES ? SV_MAX_SLICES : parts;
 }
+
+extern "C" int elo_softmax_valid_parts(int npoints) { return sv_parts(npoints); }
 
 extern "C" int elo_softmax_valid(const elo_softmax_valid_args *a, elo_stream_t stream)
 {
@@ -1629,7 +1638,8 @@ static int check_warp_project(const elo_warp_project_args *a, const char *who)
 }
 
 // pose head, optionally followed in the same launches by the warp + projection of `w` (nullptr: none)
-static int pose_head_impl(const elo_pose_head_args *a, const elo_warp_project_args *w, elo_stream_t stream, const char *who)
+// `ask` (elo_pose_head_form): every check and every decision of a launch, and where it would launch the form instead
+static int pose_head_impl(const elo_pose_head_args *a, const elo_warp_project_args *w, elo_stream_t stream, const bool ask, const char *who)
 {
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->batch >= 0 && a->npoints > 0 && a->C > 0 && a->hidden > 0, who, "bad sizes");
@@ -1656,10 +1666,19 @@ static int pose_head_impl(const elo_pose_head_args *a, const elo_warp_project_ar
     }
     ELO_REQUIRE(a->ready_parts >= 0 && a->ready_parts <= ELO_SV_MAX_PARTS, who, "ready_parts is 0..ELO_SV_MAX_PARTS");
     ELO_REQUIRE(!a->ready_parts || a->C == 64, who, "ready_parts: the partial sums of an MLP launch are 64 channels wide");
-    if (a->batch == 0) return ELO_OK;
-    hipStream_t s = (hipStream_t)stream;
+    // pose_head_kernel's dynamic LDS: [C] pooled feature, [hidden] big, [8] heads, [waves][8] head sums, [3][4][64] merge groups
+    const size_t lds = sizeof(float) * ((size_t)a->C + a->hidden + 8 + 8 * (ELO_BLOCK / ELO_WAVE) + 3 * 4 * 64);
+    if (a->batch != 0 && lds > 64 * 1024)             // (an empty batch launches nothing and is ELO_OK whatever its widths, as before)
+        return fail(ELO_ERR_LIMIT, "%s: a head of C = %d, hidden = %d needs %zu bytes of LDS (limit 65536)", who, a->C, a->hidden, lds);
     {
         const int parts = a->ready_parts ? a->ready_parts : sv_parts(a->npoints);
+        if (ask)
+            return ELO_TAIL_FORM(a->ready_parts ? ELO_TAIL_PARTIALS_READY : f16 ? ELO_TAIL_PARTIALS_F16 : ELO_TAIL_PARTIALS_F32,
+                                 sv_merge_trips16(parts) ? ELO_TAIL_TRIPS16 : ELO_TAIL_TRIPS32,
+                                 pose_model_head(a->C, a->hidden, ELO_BLOCK) ? ELO_TAIL_HEAD_MODEL : ELO_TAIL_HEAD_GENERIC,
+                                 a->C > 64 ? 1 : 0, w ? 1 : 0, parts);
+        if (a->batch == 0) return ELO_OK;
+        hipStream_t s = (hipStream_t)stream;
         const ProjectionClear clear{a->clear_scratch, a->clear_xyz, (unsigned *)a->clear_feat, a->clear_cells,
                                     f16 ? a->clear_C / 2 : a->clear_C, a->batch};
         const dim3 pgrid(parts, a->batch, (a->C + ELO_WAVE - 1) / ELO_WAVE);
@@ -1670,11 +1689,11 @@ static int pose_head_impl(const elo_pose_head_args *a, const elo_warp_project_ar
         else
             hipLaunchKernelGGL(softmax_valid_partial_kernel<false>, pgrid, dim3(ELO_BLOCK), 0, s, a->feature, a->weight, a->xyz,
                                a->npoints, a->C, parts, a->scratch, clear);
-        const size_t lds = sizeof(float) * ((size_t)a->C + a->hidden + 8 + 8 * (ELO_BLOCK / ELO_WAVE) + 3 * 4 * 64);
         const unsigned xb = w ? (unsigned)((w->npoints + ELO_BLOCK - 1) / ELO_BLOCK) : 1u;
         hipLaunchKernelGGL((pose_head_kernel<ELO_BLOCK>), dim3(xb, a->batch), dim3(ELO_BLOCK), lds, s, *a, parts, wv, w ? 1 : 0);
     }
     if (w) {
+        hipStream_t s = (hipStream_t)stream;
         const size_t cells = (size_t)w->batch * w->H * w->W, pts = (size_t)w->batch * w->npoints;
         const size_t elems = pts * (3 + (f16 ? w->C / 2 : w->C));
         const unsigned gb = (unsigned)((elems + ELO_BLOCK - 1) / ELO_BLOCK);
@@ -1686,14 +1705,19 @@ static int pose_head_impl(const elo_pose_head_args *a, const elo_warp_project_ar
 
 extern "C" int elo_pose_head(const elo_pose_head_args *a, elo_stream_t stream)
 {
-    return pose_head_impl(a, nullptr, stream, "elo_pose_head");
+    return pose_head_impl(a, nullptr, stream, false, "elo_pose_head");
 }
 
 extern "C" int elo_pose_head_warp(const elo_pose_head_args *a, const elo_warp_project_args *w, elo_stream_t stream)
 {
     const char *who = "elo_pose_head_warp";
     ELO_REQUIRE(w, who, "null warp block");
-    return pose_head_impl(a, w, stream, who);
+    return pose_head_impl(a, w, stream, false, who);
+}
+
+extern "C" int elo_pose_head_form(const elo_pose_head_args *a, const elo_warp_project_args *w)
+{
+    return pose_head_impl(a, w, nullptr, true, "elo_pose_head_form");
 }
 
 // The three launches of an input stage (clear, per-point pass, scatter); `cells_launch(grid, ps)` is the per-point pass of the

@@ -528,6 +528,36 @@ int elo_preprocess_gt(const elo_preprocess_gt_args *a, elo_stream_t stream);
  * the third launch is the projection's scatter.  w->q / w->t are ignored (the pose is a->q, a->t); w->warped is required. */
 int elo_pose_head_warp(const elo_pose_head_args *a, const elo_warp_project_args *w, elo_stream_t stream);
 
+/* WHAT THE POSE TAIL LAUNCHES for an argument block.  Host-only queries: nothing is launched, no tensor is dereferenced (only the
+ * pointers' values are read: NULL or not, equal or not).  Additive: no struct changed.
+ * elo_softmax_valid_parts(npoints): the slices per batch element of the partial-sums launch of elo_softmax_valid and of
+ *   elo_pose_head / elo_pose_head_warp without ready_parts -- ceil(npoints / 64), at least 1, at most 64.
+ * elo_pose_head_form(a, w): elo_pose_head (w == NULL) / elo_pose_head_warp itself, run up to the point where it would launch:
+ *   ELO_TAIL_FORM(partials, merge, head, wide, warp, parts) of the enumerators below, or the negative elo_status with which the
+ *   entry point would refuse the block.
+ *     partials: READY (ready_parts > 0: no partial-sums launch), F32 / F16 (softmax_valid_partial_kernel in that storage type);
+ *     merge:    TRIPS16 (parts <= 64: each of a channel's four threads takes its slices in one trip of 16) / TRIPS32 (trips of 32);
+ *     head:     MODEL (C == 64 and hidden == 256: one hidden unit per thread, weights requested ahead of the merge) / GENERIC;
+ *     wide:     1 when C > 64: channels 64.. are merged by elo_softmax_valid's own sequential merge inside the head;
+ *     warp:     1 when the warp and pass A of the projection ride in the head's launch (w != NULL);
+ *     parts:    the slices per batch element the head merges (ready_parts, or elo_softmax_valid_parts(npoints)).
+ *   With batch == 0 nothing is launched; the query still answers the form of the block's sizes.
+ * The LDS limit: the head keeps C + hidden + 808 floats in dynamic LDS; a head with C + hidden > 15576 (more than 64 KiB) is refused
+ * with ELO_ERR_LIMIT before any HIP call (an empty batch launches nothing and stays ELO_OK). */
+enum { ELO_TAIL_PARTIALS_READY = 0, ELO_TAIL_PARTIALS_F32 = 1, ELO_TAIL_PARTIALS_F16 = 2 };
+enum { ELO_TAIL_TRIPS16 = 0, ELO_TAIL_TRIPS32 = 1 };
+enum { ELO_TAIL_HEAD_MODEL = 0, ELO_TAIL_HEAD_GENERIC = 1 };
+#define ELO_TAIL_FORM(partials, merge, head, wide, warp, parts) \
+    ((partials) | (merge) << 2 | (head) << 3 | (wide) << 4 | (warp) << 5 | (parts) << 8)
+#define ELO_TAIL_PARTIALS(form) ((form) & 3)
+#define ELO_TAIL_MERGE(form) ((form) >> 2 & 1)
+#define ELO_TAIL_HEAD(form) ((form) >> 3 & 1)
+#define ELO_TAIL_WIDE(form) ((form) >> 4 & 1)
+#define ELO_TAIL_WARP(form) ((form) >> 5 & 1)
+#define ELO_TAIL_PARTS(form) ((form) >> 8)
+int elo_softmax_valid_parts(int npoints);
+int elo_pose_head_form(const elo_pose_head_args *a, const elo_warp_project_args *w);
+
 /* POSE FIT on the two range images of a pair (csrc/elo_posefit.hip): how well a relative pose registers them, the 6x6
  * information matrix of that pose, and -- on request -- a few Gauss-Newton steps on it ("polish").
  * pose_in: (batch,7) [q | t], frame 1 -> frame 2, p' = R(q) p + t: the layout and convention of elo_pose_head_args.pose7.  q is
