@@ -3,6 +3,7 @@ kernels"): weight packing into MFMA B-fragment order and torch-tensor front-ends
 
 A packed layer is cached in the VariableStore next to the folded weights and dropped by
 VariableStore.invalidate(); packing costs a few small torch ops once per parameter update."""
+import collections
 import ctypes
 import os
 
@@ -10,7 +11,7 @@ import torch
 
 from . import _lib as L
 from . import tf_util, tuning
-from .fused_conv import grouping_entry
+from .fused_conv import all_pixels as _all_pixels, grouping_entry
 
 
 def fp32_mfma():
@@ -445,27 +446,6 @@ def _prepass_rows(stage=1, batch=1):
     return (1 << 60) if e == 0 else 0 if e == 1 else int(e)
 
 
-_HW = {}
-
-
-def _all_pixels(B, H, W, device):
-    """(B, H*W, 2) int32 (h, w) of every pixel, row-major: the centre list of the cost volume's select-k (cached)."""
-    key = (B, H, W, str(device))
-    hit = _HW.get(key)
-    if hit is None:
-        hh = torch.arange(H, dtype=torch.int32, device=device).view(1, H, 1, 1).expand(B, H, W, 1)
-        ww = torch.arange(W, dtype=torch.int32, device=device).view(1, 1, W, 1).expand(B, H, W, 1)
-        hit = torch.cat([hh, ww], -1).reshape(B, H * W, 2).contiguous()
-        if hit.is_cuda and torch.cuda.is_current_stream_capturing():
-            return hit
-        if len(_HW) >= 64:
-            _HW.clear()
-        _HW[key] = hit
-    return hit
-
-
-
-
 def group_prepass(kind, xyz1_grid, xyz2_grid, group, K):
     """A cost volume's grouping (every pixel of xyz1_grid a centre; kind "select" = stage 1's select-k, "random" = stage
     2's random-k) as its own launch: (idx (B,N,K,3) int32, mask (B,N,K)).  Forms: random-k takes the LDS-tiled
@@ -523,35 +503,22 @@ def _record(stage, args, kwargs):
     _RECORD.append((stage, tuple(keep(v) for v in args), kw, bool(kwargs.get("side"))))
 
 
-def cv_stage1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group=None, K=None,
-              side=None, side_chain=False, form_only=False):
-    """Cost-volume stage 1 in one launch.  `side`: one or two set-conv jobs (dicts of setconv() keyword arguments, same
-    shape) that only share inputs with the cost volume -- run INSIDE this launch (elo_cv_stage1_setconv_fused); the call
-    then returns (out, [(out_a, new_xyz_a), ...]).
-    `side_chain` (with two side jobs): the side jobs ride only if stage 1 AND they take the register-resident chain form
-    (select-k pre-pass, then ONE launch of cv1_rr + set-conv chain workgroups: elo_cv_stage1_setconv_chain); otherwise the
-    cost volume runs alone -- in whatever form its size asks for -- and the call returns (out, None): the caller launches
-    the set-convs itself."""
+Cv1 = collections.namedtuple("Cv1", "out side")          # cv_stage1's result; side: [(out, new_xyz), ...] of the jobs that rode, or None
+Cv2 = collections.namedtuple("Cv2", "out up_out")        # cv_stage2's result; up_out: [out_a, out_b] of the jobs that rode, or None
+
+
+def _cv1_args(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group=None, K=None,
+              prepass=True):
+    """The argument block of a stage-1 launch -- with `prepass`, behind the select-k pre-pass where the stage's size asks for
+    one.  -> (args, out, whether the pre-pass ran, what must stay alive until the launch)"""
     L.require_gpu(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask)
-    if _RECORD is not None and not form_only:
-        _record(1, (xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1), dict(group=group, K=K, side=side))
     xyz1, xyz2_proj = _f32c(xyz1), _f32c(xyz2_proj)
     (feat1, feat2_proj), dt, code = _features(feat1, feat2_proj)
     _, H2, W2, C = feat2_proj.shape
     B, N = xyz1.shape[0], xyz1.shape[1]
     ptr = lambda x: x.data_ptr() if x is not None else None
-    chain_jobs = None
-    if side and side_chain:
-        rr = len(side) == 2 and N == H2 * W2 and _rr_path(group, B, N, K, C)
-        if rr:
-            chain_jobs = [_setconv_args(**job) for job in side]          # (args, out, new_xyz, keep-alive)
-            probe = L.Cv1Args(B, N, K, H2, W2, C, None, None, None, None, None, None, cv0.struct(), cv1.struct(), cv2.struct(),
-                              cv_xyz.struct(), sum_cv0.struct(), sum_cv1.struct(), None, _NO_GROUP, code)
-            if L.lib().elo_cv_stage1_setconv_chain_form(ctypes.byref(probe), ctypes.byref(chain_jobs[0][0]), ctypes.byref(chain_jobs[1][0])) != 1:
-                chain_jobs = None
-        if chain_jobs is None:
-            return cv_stage1_alone(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group, K), None
-    if (not side or chain_jobs) and N == H2 * W2 and _rr_path(group, B, N, K, C):
+    grouped = prepass and N == H2 * W2 and _rr_path(group, B, N, K, C)
+    if grouped:
         idx, mask = group_prepass("select", xyz1.reshape(B, H2, W2, 3), xyz2_proj, group, K)
         group = None
     if group is None:
@@ -562,44 +529,49 @@ def cv_stage1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_x
                   ptr(idx), ptr(mask), cv0.struct(), cv1.struct(), cv2.struct(), cv_xyz.struct(),
                   sum_cv0.struct(), sum_cv1.struct(), out.data_ptr(),
                   group.struct(B, N, K, xyz1.device) if group is not None else _NO_GROUP, code)
-    if chain_jobs:
-        L.call3("elo_cv_stage1_setconv_chain", a, chain_jobs[0][0], chain_jobs[1][0], out)
-        return out, [(j[1], j[2]) for j in chain_jobs]
+    return a, out, grouped, (xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, group)
+
+
+def cv_stage1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group=None, K=None,
+              side=None, side_chain=False):
+    """Cost-volume stage 1 in one launch.  Called without `side` it returns out; called with `side` (a list, empty or not) always
+    Cv1(out, side).  `side`: one or two set-conv jobs (dicts of setconv() keyword arguments, same shape) that only share inputs
+    with the cost volume -- run INSIDE this launch (elo_cv_stage1_setconv_fused); the result's `side` is then
+    [(out_a, new_xyz_a), ...], and None where none rode.
+    `side_chain` (with two side jobs): the side jobs ride only if stage 1 AND they take the register-resident chain form
+    (select-k pre-pass, then ONE launch of cv1_rr + set-conv chain workgroups: elo_cv_stage1_setconv_chain); otherwise the
+    cost volume runs alone -- in whatever form its size asks for -- and the result's `side` is None: the caller launches
+    the set-convs itself."""
+    layers = (cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1)
+    # side jobs on the tile kernel keep the in-kernel grouping; alone, or beside the chain form, the stage takes its pre-pass
+    a, out, grouped, _keep = _cv1_args(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, *layers, group=group, K=K, prepass=not side or side_chain)
+    if _RECORD is not None:
+        _record(1, (xyz1, feat1, xyz2_proj, feat2_proj, idx, mask) + layers, dict(group=group, K=K, side=side))
+    if side and side_chain:
+        if grouped and len(side) == 2:
+            jobs = [_setconv_args(**job) for job in side]              # (args, out, new_xyz, keep-alive)
+            if L.lib().elo_cv_stage1_setconv_chain_form(ctypes.byref(a), ctypes.byref(jobs[0][0]), ctypes.byref(jobs[1][0])) == 1:
+                L.call3("elo_cv_stage1_setconv_chain", a, jobs[0][0], jobs[1][0], out)
+                return Cv1(out, [(j[1], j[2]) for j in jobs])
+        side = []
     if side:
         jobs = [_setconv_args(**job) for job in side]                  # (args, out, new_xyz, keep-alive)
         L.call3("elo_cv_stage1_setconv_fused", a, jobs[0][0], jobs[1][0] if len(jobs) > 1 else None, out)
-        return out, [(j[1], j[2]) for j in jobs]
-    if form_only:                                            # the argument block of the launch below, asked instead of launched
-        return L.fused_form("elo_cv_stage1_form", a)
+        return Cv1(out, [(j[1], j[2]) for j in jobs])
     L.call("elo_cv_stage1_fused", a, out)
-    return out
+    return out if side is None else Cv1(out, None)
 
 
 def cv_stage1_form(*args, **kwargs):
     """Which kernel cv_stage1 with these arguments (no side jobs) launches: _lib.fused_form_name of elo_cv_stage1_form on the very
     argument block cv_stage1 builds -- behind its grouping pre-pass, where it takes one.  Nothing of the cost volume is launched."""
-    return cv_stage1(*args, form_only=True, **kwargs)
+    return L.fused_form("elo_cv_stage1_form", _cv1_args(*args, **kwargs)[0])
 
 
-def cv_stage1_alone(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group, K):
-    """cv_stage1 without side jobs and without a second recording of the call (cv_stage1(side_chain=True) falls back on it)."""
-    global _RECORD
-    keep, _RECORD = _RECORD, None
-    try:
-        return cv_stage1(xyz1, feat1, xyz2_proj, feat2_proj, idx, mask, cv0, cv1, cv2, cv_xyz, sum_cv0, sum_cv1, group=group, K=K)
-    finally:
-        _RECORD = keep
-
-
-def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group=None, K=None, side=None,
-              form_only=False):
-    """Cost-volume stage 2 in one launch.  `side`: the two set-upconv stage-2 MLPs of the level (dicts of mlp() arguments:
-    sources, layers; same shape) -- run INSIDE this launch where both are tile kernels (below THROUGHPUT_BATCH, in-kernel
-    grouping, the pair below the chain kernel's rows: elo_cv_stage2_upconv_fused); the call then returns (out, [out_a, out_b]),
-    or (out, None) where they cannot ride and the caller runs them itself."""
+def _cv2_args(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group=None, K=None):
+    """The argument block of a stage-2 launch, behind the random-k pre-pass where the stage's size asks for one.
+    -> (args, out, what must stay alive until the launch)"""
     L.require_gpu(xyz1_proj, feat1_proj, cost_proj, idx, mask)
-    if _RECORD is not None and not form_only:
-        _record(2, (xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1), dict(group=group, K=K, side=side))
     xyz1_proj = _f32c(xyz1_proj)
     (feat1_proj, cost_proj), dt, code = _features(feat1_proj, cost_proj)
     B, H, W, C = feat1_proj.shape
@@ -615,20 +587,27 @@ def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, s
     a = L.Cv2Args(B, N, K, H, W, C, xyz1_proj.data_ptr(), feat1_proj.data_ptr(), cost_proj.data_ptr(), ptr(idx),
                   ptr(mask), xyz_enc.struct(), sum_cost0.struct(), sum_cost1.struct(), out.data_ptr(),
                   group.struct(B, N, K, xyz1_proj.device) if group is not None else _NO_GROUP, code)
-    if side:
-        if B < THROUGHPUT_BATCH:
-            jobs = [_mlp_args(**job) for job in side]                   # (args, out, keep-alive)
-            if L.lib().elo_cv_stage2_upconv_form(ctypes.byref(a), ctypes.byref(jobs[0][0]), ctypes.byref(jobs[1][0])) == 1:
-                L.call3("elo_cv_stage2_upconv_fused", a, jobs[0][0], jobs[1][0], out)
-                return out, [j[1].reshape(job["sources"][0].shape[:-1] + (j[1].shape[-1],)) for j, job in zip(jobs, side)]
-        L.call("elo_cv_stage2_fused", a, out)
-        return out, None
-    if form_only:                                            # the argument block of the launch below, asked instead of launched
-        return L.fused_form("elo_cv_stage2_form", a)
+    return a, out, (xyz1_proj, feat1_proj, cost_proj, idx, mask, group)
+
+
+def cv_stage2(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group=None, K=None, side=None):
+    """Cost-volume stage 2 in one launch.  Called without `side` it returns out; called with `side` (a list, empty or not) always
+    Cv2(out, up_out).  `side`: the two set-upconv stage-2 MLPs of the level (dicts of mlp() arguments: sources, layers; same
+    shape) -- run INSIDE this launch where both are tile kernels (below THROUGHPUT_BATCH, in-kernel grouping, the pair below the
+    chain kernel's rows: elo_cv_stage2_upconv_fused); the result's `up_out` is then [out_a, out_b], and None where they cannot
+    ride (or the list was empty): the caller runs them itself."""
+    a, out, _keep = _cv2_args(xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1, group, K)
+    if _RECORD is not None:
+        _record(2, (xyz1_proj, feat1_proj, cost_proj, idx, mask, xyz_enc, sum_cost0, sum_cost1), dict(group=group, K=K, side=side))
+    if side and a.batch < THROUGHPUT_BATCH:
+        jobs = [_mlp_args(**job) for job in side]                       # (args, out, keep-alive)
+        if L.lib().elo_cv_stage2_upconv_form(ctypes.byref(a), ctypes.byref(jobs[0][0]), ctypes.byref(jobs[1][0])) == 1:
+            L.call3("elo_cv_stage2_upconv_fused", a, jobs[0][0], jobs[1][0], out)
+            return Cv2(out, [j[1].reshape(job["sources"][0].shape[:-1] + (j[1].shape[-1],)) for j, job in zip(jobs, side)])
     L.call("elo_cv_stage2_fused", a, out)
-    return out
+    return out if side is None else Cv2(out, None)
 
 
 def cv_stage2_form(*args, **kwargs):
     """Which kernel cv_stage2 with these arguments (no side jobs) launches, asked of elo_cv_stage2_form on cv_stage2's own argument block."""
-    return cv_stage2(*args, form_only=True, **kwargs)
+    return L.fused_form("elo_cv_stage2_form", _cv2_args(*args, **kwargs)[0])

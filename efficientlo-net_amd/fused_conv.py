@@ -64,6 +64,26 @@ def register_dense_index(idx_n2):
     return idx_n2
 
 
+_ALL_PIXELS = {}         # (B, H, W, device) -> the one cached "every pixel, row-major" tensor of that grid
+
+
+def all_pixels(B, H, W, device):
+    """(B, H*W, 2) int32, row-major (h, w) of every pixel (utils/pointnet_util.py:23-30): pointnet_util.get_hw_idx and the centre
+    list of fused.group_prepass.  Cached, and registered as a dense index (random-k calls with it take the LDS-tiled kernel)."""
+    key = (B, H, W, str(device))
+    hit = _ALL_PIXELS.get(key)
+    if hit is None:
+        hh = torch.arange(H, dtype=torch.int32, device=device).view(1, H, 1, 1).expand(B, H, W, 1)
+        ww = torch.arange(W, dtype=torch.int32, device=device).view(1, 1, W, 1).expand(B, H, W, 1)
+        hit = torch.cat([hh, ww], -1).reshape(B, H * W, 2).contiguous()
+        if hit.is_cuda and torch.cuda.is_current_stream_capturing():
+            return hit                      # a tensor born inside a graph's private pool is never cached
+        if len(_ALL_PIXELS) >= 256:
+            _ALL_PIXELS.clear()
+        _ALL_PIXELS[key] = register_dense_index(hit)
+    return hit
+
+
 def grouping_entry(kind, kH, kW, K, flag_copy, stride_h, stride_w, dense_ok):
     """Entry point of a grouping call (kind "random" / "select").  dense_ok is the caller's half of the choice: every pixel
     of xyz1 is a centre in row-major order (and whatever else it wants of the LDS-tiled form); whether the window fits

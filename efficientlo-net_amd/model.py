@@ -70,9 +70,9 @@ def distinct_queue_streams(device, want, candidates=16, cycles=500_000):
 def _cached_tensors():
     """Every tensor the host-side caches hold right now (strided / all-pixel index grids, centre tables, decoded
     visiting orders): what a graph captured just before may point at."""
-    from . import pointnet_util
-    return list(model_util._sel_cache.values()) + list(pointnet_util._hw_cache.values()) + \
-        list(pointnet_util._centre_hw_cache.values()) + list(fused._DECODED.values()) + list(fused._HW.values())
+    from . import fused_conv, pointnet_util
+    return list(model_util._sel_cache.values()) + list(fused_conv._ALL_PIXELS.values()) + \
+        list(pointnet_util._centre_hw_cache.values()) + list(fused._DECODED.values())
 
 
 class Lane:

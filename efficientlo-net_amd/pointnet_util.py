@@ -18,12 +18,13 @@ accumulating GEMMs on row-slices of the same weight variable).
 `tf.random_shuffle(tf.range(KT))` becomes `random_shuffle(scope, tag, KT)` from
 the active PermSource (see perm.py): the caller owns the randomness.
 """
+import collections
 import os
 
 import torch
 
 from . import _ops, fused, tf_util, tuning
-from .fused_conv import fused_conv_random_k, fused_conv_select_k, register_dense_index
+from .fused_conv import all_pixels, fused_conv_random_k, fused_conv_select_k
 from .perm import random_shuffle
 
 
@@ -85,7 +86,6 @@ def warping_layers(xyz1, upsampled_flow):
     return xyz1 + upsampled_flow
 
 
-_hw_cache = {}
 _centre_hw_cache = {}
 
 
@@ -105,17 +105,7 @@ def _centre_hw(selected_idx):
 
 def get_hw_idx(B, H, W, device="cuda"):
     """utils/pointnet_util.py:23-30 -> (B, H*W, 2) int32, row-major (h, w) of every pixel."""
-    key = (B, H, W, str(device))
-    if key not in _hw_cache:
-        hh = torch.arange(H, dtype=torch.int32, device=device).view(1, H, 1, 1).expand(B, H, W, 1)
-        ww = torch.arange(W, dtype=torch.int32, device=device).view(1, 1, W, 1).expand(B, H, W, 1)
-        grid = torch.cat([hh, ww], -1).reshape(B, H * W, 2).contiguous()
-        if grid.is_cuda and torch.cuda.is_current_stream_capturing():
-            return grid                     # a tensor born inside a graph's private pool is never cached
-        if len(_hw_cache) >= 256:
-            _hw_cache.clear()
-        _hw_cache[key] = register_dense_index(grid)      # random-k calls with it take the LDS-tiled kernel
-    return _hw_cache[key]
+    return all_pixels(B, H, W, device)      # (cached and registered as a dense index: random-k calls with it take the LDS-tiled kernel)
 
 
 def _split_conv(parts, num_output_channels, scope, is_training, bn_decay, bn=True):
@@ -143,17 +133,24 @@ def _split_conv(parts, num_output_channels, scope, is_training, bn_decay, bn=Tru
     return y.reshape(lead + (num_output_channels,))
 
 
+CostVolume = collections.namedtuple("CostVolume", "cost side up_out")      # cost_volume's result where launches ride on it
+
+
 @_storage_boundary("points1_proj", "points2_proj")
 def cost_volume(warped_xyz1_proj, xyz2_proj, points1_proj, points2_proj, kernel_size1, kernel_size2, nsample,
                 nsample_q, distance, mlp1, mlp2, is_training, bn_decay, scope, bn=True, pooling='max', knn=True,
                 corr_func='elementwise_product', side_jobs=None, side_chain=False, upconv=None):
-    """Attentive cost volume, utils/pointnet_util.py:33-149.  Returns (B, H*W, mlp2[-1]).
-    `side_jobs` (fused inference path only): one or two set-conv jobs (fused.setconv keyword dicts) that only share
-    inputs with this cost volume; they run inside stage 1's launch and the call returns (cost, [(out, new_xyz), ...]).
-    `side_chain`: they ride only on the chain form of stage 1 (fused.cv_stage1); else the second element is None.
-    `upconv` (fused inference path only): a function of stage 1's side output (the list above, or None) that returns the two
-    set-upconv stage-2 MLP jobs of the level (up_conv_stage2_jobs) or None; they ride on stage 2's launch where they can
-    (fused.cv_stage2) and the call returns (cost, side output or None, [out_a, out_b] or None)."""
+    """Attentive cost volume, utils/pointnet_util.py:33-149.  Returns (B, H*W, mlp2[-1]) -- or, called with any of the three
+    arguments below (fused inference path only), CostVolume(cost, side, up_out).
+    `side_jobs`: one or two set-conv jobs (fused.setconv keyword dicts) that only share inputs with this cost volume; they run
+    inside stage 1's launch and `side` is [(out, new_xyz), ...].
+    `side_chain`: they ride only on the chain form of stage 1 (fused.cv_stage1); else `side` is None.
+    `upconv`: up_conv_stage2_jobs' leading arguments (up_a, up_b, fp_a, fp_b, w_cost) of the level whose set-upconv stage 1 are
+    the side jobs: where those rode, their stage-2 MLPs ride on stage 2's launch where they can (fused.cv_stage2) and `up_out`
+    is [out_a, out_b]; else None."""
+    fused_path = _fused_path(is_training) and nsample_q <= 32 and nsample <= 32
+    if not fused_path and (side_jobs or upconv is not None):
+        raise NotImplementedError("side_jobs / upconv ride on the fused cost-volume launches only")
     with tf_util.variable_scope(scope):
         B, H, W, _ = warped_xyz1_proj.shape
         N = H * W
@@ -164,7 +161,7 @@ def cost_volume(warped_xyz1_proj, xyz2_proj, points1_proj, points2_proj, kernel_
         C = points1.shape[-1]
         random_HW_q = random_shuffle(tf_util.scope_name(), "random_HW_q", kernel_size2[0] * kernel_size2[1], dev, kernel_size2)
         random_HW_p = random_shuffle(tf_util.scope_name(), "random_HW_p", kernel_size1[0] * kernel_size1[1], dev, kernel_size1)
-        if _fused_path(is_training) and nsample_q <= 32 and nsample <= 32:
+        if fused_path:
             # two launches for the whole operator: each fused kernel does its own grouping (select-k / random-k),
             # gather + encoding, the conv chain on the matrix cores and the masked softmax pooling
             if list(mlp1) != [128, 64, 64] or list(mlp2) != [128, 64]:
@@ -176,22 +173,19 @@ def cost_volume(warped_xyz1_proj, xyz2_proj, points1_proj, points2_proj, kernel_
                 P('CV_xyz', 10, 64),
                 P('sum_CV_0', 128, 128, row_order=list(range(64, 128)) + list(range(64))),      # kernel order [x | enc]
                 P('sum_CV_1', 128, 64),
-                group=fused.Grouping(random_HW_q, kernel_size2, 1000), K=nsample_q, side=side_jobs, side_chain=side_chain)   # :49-100
-            pi_feat1_new, side_out = stage1 if side_jobs else (stage1, None)
-            pi_feat1_new = pi_feat1_new.reshape(B, H, W, -1)
+                group=fused.Grouping(random_HW_q, kernel_size2, 1000), K=nsample_q, side=side_jobs or [], side_chain=side_chain)   # :49-100
             order = list(range(64 + C, 128 + C)) + list(range(64)) + list(range(64, 64 + C))   # [grouped | enc | feat1]
             layers2 = (P('sum_xyz_encoding', 10, 64), P('sum_cost_volume_0', 128 + C, 128, row_order=order),
                        P('sum_cost_volume_1', 128, 64))
-            up_jobs = upconv(side_out) if upconv is not None else None          # (its layers after this operator's)
-            cost = fused.cv_stage2(warped_xyz1_proj, points1_proj, pi_feat1_new, None, None, *layers2,
-                                   group=fused.Grouping(random_HW_p, kernel_size1, distance), K=nsample, side=up_jobs)   # :104-146
-            cost, up_out = cost if up_jobs else (cost, None)
-            if upconv is not None:
-                return cost, side_out, up_out
-            return (cost, side_out) if side_jobs else cost
-        if side_jobs or upconv is not None:
-            raise NotImplementedError("side_jobs / upconv ride on the fused cost-volume launches only")
-
+    if fused_path:
+        # (the set-upconvs' stage-2 layers after this operator's, under their own scopes: the caller's, outside this operator's)
+        up_jobs = up_conv_stage2_jobs(*upconv, stage1.side) if upconv and stage1.side else None
+        stage2 = fused.cv_stage2(warped_xyz1_proj, points1_proj, stage1.out.reshape(B, H, W, -1), None, None, *layers2,
+                                 group=fused.Grouping(random_HW_p, kernel_size1, distance), K=nsample, side=up_jobs or [])   # :104-146
+        if side_jobs or side_chain or upconv is not None:
+            return CostVolume(stage2.out, stage1.side, stage2.up_out)
+        return stage2.out
+    with tf_util.variable_scope(scope):
         # ---- stage 1: point -> patch in frame 2 (:47-100)
         idx_hw = get_hw_idx(B, H, W, dev)
         qi_idx, _, _, valid_mask = fused_conv_select_k(
@@ -298,71 +292,62 @@ def merge_branches(is_training, finest_points, level_points=0):
             level_points <= tuning.get("merge_level_points"))
 
 
-def flow_predictor_pair(call_a, call_b):
-    """Two flow_predictor calls with identical shapes (dicts of flow_predictor keyword arguments) in ONE launch
-    (pwclo_model.py:253-254: the embedding and the embedding-mask predictors of a refinement level)."""
-    specs = []
-    for c in (call_a, call_b):
-        with tf_util.variable_scope(c["scope"]):
-            parts = [p for p in (c["points_f1"], c["upsampled_feat"], c["cost_volume"]) if p is not None]
-            widths = [sum(p.shape[-1] for p in parts)] + list(c["mlp"])
-            layers = [fused.packed_layer('conv_predictor%d' % i, widths[i], widths[i + 1], bn=c.get("bn", True))
-                      for i in range(len(c["mlp"]))]
-        specs.append((parts, layers))
-    return fused.mlp_pair(specs[0][0], specs[0][1], specs[1][0], specs[1][1])
+LevelPlan = collections.namedtuple("LevelPlan", "stage1 upconv_ride")
 
 
-def up_conv_pair(call_a, call_b):
-    """Two up_conv calls that differ only in scope and feat2_proj (pwclo_model.py:247,250) in TWO launches
-    instead of four: paired set-conv stage (grouping + gather + MLP + max-pool) and paired stage-2 MLP."""
-    jobs, stage2 = [], []
-    for c in (call_a, call_b):
-        with tf_util.variable_scope(c["scope"]):
-            xyz1_proj, feat1_proj, feat2_proj = c["xyz1_proj"], c["feat1_proj"], c["feat2_proj"]
-            B, H, W, _ = xyz1_proj.shape
-            ks, mlp, mlp2 = c["kernel_size"], c["mlp"], c["mlp2"]
-            random_HW = random_shuffle(tf_util.scope_name(), "random_HW", ks[0] * ks[1], xyz1_proj.device, ks)
-            P = fused.packed_layer
-            w1 = [3 + feat2_proj.shape[-1]] + list(mlp)
-            jobs.append(dict(src_xyz=c["xyz2_proj"], src_feat=feat2_proj, idx=None, mask=None,
-                             layers=[P('up_1_%d' % j, w1[j], w1[j + 1],
-                                       row_order=fused.setconv_row_order(w1[0] - 3) if j == 0 else None)
-                                     for j in range(len(mlp))],
-                             xyz1_grid=xyz1_proj, K=c["nsample"],
-                             group=fused.Grouping(random_HW, ks, c["distance"], c["stride_h"], c["stride_w"])))
-            points1 = feat1_proj.reshape(B, H * W, -1)
-            w2 = [mlp[-1] + points1.shape[-1]] + list(mlp2)
-            stage2.append((points1, [P('up_2_%d' % i, w2[i], w2[i + 1]) for i in range(len(mlp2))]))
-    (up_a, _), (up_b, _) = fused.setconv_pair(jobs[0], jobs[1])
-    return fused.mlp_pair([up_a, stage2[0][0]], stage2[0][1], [up_b, stage2[1][0]], stage2[1][1])
+def level_plan(is_training, finest_points, level_points, sv_taken):
+    """The launch plan of a warp-refinement level on the fused inference path (fused_level), None off it.  Host only.
+    `stage1`, cost-volume stage 1 and the level's two set-upconv stage-1 jobs: "merged" (merge_branches: ONE tile-kernel launch),
+    "chain_pair" (tuning chain_pair, in the forwards small enough to merge at all: ONE heterogeneous launch where both are chain
+    forms, fused.cv_stage1(side_chain=True); from batch 4 on the GPU is full and two launches are faster, batch 4 23.3 -> 21.9 k
+    pairs/s, batch 8 fp16 28.0 -> 27.4 k: profiles/r05_batch1_regimes.txt) or "separate".  `upconv_ride`: set-upconv stage 2 rides
+    on cost-volume stage 2 (tuning upconv_ride: both are tile kernels where the sv ride is taken, `sv_taken`).
+    A 64 x 1800 pair at batch 1: l2 (228 centres) and l1 (904) merge, l0 (3600) takes the chain pair."""
+    if not _fused_path(is_training):
+        return None
+    if merge_branches(is_training, finest_points, level_points):
+        stage1 = "merged"
+    else:
+        stage1 = "chain_pair" if tuning.get("chain_pair") and finest_points <= tuning.get("merge_points") else "separate"
+    return LevelPlan(stage1, bool(sv_taken and tuning.get("sv_ride") and tuning.get("upconv_ride")))
 
 
-def up_conv_predict_pair(up_a, up_b, fp_a, fp_b):
-    """The two set-upconvs of a refinement level and the two flow predictors they feed (pwclo_model.py:247-254) in
-    TWO launches: the paired set-conv stage, then ONE launch that runs each up_conv's stage-2 MLP and, on its
-    output, the predictor's MLP (flow_predictor's concat [points_f1, upsampled_feat, cost_volume] with
-    upsampled_feat coming straight from the tile).  up_x / fp_x: the keyword dicts of up_conv_pair /
-    flow_predictor_pair; fp_x's upsampled_feat is up_x's output.  Returns (up_out_a, predictor_a, up_out_b, predictor_b)."""
-    jobs = up_conv_stage1_jobs(up_a, up_b)
-    (up_a_pooled, _), (up_b_pooled, _) = fused.setconv_pair(jobs[0], jobs[1])
-    return up_conv_predict_finish(up_a, up_b, fp_a, fp_b, up_a_pooled, up_b_pooled)
+def fused_level(plan, level_cost_volume, up_w, up_c, fp_w, fp_c, clear=None, sv=None):
+    """A warp-refinement level on the fused inference path (pwclo_model.py:242-254) under `plan` (level_plan): the cost volume, the
+    embedding / embedding-mask set-upconvs and the flow predictors they feed, the twins as PAIRED launches.
+    level_cost_volume(**riders): the level's cost_volume call; up_x: up_conv's keyword arguments without is_training / bn_decay;
+    fp_x: flow_predictor's points_f1, mlp, scope.  `clear`, `sv`: as for up_conv_predict_finish.
+    Returns (w_up_sample, weight, cost_up_sample, predict)."""
+    jobs = up_conv_stage1_jobs(up_w, up_c)                 # (they only share inputs with the cost volume: :242-250)
+    if plan.stage1 == "separate":
+        got = CostVolume(level_cost_volume(), None, None)
+    else:
+        got = level_cost_volume(side_jobs=jobs, side_chain=plan.stage1 == "chain_pair",
+                                upconv=(up_w, up_c, fp_w, fp_c, 64) if plan.upconv_ride else None)
+    (up_w_pooled, _), (up_c_pooled, _) = got.side if got.side is not None else fused.setconv_pair(jobs[0], jobs[1])
+    return up_conv_predict_finish(up_w, up_c, dict(fp_w, cost_volume=got.cost), dict(fp_c, cost_volume=got.cost),
+                                  up_w_pooled, up_c_pooled, clear=clear, sv=sv, up_out=got.up_out)
 
 
-def up_conv_stage1_jobs(up_a, up_b):
-    """Stage 1 (grouping + gather + MLP + max-pool, pointnet_util.py:272-298) of the two set-upconvs of a level as two
-    fused.setconv job dicts: for fused.setconv_pair, or as `side_jobs` of the level's cost volume (they only share
+def _setconv_layers(prefix, cin, mlp, bn=True):
+    """The packed MLP of a set-conv over [xyz difference (3) | cin features] rows, layers '<prefix>0', '<prefix>1', ... of the
+    active scope; the first in the kernel's column order (fused.setconv_row_order)."""
+    widths = [3 + cin] + list(mlp)
+    return [fused.packed_layer('%s%d' % (prefix, i), widths[i], widths[i + 1], bn=bn,
+                               row_order=fused.setconv_row_order(cin) if i == 0 else None) for i in range(len(mlp))]
+
+
+def up_conv_stage1_jobs(*ups):
+    """Stage 1 (grouping + gather + MLP + max-pool, pointnet_util.py:272-298) of a set-upconv -- of the two of a level -- as
+    fused.setconv job dicts: for fused.setconv / setconv_pair, or as `side_jobs` of the level's cost volume (they only share
     inputs with it, so they can ride on its first launch)."""
     jobs = []
-    for up in (up_a, up_b):
-        P = fused.packed_layer
+    for up in ups:
         with tf_util.variable_scope(up["scope"]):
-            feat2_proj, ks, mlp = up["feat2_proj"], up["kernel_size"], up["mlp"]
+            feat2_proj, ks = up["feat2_proj"], up["kernel_size"]
             random_HW = random_shuffle(tf_util.scope_name(), "random_HW", ks[0] * ks[1], up["xyz1_proj"].device, ks)
-            w1 = [3 + feat2_proj.shape[-1]] + list(mlp)
             jobs.append(dict(src_xyz=up["xyz2_proj"], src_feat=feat2_proj, idx=None, mask=None,
-                             layers=[P('up_1_%d' % j, w1[j], w1[j + 1],
-                                       row_order=fused.setconv_row_order(w1[0] - 3) if j == 0 else None)
-                                     for j in range(len(mlp))],
+                             layers=_setconv_layers('up_1_', feat2_proj.shape[-1], up["mlp"]),
                              xyz1_grid=up["xyz1_proj"], K=up["nsample"],
                              group=fused.Grouping(random_HW, ks, up["distance"], up["stride_h"], up["stride_w"])))
     return jobs
@@ -393,13 +378,14 @@ def _predictor(up, fp, w_after=None):
                                for i in range(len(fp["mlp"]))]
 
 
-def up_conv_stage2_jobs(up_a, up_b, fp_a, fp_b, up_a_pooled, up_b_pooled, w_cost):
-    """Stage 2 of the two set-upconvs of a level ([pooled | points1] -> mlp2) as fused.mlp job dicts (sources, layers): for the
-    level's cost-volume stage 2 to carry (cost_volume(upconv=...)): they only read stage 1's output, so they leave the
-    predictors' critical path.  The predictors' layers (fp_x without cost_volume; w_cost: its width) are made here too, in
-    up_conv_predict_finish's order: a fresh store creates the same variables."""
+def up_conv_stage2_jobs(up_a, up_b, fp_a, fp_b, w_cost, side):
+    """Stage 2 of the two set-upconvs of a level ([pooled | points1] -> mlp2; side: [(pooled, _), (pooled, _)], their stage 1 as
+    it rode on the cost volume's) as fused.mlp job dicts (sources, layers): for the level's cost-volume stage 2 to carry
+    (cost_volume(upconv=...)): they only read stage 1's output, so they leave the predictors' critical path.  The predictors'
+    layers (fp_x without cost_volume; w_cost: its width) are made here too, in up_conv_predict_finish's order: a fresh store
+    creates the same variables."""
     jobs = []
-    for up, fp, pooled in ((up_a, fp_a, up_a_pooled), (up_b, fp_b, up_b_pooled)):
+    for up, fp, (pooled, _) in ((up_a, fp_a, side[0]), (up_b, fp_b, side[1])):
         points1, layers = _up_stage2(up)
         _predictor(up, fp, w_after=w_cost)
         jobs.append(dict(sources=[pooled, points1], layers=layers))
@@ -407,7 +393,10 @@ def up_conv_stage2_jobs(up_a, up_b, fp_a, fp_b, up_a_pooled, up_b_pooled, w_cost
 
 
 def up_conv_predict_finish(up_a, up_b, fp_a, fp_b, up_a_pooled, up_b_pooled, clear=None, sv=None, up_out=None):
-    """Stage 2 of both set-upconvs and the two flow predictors they feed, in ONE launch (see up_conv_predict_pair).
+    """Stage 2 of both set-upconvs and the two flow predictors they feed (pwclo_model.py:247-254), in ONE launch: each up_conv's
+    stage-2 MLP and, on its output, the predictor's MLP (flow_predictor's concat [points_f1, upsampled_feat, cost_volume] with
+    upsampled_feat coming straight from the tile).  up_x / fp_x: as for fused_level, fp_x with its cost_volume; up_x_pooled: the
+    set-upconvs' stage-1 outputs.  Returns (up_out_a, predictor_a, up_out_b, predictor_b).
     `sv`: an _ops.SvPartials: predictor a's output are softmax_valid's logits, predictor b's its features (fused.mlp2_pair).
     `up_out`: [out_a, out_b] when the set-upconvs' stage 2 already ran (on the cost volume's stage-2 launch,
     up_conv_stage2_jobs): then the launch runs the predictors alone on [out | points_f1 | cost] (fused.mlp_pair) -- the same
@@ -434,10 +423,7 @@ def down_conv_job(xyz_proj, points_proj, selected_idx, K_sample, kernel_size, di
     finish(out, new_xyz) gives down_conv's return value."""
     with tf_util.variable_scope(scope):
         random_HW = random_shuffle(tf_util.scope_name(), "random_HW", kernel_size[0] * kernel_size[1], xyz_proj.device, kernel_size)
-        widths = [3 + points_proj.shape[-1]] + list(mlp)
-        layers = [fused.packed_layer('conv%d' % i, widths[i], widths[i + 1], bn=bn,
-                                     row_order=fused.setconv_row_order(widths[0] - 3) if i == 0 else None)
-                  for i in range(len(mlp))]
+        layers = _setconv_layers('conv', points_proj.shape[-1], mlp, bn)
     job = dict(src_xyz=xyz_proj, src_feat=points_proj, idx=None, mask=None, layers=layers, xyz1_grid=xyz_proj,
                centre_hw=_centre_hw(selected_idx), K=K_sample, group=fused.Grouping(random_HW, kernel_size, distance))
     return job, lambda out, new_xyz: (out, new_xyz.reshape(selected_idx.shape[:-1] + (3,)))
@@ -449,6 +435,12 @@ def down_conv(xyz_proj, points_proj, selected_idx, K_sample, kernel_size, distan
     """Set-conv, utils/pointnet_util.py:179-250.  Returns ((B, n, mlp[-1]), new_xyz_proj (B,H',W',3))."""
     if use_nchw or pooling != 'max' or mlp2 is not None:
         raise NotImplementedError("the model uses NHWC, max pooling and mlp2=None (pwclo_model.py:126-177)")
+    if _fused_path(is_training) and len(mlp) <= 3 and K_sample <= 32:
+        # ONE launch: random-k grouping, gather, centre-subtract, MLP on the matrix cores, masked max-pool.
+        # The centre is xyz_proj[b, h, w] (selected_idx's batch column is the batch index, as
+        # get_selected_idx builds it)                                                               :197-230
+        job, finish = down_conv_job(xyz_proj, points_proj, selected_idx, K_sample, kernel_size, distance, mlp, scope, bn)
+        return finish(*fused.setconv(**job))
     with tf_util.variable_scope(scope):
         B, H, W, _ = xyz_proj.shape
         idx_n2 = selected_idx.reshape(B, -1, 3)
@@ -456,18 +448,6 @@ def down_conv(xyz_proj, points_proj, selected_idx, K_sample, kernel_size, distan
         dev = xyz_proj.device
         random_HW = random_shuffle(tf_util.scope_name(), "random_HW", kernel_size[0] * kernel_size[1], dev, kernel_size)
         centre_hw = _centre_hw(selected_idx)
-        if _fused_path(is_training) and len(mlp) <= 3 and K_sample <= 32:
-            # ONE launch: random-k grouping, gather, centre-subtract, MLP on the matrix cores, masked max-pool.
-            # The centre is xyz_proj[b, h, w] (selected_idx's batch column is the batch index, as
-            # get_selected_idx builds it)                                                           :197-230
-            widths = [3 + points_proj.shape[-1]] + list(mlp)
-            layers = [fused.packed_layer('conv%d' % i, widths[i], widths[i + 1], bn=bn,
-                                         row_order=fused.setconv_row_order(widths[0] - 3) if i == 0 else None)
-                      for i in range(len(mlp))]
-            out, new_xyz = fused.setconv(xyz_proj, points_proj, None, None, layers, xyz1_grid=xyz_proj,
-                                         centre_hw=centre_hw, K=K_sample,
-                                         group=fused.Grouping(random_HW, kernel_size, distance))
-            return out, new_xyz.reshape(selected_idx.shape[:-1] + (3,))
         sel, _, _, valid_mask = fused_conv_random_k(
             xyz_proj, xyz_proj, centre_hw, random_HW, H, W, n_sampled, kernel_size[0],
             kernel_size[1], K_sample, flag_copy=0, distance=distance, stride_h=1, stride_w=1, want_valid=False)  # :197-199
@@ -486,6 +466,13 @@ def down_conv(xyz_proj, points_proj, selected_idx, K_sample, kernel_size, distan
 def up_conv(xyz1_proj, xyz2_proj, feat1_proj, feat2_proj, kernel_size, stride_h, stride_w, nsample, distance, mlp,
             mlp2, is_training, scope, bn_decay=None, bn=True, pooling='max', radius=None, knn=True):
     """Set-upconv (embedding and embedding-mask up-convolution), utils/pointnet_util.py:254-316."""
+    if _fused_path(is_training) and len(mlp) <= 3 and len(mlp2) <= 3 and nsample <= 32:
+        up = dict(xyz1_proj=xyz1_proj, xyz2_proj=xyz2_proj, feat1_proj=feat1_proj, feat2_proj=feat2_proj, kernel_size=kernel_size,
+                  stride_h=stride_h, stride_w=stride_w, nsample=nsample, distance=distance, mlp=mlp, mlp2=mlp2, scope=scope)
+        (job,) = up_conv_stage1_jobs(up)
+        up_feat, _ = fused.setconv(**job)                                                         # :272-298
+        points1, layers = _up_stage2(up)
+        return fused.mlp([up_feat, points1], layers)                                              # :303-311
     with tf_util.variable_scope(scope):
         B, H, W, _ = xyz1_proj.shape
         N = H * W
@@ -493,17 +480,6 @@ def up_conv(xyz1_proj, xyz2_proj, feat1_proj, feat2_proj, kernel_size, stride_h,
         xyz1 = xyz1_proj.reshape(B, N, 3)
         points1 = feat1_proj.reshape(B, N, -1)
         random_HW = random_shuffle(tf_util.scope_name(), "random_HW", kernel_size[0] * kernel_size[1], dev, kernel_size)
-        if _fused_path(is_training) and len(mlp) <= 3 and len(mlp2) <= 3 and nsample <= 32:
-            P = fused.packed_layer
-            w1 = [3 + feat2_proj.shape[-1]] + list(mlp)
-            up_feat, _ = fused.setconv(xyz2_proj, feat2_proj, None, None,
-                                       [P('up_1_%d' % j, w1[j], w1[j + 1],
-                                          row_order=fused.setconv_row_order(w1[0] - 3) if j == 0 else None)
-                                        for j in range(len(mlp))],
-                                       xyz1_grid=xyz1_proj, K=nsample,
-                                       group=fused.Grouping(random_HW, kernel_size, distance, stride_h, stride_w))  # :272-298
-            w2 = [mlp[-1] + points1.shape[-1]] + list(mlp2)
-            return fused.mlp([up_feat, points1], [P('up_2_%d' % i, w2[i], w2[i + 1]) for i in range(len(mlp2))])  # :303-311
         idx_hw = get_hw_idx(B, H, W, dev)
         sel, _, _, valid_mask = fused_conv_random_k(
             xyz1_proj, xyz2_proj, idx_hw, random_HW, H, W, N, kernel_size[0], kernel_size[1], nsample,

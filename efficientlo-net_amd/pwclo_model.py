@@ -20,8 +20,8 @@ import torch
 from . import _ops, fused, tf_util, tuning
 from .model_util import (PreProcess, ProjectPC2SphericalRing, input_stage, preprocess_gt, get_selected_idx, inv_q, mul_point_q, mul_q_point,
                          softmax_valid, warp_and_project)
-from .pointnet_util import (cost_volume, down_conv, down_conv_job, flow_predictor, fused_pairs_available, merge_branches,
-                            up_conv, up_conv_predict_finish, up_conv_stage1_jobs, up_conv_stage2_jobs)
+from .pointnet_util import (cost_volume, down_conv, down_conv_job, flow_predictor, fused_level, fused_pairs_available, level_plan,
+                            merge_branches, up_conv)
 
 Down_conv_dis = [0.5, 3.0, 6.0, 12.0]       # pwclo_model.py:38
 Up_conv_dis = [3.0, 6.0, 9.0]               # :39
@@ -288,7 +288,7 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
                                    bn=True, pooling='max', knn=True, corr_func='concat',
                                    side_jobs=[job for job, _ in deferred] or None)
     if deferred:                                      # the layer-3 set-conv(s) that rode on the cost volume's first launch
-        l2_points_f1_new, side = l2_points_f1_new
+        l2_points_f1_new, side, _ = l2_points_f1_new
         for f, ((_job, finish), (out, new_xyz)) in enumerate(zip(deferred, side)):
             l3_points, l3_xyz_proj = finish(out, new_xyz)
             if len(deferred) == 1 and l3_points.shape[0] == 2 * batch_size:          # the 2B Siamese batch: frame 1 | frame 2
@@ -357,8 +357,7 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
                                distance=Cost_volume_dis[level], mlp1=[128, 64, 64], mlp2=[128, 64],
                                is_training=is_training, bn_decay=bn_decay, scope='flow_embedding_l%d' % level,
                                bn=True, pooling='max', knn=True, corr_func='concat', side_jobs=side_jobs,
-                               **({"side_chain": True} if side_chain else {}),
-                               **({"upconv": upconv} if upconv is not None else {}))                     # :242
+                               side_chain=side_chain, upconv=upconv)                                # :242
 
         def branch_up(kind, coarse_feat_proj):
             return up_conv(xyz_warp_proj_f1, coarse_xyz_proj, points_warp_proj_f1, coarse_feat_proj,
@@ -369,46 +368,18 @@ def get_model_from_projection(xyz_f1_input_proj, xyz_f2_input_proj, is_training,
 
         if fused_pairs_available(is_training):
             # inference: the embedding / embedding-mask twins of a level run as PAIRED launches (same shapes,
-            # different weights): 2 + 1 launches instead of 4 + 2
+            # different weights), on the schedule pointnet_util.level_plan picks for the level's size
             up = dict(xyz1_proj=xyz_warp_proj_f1, xyz2_proj=coarse_xyz_proj, feat1_proj=points_warp_proj_f1,
                       kernel_size=[7, 15], stride_h=stride_h_list[g + 1], stride_w=stride_w_list[g + 1], nsample=8,
                       distance=Up_conv_dis[level], mlp=[128, 64], mlp2=[128, 64])
             up_w = dict(up, feat2_proj=coarse_w_proj, scope='up_sa_layer_layer_l%dw' % level)
             up_c = dict(up, feat2_proj=coarse_predict_proj, scope='up_sa_layer_layer_l%dcostvolume' % level)
-            # the cost volume and stage 1 of the two set-upconvs only share inputs (:242-250): while the GPU is underfilled
-            # ONE launch runs cost-volume stage 1 and both set-conv jobs (both branches in flight together, one launch
-            # boundary less); a full GPU takes them as two launches
-            jobs = up_conv_stage1_jobs(up_w, up_c)
             fp = dict(points_f1=points_warp_f1, mlp=[128, 64])
             fp_w, fp_c = dict(fp, scope='l%d_w_predict' % level), dict(fp, scope='l%d_costvolume_predict' % level)
             sv = sv_ride(xyz_warp_f1)
-            # set-upconv stage 2 rides on the cost volume's stage-2 launch (tuning upconv_ride: both tile kernels, where the
-            # sv ride is taken), so the predictor launch behind it runs its own two layers only; else it shares that launch
-            upconv = None
-            if sv is not None and tuning.get("upconv_ride"):
-                upconv = tf_util.in_current_scope(
-                    lambda side: None if side is None else up_conv_stage2_jobs(up_w, up_c, fp_w, fp_c, side[0][0], side[1][0], 64))
-            up_out = None
-            if merge_branches(is_training, finest_points, batch_size * out_h_list[g] * out_w_list[g]):
-                got = branch_cost(side_jobs=jobs, upconv=upconv)
-                cost, ((up_w_pooled, _), (up_c_pooled, _)) = got[:2]
-                up_out = got[2] if upconv is not None else None
-            else:
-                # ... and where both are register-resident chain launches (a larger level below the throughput batch), the
-                # chain kernels' heterogeneous launch (tuning chain_pair); the select-k pre-pass stays a launch of its own
-                # (only in the forwards small enough to merge at all: from batch 4 on the GPU is full and the two launches are faster,
-                #  batch 4 23.3 -> 21.9 k pairs/s, batch 8 fp16 28.0 -> 27.4 k: profiles/r05_batch1_regimes.txt)
-                pair = tuning.get("chain_pair") and finest_points <= tuning.get("merge_points")
-                if pair:
-                    got = branch_cost(side_jobs=jobs, side_chain=True, upconv=upconv)
-                    cost, sides = got[:2]
-                    up_out = got[2] if upconv is not None else None
-                else:
-                    cost, sides = branch_cost(), None
-                (up_w_pooled, _), (up_c_pooled, _) = sides if sides is not None else fused.setconv_pair(jobs[0], jobs[1])
-            w_up_sample, weight, cost_up_sample, predict = up_conv_predict_finish(
-                up_w, up_c, dict(fp_w, cost_volume=cost), dict(fp_c, cost_volume=cost),
-                up_w_pooled, up_c_pooled, clear=next_buffers if sv is not None else None, sv=sv, up_out=up_out)
+            plan = level_plan(is_training, finest_points, batch_size * out_h_list[g] * out_w_list[g], sv is not None)
+            w_up_sample, weight, cost_up_sample, predict = fused_level(
+                plan, branch_cost, up_w, up_c, fp_w, fp_c, clear=next_buffers if sv is not None else None, sv=sv)
         else:
             # the cost volume and the two set-upconvs only share inputs: optional concurrent branches
             cost, w_up_sample, cost_up_sample = _parallel([branch_cost, lambda: branch_up('w', coarse_w_proj),

@@ -150,21 +150,6 @@ def variable_scope(name):
     return get_store().variable_scope(name)
 
 
-def in_current_scope(fn):
-    """`fn`, called later from inside other variable scopes (a callback an operator runs), under the scope stack active NOW:
-    the variables it creates keep the names its author gave them."""
-    store = get_store()
-    names = list(store._scope)
-
-    def call(*args, **kw):
-        saved, store._scope = store._scope, list(names)
-        try:
-            return fn(*args, **kw)
-        finally:
-            store._scope = saved
-    return call
-
-
 def scope_name():
     """Full name of the active variable scope, e.g. 'sa1/layer0'."""
     return "/".join(get_store()._scope)

@@ -270,10 +270,10 @@ def test_the_heterogeneous_chain_launch_matches_the_oracle_elementwise(B, storag
     def forward():
         jobs = pu.up_conv_stage1_jobs(ups[0], ups[1])
         with fused.recording() as calls:
-            out, sides = pu.cost_volume(t(f1), t(f2), d(fa), d(fb), kernel_size1=[3, 5], kernel_size2=ks2, nsample=4, nsample_q=Kq,
-                                        distance=dist, mlp1=[128, 64, 64], mlp2=[128, 64], is_training=False, bn_decay=None,
-                                        scope='flow_embedding_c', bn=True, pooling='max', knn=True, corr_func='concat',
-                                        side_jobs=jobs, side_chain=True)
+            out, sides, _ = pu.cost_volume(t(f1), t(f2), d(fa), d(fb), kernel_size1=[3, 5], kernel_size2=ks2, nsample=4, nsample_q=Kq,
+                                           distance=dist, mlp1=[128, 64, 64], mlp2=[128, 64], is_training=False, bn_decay=None,
+                                           scope='flow_embedding_c', bn=True, pooling='max', knn=True, corr_func='concat',
+                                           side_jobs=jobs, side_chain=True)
         assert sides is not None, "the chain-pair form was not taken"
         return out, [c for c in calls if c[0] == 2][0][1][2], sides[0][0], sides[1][0]
     lib.check(lib.lib().elo_debug_chain_pair_launches(ctypes.byref(n_pair), 1))

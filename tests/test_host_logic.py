@@ -267,6 +267,33 @@ def test_the_regime_switches_of_a_forward_are_tuning_values():
     assert tuning.digest() == before
 
 
+def test_the_level_plan_is_one_host_decision_over_five_tuning_fields():
+    """pointnet_util.level_plan(is_training, finest_points, level_points, sv_taken): which of {merged, chain pair, separate} a refinement
+    level's first launches take and whether set-upconv stage 2 rides on cost-volume stage 2 -- the answers the docstrings state for a
+    64 x 1800 pair, and every tuning field it reads flips the answer it governs."""
+    tuning, pu = load_pkg("tuning"), load_pkg("pointnet_util")
+    with tuning.override(fused=True):
+        plan = lambda B, n, sv=True: pu.level_plan(False, B * 3600, B * n, sv)
+        # batch 1: l2 (228 centres) and l1 (904) merge, l0 (3600) does not and takes the chain pair; stage 2 carries the set-upconvs
+        assert [plan(1, n) for n in (228, 904, 3600)] == [("merged", True), ("merged", True), ("chain_pair", True)]
+        assert [plan(2, n).stage1 for n in (228, 904, 3600)] == ["merged", "merged", "chain_pair"]
+        # from batch 3 on nothing merges (more than merge_points centres at l0): two launches at every level
+        assert all(plan(B, n) == ("separate", True) for B in (3, 4, 8) for n in (228, 904, 3600))
+        # training (and the per-operator path) has no fused plan
+        assert pu.level_plan(True, 3600, 228, True) is None
+        with tuning.override(fused=False):
+            assert pu.level_plan(False, 3600, 228, True) is None
+        # where the softmax_valid ride is not taken the launch behind stage 2 is no tile kernel: nothing rides
+        assert plan(1, 228, sv=False) == ("merged", False)
+        for fields, n, want in ((dict(merge_points=3599), 228, ("separate", True)), (dict(merge_level_points=227), 228, ("chain_pair", True)),
+                                (dict(merge_level_points=3600), 3600, ("merged", True)), (dict(chain_pair=False), 3600, ("separate", True)),
+                                (dict(upconv_ride=False), 228, ("merged", False)), (dict(sv_ride=False), 228, ("merged", False))):
+            assert plan(1, n) != want
+            with tuning.override(**fields):
+                assert plan(1, n) == want, fields
+        assert [pu.merge_branches(False, 3600, n) for n in (228, 904, 3600)] == [plan(1, n).stage1 == "merged" for n in (228, 904, 3600)]
+
+
 def test_kitti_density_profile_of_the_synthetic_scene():
     """synth.range_image(profile="kitti"): the density of a projected HDL-64 scan after the 35 m crop (kitti_dataset.py:38-103,
     model_util.py:380-383) -- about half of the grid valid, whole dead beam rows, a sector without returns -- and frame_pair's starved
