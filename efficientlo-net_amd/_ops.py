@@ -3,9 +3,10 @@ backward passes (csrc/elo_backward.hip).  Every public operator here is ONE impl
 input requires grad (training) the call goes through a torch.autograd.Function whose forward is that same kernel and
 whose backward is the matching `elo_*_backward` kernel -- there is no second (torch) implementation to fall onto and
 nothing here looks at the global autograd mode.  Shapes are validated in C as well.  No CPU fallback: CPU tensors raise."""
-import numpy as np
-
+import collections
 import ctypes
+
+import numpy as np
 
 import torch
 
@@ -596,6 +597,64 @@ def beam_table(table, H, device):
     return torch.from_numpy(host).to(device)
 
 
+def _on_device(table):
+    return isinstance(table, torch.Tensor) and table.is_cuda
+
+
+def bind_sensor(sensor, device, beam_elev=None, H=None):
+    """For whoever OWNS a beam table -- a net, a tracker, a trainer: (the resolved Sensor, its table as a float32 tensor on `device`
+    or None).  `beam_elev` (None: the sensor's own table) and `H` (None: that table's length) as beam_table() takes them; a tensor
+    that already lives on a GPU is handed back as it is.  The launches the owner issues read the table when they RUN, and a graph
+    that records them holds its pointer: the owner keeps the tensor for as long as either can."""
+    sensor = _sensor.resolve(sensor)
+    if beam_elev is None and sensor.beam_elevations_deg is not None:
+        beam_elev, H = sensor, len(sensor.beam_elevations_deg) if H is None else H
+    if beam_elev is not None and not _on_device(beam_elev):
+        beam_elev = beam_table(beam_elev, H, device)
+    return sensor, beam_elev
+
+
+CellRule = collections.namedtuple("CellRule", "az_res vert_res vert_off beam_elev sensor")
+
+
+def cell_rule(H, W, device, sensor=None, beam_elev=None, whose="cloud's", max_beams=None, one_row=None):
+    """The rule that gives a point its cell of an (H,W) image, resolved for ONE call: the three constants of the row formula
+    (projection_constants) at the resolved `sensor`, and the beam table the launch reads -- a float32 tensor on `device` -- or None
+    for the formula alone.  `beam_elev` None: the sensor's table, if it has one.  A tensor on a GPU is used as it is -- its owner
+    (bind_sensor) validated its values and keeps it alive -- once its device (the `whose` device), dtype, layout and length are
+    checked; anything else is validated and uploaded here, which a graph capture cannot record: refused while one is open.
+    `max_beams`: an explicit table of more rows is refused here and not by the library; `one_row`: (vert_res, vert_off) of an
+    image of ONE row, where the formula has no resolution."""
+    sensor = _sensor.resolve(sensor)
+    if isinstance(device, str):
+        device = torch.device(device)
+    if beam_elev is not None and max_beams is not None and H > max_beams:
+        raise L.EloError("a beam table has at most %d beams (H = %d)" % (max_beams, H))
+    if beam_elev is None and sensor.beam_elevations_deg is not None:
+        beam_elev = sensor
+    if _on_device(beam_elev):
+        if beam_elev.device != device or beam_elev.dtype != torch.float32 or not beam_elev.is_contiguous() or beam_elev.numel() != H:
+            raise L.EloError("a device beam table is a contiguous float32 tensor of H = %d entries on the %s device" % (H, whose))
+    elif beam_elev is not None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
+        beam_elev = beam_table(beam_elev, H, device)
+    if H == 1 and one_row is not None:
+        return CellRule(projection_constants(2, W, sensor)[0], *one_row, beam_elev, sensor)
+    return CellRule(*projection_constants(H, W, sensor), beam_elev, sensor)
+
+
+def _check_tensors(given):
+    """Each (name, tensor, dtype) of `given` is a tensor of that dtype (TypeError) that the launch can use in place (EloError)."""
+    for name, t, dtype in given:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s is a tensor (got %r)" % (name, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError("%s is %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
+        if not t.is_contiguous():
+            raise L.EloError("%s must be contiguous: the launch uses it in place" % name)
+
+
 def _motion_dev(motion, B, dev, name):
     """(B,7) float32 on `dev`: a contiguous float32 tensor that already lives there is passed through (same memory: its pointer is
     what the launch -- and a graph that records it -- reads), anything else is converted and copied (not inside a capture)."""
@@ -657,43 +716,27 @@ def input_stage(cloud, T_trans, aug_frame, H, W, crop_xy=None, sensor=None, beam
         motion = _motion_dev(motion, B, dev, "motion")
         if motion2 is not None:
             motion2 = _motion_dev(motion2, B, dev, "motion2")
-    sensor = _sensor.resolve(sensor)
-    if crop_xy is None:
-        crop_xy = sensor.crop_xy
+    rule = cell_rule(H, W, dev, sensor, beam_elev)
+    crop = float(rule.sensor.crop_xy if crop_xy is None else crop_xy)
     if T_trans is not None:
         (T_trans,) = _f32(T_trans.reshape(B, 4, 4))
         aug = _aug_frame_dev(aug_frame, B, dev)
     points = torch.empty((2 * B, N, 3), dtype=torch.float32, device=dev)
     out_xyz = torch.empty((2 * B, H, W, 3), dtype=torch.float32, device=dev)
     scratch = torch.empty((2 * B * H * W + 4 * 2 * B + 2 * 2 * B * N,), dtype=torch.int32, device=dev)
-    az, vres, voff = projection_constants(H, W, sensor)
+    az, vres, voff, table = rule.az_res, rule.vert_res, rule.vert_off, _ptr(rule.beam_elev)
     tail = (cloud.data_ptr(), T_trans.data_ptr() if T_trans is not None else None,
             aug.data_ptr() if T_trans is not None else None, points.data_ptr(), out_xyz.data_ptr(), scratch.data_ptr())
-    if sweep is not None:
-        skew = (motion.data_ptr(), motion2.data_ptr() if motion2 is not None else None, 1 if motion_is_pose else 0,
-                L.PHASE_AZIMUTH if sweep.phase == "azimuth" else L.PHASE_CHANNEL, 0 if sweep.phase == "azimuth" else sweep.phase,
-                sweep.phase_ref)
-    if beam_elev is None and sensor.beam_elevations_deg is None:
-        if sweep is not None:
-            a = L.InputStageDeskewArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), *tail, None, *skew)
-            L.call("elo_input_stage_deskew", a, out_xyz)
-            return points, out_xyz
-        a = L.InputStageArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), *tail)
-        L.call("elo_input_stage", a, out_xyz)
-        return points, out_xyz
-    if isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda:
-        if beam_elev.device != dev or beam_elev.dtype != torch.float32 or not beam_elev.is_contiguous() or beam_elev.numel() != H:
-            raise L.EloError("a device beam table is a contiguous float32 tensor of H = %d entries on the cloud's device" % H)
+    if sweep is not None:                                    # (with or without a table: the de-skewing entry takes both row rules)
+        azimuth = sweep.phase == "azimuth"
+        entry, a = "elo_input_stage_deskew", L.InputStageDeskewArgs(
+            B, N, S, H, W, az, vres, voff, crop, *tail, table, motion.data_ptr(), _ptr(motion2), 1 if motion_is_pose else 0,
+            L.PHASE_AZIMUTH if azimuth else L.PHASE_CHANNEL, 0 if azimuth else sweep.phase, sweep.phase_ref)
+    elif table is None:
+        entry, a = "elo_input_stage", L.InputStageArgs(B, N, S, H, W, az, vres, voff, crop, *tail)
     else:
-        if torch.cuda.is_current_stream_capturing():
-            raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
-        beam_elev = beam_table(beam_elev if beam_elev is not None else sensor, H, dev)
-    if sweep is not None:
-        a = L.InputStageDeskewArgs(B, N, S, H, W, az, vres, voff, float(crop_xy), *tail, beam_elev.data_ptr(), *skew)
-        L.call("elo_input_stage_deskew", a, out_xyz)
-        return points, out_xyz
-    a = L.InputStageBeamsArgs(B, N, S, H, W, az, float(crop_xy), *tail, beam_elev.data_ptr())
-    L.call("elo_input_stage_beams", a, out_xyz)
+        entry, a = "elo_input_stage_beams", L.InputStageBeamsArgs(B, N, S, H, W, az, crop, *tail, table)
+    L.call(entry, a, out_xyz)
     return points, out_xyz
 
 
@@ -703,10 +746,11 @@ class PoseFitResult:
     stats block: count (terms, an exact integer in float32), cost = sum w r^2, rms = sqrt(cost / sum w), status (0: fine; bits
     _lib.FIT_FEW / FIT_SINGULAR: a step was refused and the pose is the input's; FIT_FEW_FINAL: the reported evaluation has fewer
     than min_count terms).  The tensors are the launch's own outputs: valid once its stream has been synchronised or waited on."""
-    __slots__ = ("pose", "info", "grad", "stats", "scratch")
+    __slots__ = ("pose", "info", "grad", "stats", "scratch", "keep")
 
-    def __init__(self, pose, info, grad, stats, scratch=None):
+    def __init__(self, pose, info, grad, stats, scratch=None, keep=None):
         self.pose, self.info, self.grad, self.stats, self.scratch = pose, info, grad, stats, scratch
+        self.keep = keep                  # the beam table the launches read when they run: it lives as long as the result
 
     count = property(lambda self: self.stats[:, 0])
     cost = property(lambda self: self.stats[:, 1])
@@ -728,17 +772,12 @@ class PoseFitResult:
         return out
 
 
-def _check_pose_fit(xyz1, xyz2, pose7, fit, beam_elev):
-    """What the host can refuse about a pose fit without a GPU or the library: the value, shapes, dtypes, layout, devices."""
+def _check_pose_fit(xyz1, xyz2, pose7, fit):
+    """What the host can refuse about a pose fit without a GPU or the library: the value, shapes, dtypes, layout, devices (the
+    beam table: cell_rule)."""
     if not isinstance(fit, _sensor.PoseFit):
         raise TypeError("fit is a PoseFit (got %r)" % (type(fit).__name__,))
-    for name, t in (("xyz1", xyz1), ("xyz2", xyz2), ("pose7", pose7)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s is a tensor (got %r)" % (name, type(t).__name__))
-        if t.dtype != torch.float32:
-            raise TypeError("%s is float32 (got %s)" % (name, t.dtype))
-        if not t.is_contiguous():
-            raise L.EloError("%s must be contiguous: the launch reads it in place" % name)
+    _check_tensors((("xyz1", xyz1, torch.float32), ("xyz2", xyz2, torch.float32), ("pose7", pose7, torch.float32)))
     if xyz1.dim() != 4 or xyz1.shape[-1] != 3 or xyz1.shape != xyz2.shape:
         raise L.EloError("xyz1 / xyz2 are two (B,H,W,3) range images of one shape (got %s, %s)" % (tuple(xyz1.shape), tuple(xyz2.shape)))
     B, H, W, _ = xyz1.shape
@@ -748,12 +787,6 @@ def _check_pose_fit(xyz1, xyz2, pose7, fit, beam_elev):
         raise L.EloError("pose7 is one [q0 q1 q2 q3 | t0 t1 t2] row per image: (%d, 7) (got %s)" % (B, tuple(pose7.shape)))
     if xyz2.device != xyz1.device or pose7.device != xyz1.device:
         raise L.EloError("xyz1, xyz2 and pose7 live on one device")
-    if isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda:
-        if (beam_elev.device != xyz1.device or beam_elev.dtype != torch.float32 or not beam_elev.is_contiguous()
-                or beam_elev.numel() != H):
-            raise L.EloError("a device beam table is a contiguous float32 tensor of H = %d entries on the images' device" % H)
-    if (beam_elev is not None) and H > L.MAX_BEAMS:
-        raise L.EloError("a beam table has at most %d beams (H = %d)" % (L.MAX_BEAMS, H))
 
 
 def pose_fit(xyz1, xyz2, pose7, fit, sensor=None, beam_elev=None):
@@ -763,42 +796,28 @@ def pose_fit(xyz1, xyz2, pose7, fit, sensor=None, beam_elev=None):
     the input stage of such a sensor wrote the images with.  Inputs are float32, contiguous and used in place: pose7 is read when
     the launches RUN (a graph that records this call fits what the row holds at every replay).  Bad shapes, dtypes or layouts
     are refused here, before anything is launched."""
-    _check_pose_fit(xyz1, xyz2, pose7, fit, beam_elev)
-    sensor = _sensor.resolve(sensor)
-    L.require_gpu(xyz1, xyz2, pose7)
+    _check_pose_fit(xyz1, xyz2, pose7, fit)
     B, H, W, _ = xyz1.shape
     dev = xyz1.device
-    if beam_elev is None and sensor.beam_elevations_deg is not None:
-        beam_elev = sensor
-    if beam_elev is not None and not (isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda):
-        if torch.cuda.is_current_stream_capturing():
-            raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
-        beam_elev = beam_table(beam_elev, H, dev)
+    rule = cell_rule(H, W, dev, sensor, beam_elev, "images'", L.MAX_BEAMS)
+    L.require_gpu(xyz1, xyz2, pose7)
     words = L.lib().elo_pose_fit_scratch_words(B, H, W)
     if words < 0:
         raise L.EloError("elo_pose_fit refuses a (%d,%d,%d) batch of images" % (B, H, W))
     res = PoseFitResult(torch.empty((B, 7), dtype=torch.float32, device=dev), torch.empty((B, 6, 6), dtype=torch.float32, device=dev),
                         torch.empty((B, 6), dtype=torch.float32, device=dev), torch.empty((B, 4), dtype=torch.float32, device=dev),
-                        torch.empty((max(words, 1),), dtype=torch.int32, device=dev))
-    az, vres, voff = projection_constants(H, W, sensor)
-    a = L.PoseFitArgs(B, H, W, az, vres, voff, xyz1.data_ptr(), xyz2.data_ptr(), pose7.data_ptr(), _ptr(beam_elev), fit.iters, fit.gate,
-                      fit.huber, fit.jump_rel, fit.min_count, fit.damping, res.pose.data_ptr(), res.info.data_ptr(), res.grad.data_ptr(),
-                      res.stats.data_ptr(), res.scratch.data_ptr())
+                        torch.empty((max(words, 1),), dtype=torch.int32, device=dev), keep=rule.beam_elev)
+    a = L.PoseFitArgs(B, H, W, rule.az_res, rule.vert_res, rule.vert_off, xyz1.data_ptr(), xyz2.data_ptr(), pose7.data_ptr(),
+                      _ptr(rule.beam_elev), fit.iters, fit.gate, fit.huber, fit.jump_rel, fit.min_count, fit.damping, res.pose.data_ptr(),
+                      res.info.data_ptr(), res.grad.data_ptr(), res.stats.data_ptr(), res.scratch.data_ptr())
     L.call("elo_pose_fit", a, xyz1)
-    if beam_elev is not None:
-        res.scratch = (res.scratch, beam_elev)          # (the launches read the table when they run: it lives as long as the result)
     return res
 
 
-def _check_model_render(src, pose, beam_elev):
-    """What the host can refuse about a model render without a GPU or the library: shapes, dtypes, layout, devices."""
-    for name, t in (("src", src), ("pose", pose)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s is a tensor (got %r)" % (name, type(t).__name__))
-        if t.dtype != torch.float32:
-            raise TypeError("%s is float32 (got %s)" % (name, t.dtype))
-        if not t.is_contiguous():
-            raise L.EloError("%s must be contiguous: the launch reads it in place" % name)
+def _check_model_render(src, pose):
+    """What the host can refuse about a model render without a GPU or the library: shapes, dtypes, layout, devices (the beam
+    table: cell_rule)."""
+    _check_tensors((("src", src, torch.float32), ("pose", pose, torch.float32)))
     if src.dim() != 5 or src.shape[-1] != 3:
         raise L.EloError("src is (B,K,H,W,3): K range images per batch element (got %s)" % (tuple(src.shape),))
     B, K, H, W, _ = src.shape
@@ -812,12 +831,6 @@ def _check_model_render(src, pose, beam_elev):
         raise L.EloError("pose is one [q0 q1 q2 q3 | t0 t1 t2] row per source: (%d, %d, 7) (got %s)" % (B, K, tuple(pose.shape)))
     if pose.device != src.device:
         raise L.EloError("src and pose live on one device")
-    if isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda:
-        if (beam_elev.device != src.device or beam_elev.dtype != torch.float32 or not beam_elev.is_contiguous()
-                or beam_elev.numel() != H):
-            raise L.EloError("a device beam table is a contiguous float32 tensor of H = %d entries on the images' device" % H)
-    if (beam_elev is not None) and H > L.MAX_BEAMS:
-        raise L.EloError("a beam table has at most %d beams (H = %d)" % (L.MAX_BEAMS, H))
 
 
 def model_render(src, pose, sensor=None, beam_elev=None):
@@ -826,26 +839,19 @@ def model_render(src, pose, sensor=None, beam_elev=None):
     of the point each cell holds, -1 where it is empty).  `sensor` / `beam_elev`: the cell rule, as pose_fit takes them.  Inputs
     are float32, contiguous and used in place: both are read when the launches RUN (a graph that records this call renders what
     they hold at every replay).  Bad shapes, dtypes or layouts are refused here, before anything is launched."""
-    _check_model_render(src, pose, beam_elev)
-    sensor = _sensor.resolve(sensor)
-    L.require_gpu(src, pose)
+    _check_model_render(src, pose)
     B, K, H, W, _ = src.shape
     dev = src.device
-    if beam_elev is None and sensor.beam_elevations_deg is not None:
-        beam_elev = sensor
-    if beam_elev is not None and not (isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda):
-        if torch.cuda.is_current_stream_capturing():
-            raise L.EloError("a graph capture needs the beam table as a device tensor its owner keeps (beam_elev=beam_table(...))")
-        beam_elev = beam_table(beam_elev, H, dev)
+    rule = cell_rule(H, W, dev, sensor, beam_elev, "images'", L.MAX_BEAMS, one_row=(1.0, 0.0))
+    L.require_gpu(src, pose)
     words = L.lib().elo_model_render_scratch_words(B, H, W)
     if words < 0:
         raise L.EloError("elo_model_render refuses a (%d,%d,%d) batch of images" % (B, H, W))
     xyz = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
     idx = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     scratch = torch.empty((max(words, 2),), dtype=torch.int32, device=dev)
-    az, vres, voff = projection_constants(H, W, sensor) if H > 1 else (projection_constants(2, W, sensor)[0], 1.0, 0.0)
-    a = L.ModelRenderArgs(B, K, H, W, az, vres, voff, src.data_ptr(), pose.data_ptr(), _ptr(beam_elev), xyz.data_ptr(), idx.data_ptr(),
-                          scratch.data_ptr())
+    a = L.ModelRenderArgs(B, K, H, W, rule.az_res, rule.vert_res, rule.vert_off, src.data_ptr(), pose.data_ptr(), _ptr(rule.beam_elev),
+                          xyz.data_ptr(), idx.data_ptr(), scratch.data_ptr())
     L.call("elo_model_render", a, src)
     return xyz, idx
 
@@ -855,13 +861,7 @@ def _check_model_state(ring, state, image, name, poses64=None, poses32=None, T=N
     given = [("ring", ring, torch.float32), ("state", state, torch.int32), (name, image, torch.float32)]
     if poses64 is not None or poses32 is not None or T is not None:
         given += [("poses64", poses64, torch.float64), ("poses32", poses32, torch.float32), ("T", T, torch.float32)]
-    for what, t, dtype in given:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s is a tensor (got %r)" % (what, type(t).__name__))
-        if t.dtype != dtype:
-            raise TypeError("%s is %s (got %s)" % (what, str(dtype).replace("torch.", ""), t.dtype))
-        if not t.is_contiguous():
-            raise L.EloError("%s must be contiguous: the launch uses it in place" % what)
+    _check_tensors(given)
     if ring.dim() != 4 or ring.shape[-1] != 3:
         raise L.EloError("ring is (K,H,W,3): the K scans a model holds (got %s)" % (tuple(ring.shape),))
     K, H, W, _ = ring.shape

@@ -110,15 +110,10 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
             if sweep is not None:
                 last = len(chunk) - 1
                 skew["motion"] = pose7[last].repeat(batch_size, 1).contiguous()
-            for j in range(len(chunk)):
-                i = start + j
-                if i > 0 and frames[i] != frames[i - 1] + 1:
-                    tracker.reset()
-                res = tracker.step(both[j:j + 1], both[batch_size + j:batch_size + j + 1], pose7[j:j + 1])
-                pose = res.pose.cpu().numpy()
-                qs.append(pose[:, :4].copy())
-                ts.append(pose[:, 4:].copy())
-                fits.append(fit_rows(res, 1))
+            pose, rows = _track(tracker, frames, start, both, pose7, len(chunk))
+            qs.append(pose[:, :4].copy())
+            ts.append(pose[:, 4:].copy())
+            fits.append(rows)
             continue
         out = net.forward_points(torch.from_numpy(cloud).to(dev), H_input, W_input, torch.from_numpy(T_gt).to(dev),
                                  eye, eye, is_training=False, aug_frame=np.ones(batch_size, np.int64), **skew)
@@ -133,9 +128,7 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
             continue
         qs.append(out[0][:len(chunk)].reshape(-1, 4).cpu().numpy())
         ts.append(out[1][:len(chunk)].reshape(-1, 3).cpu().numpy())
-    if fit is not None:
-        return np.concatenate(qs), np.concatenate(ts), np.concatenate(fits)
-    return np.concatenate(qs), np.concatenate(ts)
+    return _stacked(qs, ts, fits, fit)
 
 
 _TRIU = np.triu_indices(6)
@@ -146,6 +139,29 @@ def fit_rows(result, n):
     stats = result.stats[:n].cpu().numpy().astype(np.float64)
     info = result.info[:n].cpu().numpy().astype(np.float64)
     return np.concatenate([stats[:, [0, 2, 3]], info[:, _TRIU[0], _TRIU[1]]], 1)
+
+
+def _stacked(qs, ts, fits, fit):
+    """predict_sequence's return from the per-chunk pieces: (q, t), and the fit rows where a fit was asked for."""
+    q_t = (np.concatenate(qs), np.concatenate(ts))
+    return q_t if fit is None else q_t + (np.concatenate(fits),)
+
+
+def _track(tracker, frames, first, both, pose7, n):
+    """The first `n` samples of a chunk -- samples first .. first + n - 1 of `frames` -- through the tracker, in order: `both`
+    (2B,H,W,3) the chunk's stacked range images (frame 1 of sample j at j, its frame 2 at B + j), `pose7` (B,7) its pose rows ->
+    (poses (n,7), fit_rows (n,24)).  The tracker is reset wherever `frames` does not continue by one, and every result is on the
+    host (.cpu()) before the next step overwrites it."""
+    B = both.shape[0] // 2
+    poses, rows = [], []
+    for j in range(n):
+        i = first + j
+        if i > 0 and frames[i] != frames[i - 1] + 1:
+            tracker.reset()
+        res = tracker.step(both[j:j + 1], both[B + j:B + j + 1], pose7[j:j + 1])
+        poses.append(res.pose.cpu().numpy())
+        rows.append(fit_rows(res, 1))
+    return np.concatenate(poses), np.concatenate(rows)
 
 
 def _tracker(net, H_input, W_input, model, fit):
@@ -170,20 +186,11 @@ def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size
         if tracker is not None:
             # the range images of the lane's clouds: a lane that starts from raw clouds keeps them inside its graph (lane_input() is
             # the buffer of a lane fed with range images), so the input stage runs once more on the cloud buffer -- the same launches on
-            # the same bytes.  Every result is on the host (.cpu()) before the next step overwrites it and before the lane's buffers
-            # are written again.
+            # the same bytes.  Every result is on the host (_track) before the lane's buffers are written again.
             with torch.no_grad():
                 _pts, both = pwclo_model.input_stage(net.lane_cloud(lane), None, None, H_input, W_input, sensor=net.sensor,
                                                      beam_elev=net.beam_elev)
-            pose7, rows, poses = net.lane_pose(lane), [], []
-            for j in range(len(chunks[ci])):
-                i = ci * batch_size + j
-                if i > 0 and frames[i] != frames[i - 1] + 1:
-                    tracker.reset()
-                res = tracker.step(both[j:j + 1], both[batch_size + j:batch_size + j + 1], pose7[j:j + 1])
-                poses.append(res.pose.cpu().numpy())
-                rows.append(fit_rows(res, 1))
-            pose, fits[ci] = np.concatenate(poses), np.concatenate(rows)
+            pose, fits[ci] = _track(tracker, frames, ci * batch_size, both, net.lane_pose(lane), len(chunks[ci]))
         elif fit is not None:
             res = net.lane_fit(lane, fit)
             pose, fits[ci] = res.pose[:len(chunks[ci])].cpu().numpy(), fit_rows(res, len(chunks[ci]))
@@ -202,9 +209,7 @@ def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size
         net.submit_points(lane, pinned[lane])                # async H2D into the lane's cloud buffer + one replay
     for ci in range(max(0, len(chunks) - lanes), len(chunks)):
         collect(ci)
-    if fit is not None:
-        return np.concatenate(qs), np.concatenate(ts), np.concatenate(fits)
-    return np.concatenate(qs), np.concatenate(ts)
+    return _stacked(qs, ts, fits, fit)
 
 
 def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):

@@ -54,14 +54,9 @@ def rebase(poses64, T):
     return torch.cat([qn, tn], 1)
 
 
-class ModelTracker:
-    """ModelTracker(H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"): the local model of ONE drive.
-    model: sensor.LocalModel; fit: sensor.PoseFit; sensor / beam_elev: the cell rule, as _ops.pose_fit takes them (a sensor with a
-    beam table is uploaded once, here).
-    State, all on the device: `ring` (scans,H,W,3) float32, zeroed -- slot i % scans holds the i-th scan that entered since
-    reset(), an unused slot is all empty cells and gives the render nothing --; `poses64` (scans,7) float64 [q | t], scan of the
-    slot -> the model's frame (the frame of the newest scan held), with the float32 copy `poses32` (1,scans,7) the render reads.
-    step() enqueues launches and device-side float64 torch operators only: the host never waits for the device."""
+class _Tracker:
+    """What both trackers are built from: the values, checked before any tensor is made, and the cell rule -- the sensor and its
+    beam table on the tracker's device (_ops.bind_sensor: uploaded once, owned here for every launch and graph that reads it)."""
 
     def __init__(self, H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"):
         if not isinstance(model, _sensor.LocalModel):
@@ -71,13 +66,26 @@ class ModelTracker:
         self.H, self.W, self.model, self.fit = int(H), int(W), model, fit
         if self.H < 3 or self.W < 1:
             raise ValueError("a pose fit needs H >= 3 and W >= 1 (got %d x %d)" % (self.H, self.W))
-        self.sensor = _sensor.resolve(sensor)
         self.device = torch.device(device)
-        if beam_elev is None and self.sensor.beam_elevations_deg is not None:
-            beam_elev = self.sensor
-        if beam_elev is not None and not (isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda):
-            beam_elev = _ops.beam_table(beam_elev, self.H, self.device)
-        self.beam_elev = beam_elev
+        self.sensor, self.beam_elev = _ops.bind_sensor(sensor, self.device, beam_elev, self.H)
+
+    def _pair(self, xyz1, xyz2):
+        want = (1, self.H, self.W, 3)
+        if tuple(xyz1.shape) != want or tuple(xyz2.shape) != want:
+            raise ValueError("xyz1 / xyz2 are %s range images (got %s, %s)" % (want, tuple(xyz1.shape), tuple(xyz2.shape)))
+
+
+class ModelTracker(_Tracker):
+    """ModelTracker(H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"): the local model of ONE drive.
+    model: sensor.LocalModel; fit: sensor.PoseFit; sensor / beam_elev: the cell rule, as _ops.pose_fit takes them (a sensor with a
+    beam table is uploaded once, here).
+    State, all on the device: `ring` (scans,H,W,3) float32, zeroed -- slot i % scans holds the i-th scan that entered since
+    reset(), an unused slot is all empty cells and gives the render nothing --; `poses64` (scans,7) float64 [q | t], scan of the
+    slot -> the model's frame (the frame of the newest scan held), with the float32 copy `poses32` (1,scans,7) the render reads.
+    step() enqueues launches and device-side float64 torch operators only: the host never waits for the device."""
+
+    def __init__(self, H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"):
+        super().__init__(H, W, model, fit, sensor, beam_elev, device)
         K = model.scans
         self.ring = torch.zeros((K, self.H, self.W, 3), dtype=torch.float32, device=self.device)
         self._identity = torch.zeros((K, 7), dtype=torch.float64, device=self.device)
@@ -108,9 +116,7 @@ class ModelTracker:
         """One pair: xyz1 / xyz2 (1,H,W,3) float32 range images on the tracker's device, pose7 (1,7) [q | t] from frame 1 to frame 2
         -> the _ops.PoseFitResult of xyz1 against the MODEL at pose7.  Then the model moves into frame 1 by the pose the fit
         returned (a flagged image's is pose7, by the kernel's own guarantee) and xyz1 enters it."""
-        want = (1, self.H, self.W, 3)
-        if tuple(xyz1.shape) != want or tuple(xyz2.shape) != want:
-            raise ValueError("xyz1 / xyz2 are %s range images (got %s, %s)" % (want, tuple(xyz1.shape), tuple(xyz2.shape)))
+        self._pair(xyz1, xyz2)
         if self.entered == 0:
             self._enter(xyz2)
         model, _src = self.render()
@@ -120,7 +126,7 @@ class ModelTracker:
         return res
 
 
-class DeviceTracker:
+class DeviceTracker(_Tracker):
     """DeviceTracker(H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"): ModelTracker with the state machine on the
     device -- the same arguments, the same checks, the same model of the last `model.scans` scans.
     State, four device tensors: `ring` (scans,H,W,3) float32; `poses64` (scans,7) float64 [q | t], scan of the slot -> the model's
@@ -130,20 +136,7 @@ class DeviceTracker:
     launches from `state` when they run (include/elo.h, elo_model_begin / elo_model_advance): the host branches on nothing."""
 
     def __init__(self, H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"):
-        if not isinstance(model, _sensor.LocalModel):
-            raise TypeError("model is a LocalModel (got %r)" % (type(model).__name__,))
-        if not isinstance(fit, _sensor.PoseFit):
-            raise TypeError("fit is a PoseFit (got %r)" % (type(fit).__name__,))
-        self.H, self.W, self.model, self.fit = int(H), int(W), model, fit
-        if self.H < 3 or self.W < 1:
-            raise ValueError("a pose fit needs H >= 3 and W >= 1 (got %d x %d)" % (self.H, self.W))
-        self.sensor = _sensor.resolve(sensor)
-        self.device = torch.device(device)
-        if beam_elev is None and self.sensor.beam_elevations_deg is not None:
-            beam_elev = self.sensor
-        if beam_elev is not None and not (isinstance(beam_elev, torch.Tensor) and beam_elev.is_cuda):
-            beam_elev = _ops.beam_table(beam_elev, self.H, self.device)
-        self.beam_elev = beam_elev
+        super().__init__(H, W, model, fit, sensor, beam_elev, device)
         K = model.scans
         self.ring = torch.empty((K, self.H, self.W, 3), dtype=torch.float32, device=self.device)
         self.poses64 = torch.empty((K, 7), dtype=torch.float64, device=self.device)
@@ -169,9 +162,7 @@ class DeviceTracker:
         the current stream: begin (frame 2 enters an empty model), render, the fit of xyz1 against the rendered image at pose7, advance
         (the model moves into frame 1 by the pose the fit returned, xyz1 enters).  6 + 2 (iters + 1) launches, no host branch on
         device state, no synchronisation -> the _ops.PoseFitResult."""
-        want = (1, self.H, self.W, 3)
-        if tuple(xyz1.shape) != want or tuple(xyz2.shape) != want:
-            raise ValueError("xyz1 / xyz2 are %s range images (got %s, %s)" % (want, tuple(xyz1.shape), tuple(xyz2.shape)))
+        self._pair(xyz1, xyz2)
         _ops.model_begin(self.ring, self.state, xyz2[0])
         model, _src = _ops.model_render(self.ring.unsqueeze(0), self.poses32.unsqueeze(0), sensor=self.sensor, beam_elev=self.beam_elev)
         res = _ops.pose_fit(xyz1, model, pose7, self.fit, sensor=self.sensor, beam_elev=self.beam_elev)

@@ -128,10 +128,7 @@ class PWCLONet:
         fixed for the net's life: every forward, eager or captured, projects with it.  A beam table lives on the device as
         `beam_elev`, a tensor this net owns for as long as its graphs (which hold its pointer) exist."""
         self.device = torch.device(device)
-        self.sensor = sensor_mod.resolve(sensor)
-        self.beam_elev = None
-        if self.sensor.beam_elevations_deg is not None:
-            self.beam_elev = _ops.beam_table(self.sensor, len(self.sensor.beam_elevations_deg), self.device)
+        self.sensor, self.beam_elev = _ops.bind_sensor(sensor, self.device)
         self.feature_dtype = feature_dtype
         self.store = tf_util.VariableStore(self.device, seed=seed)
         self.perms = perm_source if perm_source is not None else perm.PermSource(seed=seed)

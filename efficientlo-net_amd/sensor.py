@@ -18,7 +18,32 @@ one range image (elo_model_render; local_model.ModelTracker) instead of against 
 import math
 
 
-class Sensor:
+class _Frozen:
+    """A value: its fields (the subclass's __slots__) are set once by _freeze and never again; equal where the class and every
+    field are equal, hashable alike."""
+    __slots__ = ()
+
+    def _freeze(self, *values):
+        for name, value in zip(self.__slots__, values):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("%s is immutable" % type(self).__name__)
+
+    def __delattr__(self, name):
+        raise AttributeError("%s is immutable" % type(self).__name__)
+
+    def _key(self):
+        return tuple(getattr(self, name) for name in self.__slots__)
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash((type(self).__name__, self._key()))
+
+
+class Sensor(_Frozen):
     """Sensor(fov_up_deg=2.0, fov_down_deg=-24.8, crop_xy=35.0, beam_elevations_deg=None): frozen and hashable.
     beam_elevations_deg: the elevation of every beam in degrees, row 0 (the highest) first, strictly descending; with a table
     and no explicit field of view, fov_up / fov_down are its first / last entry."""
@@ -41,23 +66,7 @@ class Sensor:
             raise ValueError("fov_up_deg must lie above fov_down_deg (got %r, %r)" % (up, down))
         if not (crop > 0):
             raise ValueError("crop_xy must be positive (got %r)" % (crop,))
-        for name, value in (("fov_up_deg", up), ("fov_down_deg", down), ("crop_xy", crop), ("beam_elevations_deg", table)):
-            object.__setattr__(self, name, value)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Sensor is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("Sensor is immutable")
-
-    def _key(self):
-        return (self.fov_up_deg, self.fov_down_deg, self.crop_xy, self.beam_elevations_deg)
-
-    def __eq__(self, other):
-        return isinstance(other, Sensor) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
+        self._freeze(up, down, crop, table)
 
     def __repr__(self):
         table = "" if self.beam_elevations_deg is None else ", beam_elevations_deg=<%d beams>" % len(self.beam_elevations_deg)
@@ -82,7 +91,7 @@ class Sensor:
 KITTI_HDL64 = Sensor()
 
 
-class Sweep:
+class Sweep(_Frozen):
     """Sweep(phase="azimuth", phase_ref=1.0): how a scan that is NOT motion-compensated tells WHEN each of its points was
     acquired, and the instant the input stage carries them all to (elo_input_stage_deskew, include/elo.h).  Frozen and hashable.
     phase: "azimuth" -- the fraction of the turn, (pi - atan2(y, x)) / 2 pi, of a sensor that starts its sweep at azimuth pi --
@@ -103,29 +112,13 @@ class Sweep:
         ref = float(phase_ref)
         if not math.isfinite(ref):
             raise ValueError("phase_ref must be finite (got %r)" % (ref,))
-        object.__setattr__(self, "phase", phase)
-        object.__setattr__(self, "phase_ref", ref)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Sweep is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("Sweep is immutable")
-
-    def _key(self):
-        return (self.phase, self.phase_ref)
-
-    def __eq__(self, other):
-        return isinstance(other, Sweep) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
+        self._freeze(phase, ref)
 
     def __repr__(self):
         return "Sweep(phase=%r, phase_ref=%r)" % (self.phase, self.phase_ref)
 
 
-class PoseFit:
+class PoseFit(_Frozen):
     """PoseFit(iters=0, gate=1.0, huber=0.1, jump_rel=0.1, min_count=50, damping=0.0): the point-to-plane fit of a pose on the two
     range images of its pair (elo_pose_fit, include/elo.h).  Frozen and hashable.
     iters: Gauss-Newton steps on the pose (0: only measure it); gate (m): a frame-1 point further than this from the point of the
@@ -150,30 +143,13 @@ class PoseFit:
         for name, value in (("jump_rel", jump_rel), ("damping", damping)):
             if not (math.isfinite(value) and value >= 0):
                 raise ValueError("%s must be finite and >= 0 (got %r)" % (name, value))
-        for name, value in (("iters", iters), ("gate", gate), ("huber", huber), ("jump_rel", jump_rel), ("min_count", min_count),
-                            ("damping", damping)):
-            object.__setattr__(self, name, value)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("PoseFit is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("PoseFit is immutable")
-
-    def _key(self):
-        return (self.iters, self.gate, self.huber, self.jump_rel, self.min_count, self.damping)
-
-    def __eq__(self, other):
-        return isinstance(other, PoseFit) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
+        self._freeze(iters, gate, huber, jump_rel, min_count, damping)
 
     def __repr__(self):
         return "PoseFit(iters=%r, gate=%r, huber=%r, jump_rel=%r, min_count=%r, damping=%r)" % self._key()
 
 
-class LocalModel:
+class LocalModel(_Frozen):
     """LocalModel(scans=4, resident=False): fit every scan against the last `scans` scans, rendered into one range image by nearest
     range (elo_model_render, include/elo.h), instead of against the last scan alone.  Frozen and hashable.
     scans: how many scans the model holds, an integer in 1 .. 16 (1: the pair fit, through the same path).
@@ -189,20 +165,7 @@ class LocalModel:
             raise ValueError("scans is 1 .. 16 (got %d)" % scans)
         if not isinstance(resident, bool):
             raise ValueError("resident is True or False (got %r)" % (resident,))
-        object.__setattr__(self, "scans", scans)
-        object.__setattr__(self, "resident", resident)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("LocalModel is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("LocalModel is immutable")
-
-    def __eq__(self, other):
-        return isinstance(other, LocalModel) and (self.scans, self.resident) == (other.scans, other.resident)
-
-    def __hash__(self):
-        return hash(("LocalModel", self.scans, self.resident))
+        self._freeze(scans, resident)
 
     def __repr__(self):
         if self.resident:

@@ -250,12 +250,10 @@ class Trainer:
         the tables: a captured step keeps the pointer of the one it was recorded with."""
         sensor = self.net.sensor if sensor is None else sensor_mod.resolve(sensor)
         self._sensor = sensor
-        if sensor.beam_elevations_deg is None:
-            return sensor, None
         if sensor == self.net.sensor:
             return sensor, self.net.beam_elev
         if sensor not in self._beam_tables:
-            self._beam_tables[sensor] = _ops.beam_table(sensor, len(sensor.beam_elevations_deg), self.net.device)
+            self._beam_tables[sensor] = _ops.bind_sensor(sensor, self.net.device)[1]
         return sensor, self._beam_tables[sensor]
 
     def _global_batch(self, B):
