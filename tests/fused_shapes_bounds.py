@@ -281,11 +281,13 @@ def _rtz16(x):
     return np.where(np.isinf(out), np.sign(x) * _F(65504.0), out).astype(_F)
 
 
-def emulate_layer(x, layer, mode, exact_input=False, sequential=False):
+def emulate_layer(x, layer, mode, exact_input=False, sequential=False, drop_w_lo=False):
     """One layer as the tile kernels compute it, in float32 numpy: operands split into fp16 hi + lo (activations toward zero,
     weights to nearest), the three products hi*hi + lo*hi + hi*lo (half: the one product of the rounded operands), k-blocks of
     32 accumulated in fp32 on top of the bias.  (A plain float32 matmul per block -- 31 sequential roundings instead of the tree the
-    bound models -- stays inside the bound too, at up to 0.8 of it for half products; it is the model that is emulated here.)"""
+    bound models -- stays inside the bound too, at up to 0.8 of it for half products; it is the model that is emulated here.)
+    drop_w_lo: a WRONG split scheme that leaves out the product with the weights' lo half (a mistake of 2^-12 of a term): the
+    CPU tests show with it that the bound tells such a mistake from rounding."""
     W, b, relu = layer
     x, W = np.asarray(x, _F), np.asarray(W, _F)
     K, N = W.shape
@@ -303,7 +305,7 @@ def emulate_layer(x, layer, mode, exact_input=False, sequential=False):
         xl = np.zeros_like(xp) if exact_input else _rtz16(xp - xh)
         wh = Wp.astype(np.float16).astype(_F)
         wl = (Wp - wh).astype(np.float16).astype(_F)
-        parts = [(wh, xh), (wl, xh), (wh, xl)]
+        parts = [(wh, xh), (wh, xl)] if drop_w_lo else [(wh, xh), (wl, xh), (wh, xl)]
     for k0 in range(0, Kp, 32):                          # one matrix instruction per product and k-block, as (1) models it: the
         for w_, x_ in parts:                             # block's exact products summed and rounded once, then added in fp32
             if sequential:                               # (a plain float32 sum of the block's products, one rounding per term)
@@ -316,7 +318,7 @@ def emulate_layer(x, layer, mode, exact_input=False, sequential=False):
     return np.maximum(acc, _F(0)) if relu else acc
 
 
-def emulate_chain(x, layers, mode, exact_input=False, sequential=False):
+def emulate_chain(x, layers, mode, exact_input=False, sequential=False, drop_w_lo=False):
     for l, layer in enumerate(layers):
-        x = emulate_layer(x, layer, mode, exact_input and l == 0, sequential)
+        x = emulate_layer(x, layer, mode, exact_input and l == 0, sequential, drop_w_lo)
     return x

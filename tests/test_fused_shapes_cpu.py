@@ -51,14 +51,15 @@ def fake_mlp(L, srcs, layers, rows, stage2=None, storage="f32", products="split"
     return a
 
 
-def fake_setconv(L, B, n, K, C, layers, centre="xyz", group=None, storage="f32", products="split", mixed=False):
-    H2, W2 = table.GRID
+def fake_setconv(L, B, n, K, C, layers, centre="xyz", group=None, storage="f32", products="split", mixed=False, grid=None, idx_out=False):
+    """grid: the queried (H2, W2) where it is not the table's 3 x 7; idx_out: the grouping also returns its indices and mask"""
+    H2, W2 = grid or table.GRID
     H = W = 0
     spec = L.GroupSpec(None, 0, 0, 0.0, 0, 0, None, None, None)
     if group:
         kh, kw, dist, sh, sw = group
         H, W = H2 * sh - (sh - 1), W2 * sw - (sw - 1)
-        spec = L.GroupSpec(_ptr(20), kh, kw, dist, sh, sw, None, None, None)
+        spec = L.GroupSpec(_ptr(20), kh, kw, dist, sh, sw, _ptr(45) if idx_out else None, _ptr(46) if idx_out else None, None)
     elif centre == "hw":
         H, W = 5, 9
     return L.SetconvArgs(B, n, K, H, W, H2, W2, C, _ptr(21) if H else None, _ptr(22) if centre == "hw" else None,
@@ -67,15 +68,17 @@ def fake_setconv(L, B, n, K, C, layers, centre="xyz", group=None, storage="f32",
                          _ptr(28), _ptr(29) if centre == "hw" else None, spec, L.ELO_F16 if storage == "f16" else L.ELO_F32)
 
 
-def fake_cv(L, stage, B, K, C, storage="f32", products="split", mixed=False):
-    H, W = table.GRID
+def fake_cv(L, stage, B, K, C, storage="f32", products="split", mixed=False, grid=None, n=None):
+    """grid: the queried (H, W) where it is not the table's 3 x 7; n: stage 1's points per batch element where they are not H * W"""
+    H, W = grid or table.GRID
+    n = H * W if n is None else n
     code = L.ELO_F16 if storage == "f16" else L.ELO_F32
     none = L.GroupSpec(None, 0, 0, 0.0, 0, 0, None, None, None)
     d = lambda k, n, last=False: _dense(L, k, n, "half" if mixed and last and products == "split" else products)
     if stage == 1:
-        return L.Cv1Args(B, H * W, K, H, W, C, _ptr(30), _ptr(31), _ptr(32), _ptr(33), _ptr(34), _ptr(35), d(10 + 2 * C, 128), d(128, 64),
+        return L.Cv1Args(B, n, K, H, W, C, _ptr(30), _ptr(31), _ptr(32), _ptr(33), _ptr(34), _ptr(35), d(10 + 2 * C, 128), d(128, 64),
                          d(64, 64), d(10, 64), d(128, 128), d(128, 64, True), _ptr(36), none, code)
-    return L.Cv2Args(B, H * W, K, H, W, C, _ptr(30), _ptr(31), _ptr(32), _ptr(34), _ptr(35), d(10, 64), d(128 + C, 128), d(128, 64, True),
+    return L.Cv2Args(B, n, K, H, W, C, _ptr(30), _ptr(31), _ptr(32), _ptr(34), _ptr(35), d(10, 64), d(128 + C, 128), d(128, 64, True),
                      _ptr(36), none, code)
 
 
