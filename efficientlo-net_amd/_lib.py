@@ -124,6 +124,13 @@ MODEL_MAX_SCANS = 16   # ELO_MODEL_MAX_SCANS
 ModelBeginArgs = _struct("elo_model_begin_args", [("K", _i), ("H", _i), ("W", _i), ("ring", _vp), ("state", _vp), ("first", _vp)])
 ModelAdvanceArgs = _struct("elo_model_advance_args", [
     ("K", _i), ("H", _i), ("W", _i), ("ring", _vp), ("poses64", _vp), ("poses32", _vp), ("state", _vp), ("scan", _vp), ("T", _vp)])
+MapInsertArgs = _struct("elo_map_insert_args", [
+    ("batch", _i), ("H", _i), ("W", _i), ("voxel", _f), ("min_range", _f), ("max_range", _f), ("log2_capacity", _i), ("xyz", _vp),
+    ("pose", _vp), ("keys", _vp), ("acc", _vp), ("stats", _vp)])
+MapExtractArgs = _struct("elo_map_extract_args", [
+    ("voxel", _f), ("log2_capacity", _i), ("max_out", ctypes.c_long), ("keys", _vp), ("acc", _vp), ("out_key", _vp), ("out_count", _vp),
+    ("out_xyz", _vp), ("cursor", _vp)])
+MAP_MAX_PROBE, MAP_MIN_LOG2, MAP_MAX_LOG2 = 128, 10, 28        # ELO_MAP_*
 
 # backward passes (csrc/elo_backward.hip)
 GroupConcatBwdArgs = _struct("elo_group_concat_bwd_args", [
@@ -248,6 +255,8 @@ SYMBOLS = [
     ("elo_model_render_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
     ("elo_model_begin", ctypes.c_int, [ctypes.POINTER(ModelBeginArgs), _vp]),
     ("elo_model_advance", ctypes.c_int, [ctypes.POINTER(ModelAdvanceArgs), _vp]),
+    ("elo_map_insert", ctypes.c_int, [ctypes.POINTER(MapInsertArgs), _vp]),
+    ("elo_map_extract", ctypes.c_int, [ctypes.POINTER(MapExtractArgs), _vp]),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),
     ("elo_masked_maxpool_backward", ctypes.c_int, [ctypes.POINTER(MaskedMaxpoolBwdArgs), _vp]),
     ("elo_cv_encode1_backward", ctypes.c_int, [ctypes.POINTER(CvEncode1BwdArgs), _vp]),

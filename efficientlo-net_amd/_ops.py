@@ -909,6 +909,70 @@ def model_advance(ring, poses64, poses32, state, scan, T):
     L.call("elo_model_advance", a, ring)
 
 
+def _check_map(keys, acc, spec, stats=None):
+    """What the host can refuse about a world map's buffers without a GPU or the library: the value, dtypes, layout, shapes, devices.
+    The table's words are unsigned 64-bit on the device; torch holds them as int64 (counts and sums stay far below 2^63, and an empty
+    key, all ones, reads -1)."""
+    from .sensor import VoxelMap
+    if not isinstance(spec, VoxelMap):
+        raise TypeError("spec is a VoxelMap (got %r)" % (type(spec).__name__,))
+    given = [("keys", keys, torch.int64), ("acc", acc, torch.int64)] + ([("stats", stats, torch.int64)] if stats is not None else [])
+    _check_tensors(given)
+    C = spec.capacity
+    if tuple(keys.shape) != (C,) or tuple(acc.shape) != (C, 4):
+        raise L.EloError("a map of log2_capacity %d has keys (%d,) and acc (%d, 4) (got %s, %s)"
+                         % (spec.log2_capacity, C, C, tuple(keys.shape), tuple(acc.shape)))
+    if stats is not None and tuple(stats.shape) != (8,):
+        raise L.EloError("stats is eight 64-bit words (got %s)" % (tuple(stats.shape),))
+    if any(t.device != keys.device for _w, t, _d in given):
+        raise L.EloError("a map's buffers live on one device")
+
+
+def map_insert(keys, acc, stats, xyz, pose64, spec):
+    """elo_map_insert: the range images xyz (B,H,W,3) float32, each carried by its row of pose64 (B,7) float64 [q | t] (scan ->
+    world), summed into the voxel map (keys (C,), acc (C,4), stats (8,), all int64, C = spec.capacity; spec: sensor.VoxelMap).  One
+    launch on the current stream, no host synchronisation, capturable; inputs are contiguous and used in place.  Bad types, shapes or
+    layouts are refused here, before anything is launched."""
+    _check_map(keys, acc, spec, stats)
+    _check_tensors((("xyz", xyz, torch.float32), ("pose64", pose64, torch.float64)))
+    if xyz.dim() != 4 or xyz.shape[-1] != 3:
+        raise L.EloError("xyz is (B,H,W,3): one range image per scan (got %s)" % (tuple(xyz.shape),))
+    B, H, W, _ = xyz.shape
+    if H < 1 or W < 1:
+        raise L.EloError("xyz has no cells: H, W >= 1 (got %d x %d)" % (H, W))
+    if B * H * W >= 2 ** 31:
+        raise L.EloError("B*H*W stays below 2^31 (got B, H, W = %d, %d, %d)" % (B, H, W))
+    if tuple(pose64.shape) != (B, 7):
+        raise L.EloError("pose64 is one [q0 q1 q2 q3 | t0 t1 t2] row per scan: (%d, 7) (got %s)" % (B, tuple(pose64.shape)))
+    if xyz.device != keys.device or pose64.device != keys.device:
+        raise L.EloError("the map, the images and the poses live on one device")
+    L.require_gpu(keys, acc, stats, xyz, pose64)
+    a = L.MapInsertArgs(B, H, W, spec.voxel, spec.min_range, spec.max_range, spec.log2_capacity, xyz.data_ptr(), pose64.data_ptr(),
+                        keys.data_ptr(), acc.data_ptr(), stats.data_ptr())
+    L.call("elo_map_insert", a, keys)
+
+
+def map_extract(keys, acc, spec, max_out):
+    """elo_map_extract: the occupied slots of the map as rows in ARBITRARY order -> (key (max_out,) int64, count (max_out,) int64, xyz
+    (max_out,3) float32 centroids, n: a 0-dim int64 device tensor, the number of occupied slots -- it may exceed max_out; only the
+    first min(n, max_out) rows are written).  Two launches on the current stream, no host synchronisation, capturable."""
+    _check_map(keys, acc, spec)
+    if isinstance(max_out, bool) or not hasattr(max_out, "__index__") or max_out.__index__() < 0:
+        raise L.EloError("max_out is a non-negative integer (got %r)" % (max_out,))
+    max_out = max_out.__index__()
+    L.require_gpu(keys, acc)
+    dev = keys.device
+    rows = max(max_out, 1)                                    # (an empty tensor has no address: with max_out = 0 the call still counts)
+    key = torch.empty((rows,), dtype=torch.int64, device=dev)
+    count = torch.empty((rows,), dtype=torch.int64, device=dev)
+    xyz = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+    n = torch.empty((), dtype=torch.int64, device=dev)
+    a = L.MapExtractArgs(spec.voxel, spec.log2_capacity, max_out, keys.data_ptr(), acc.data_ptr(), key.data_ptr(), count.data_ptr(),
+                         xyz.data_ptr(), n.data_ptr())
+    L.call("elo_map_extract", a, keys)
+    return key[:max_out], count[:max_out], xyz[:max_out], n
+
+
 class _WarpProject(torch.autograd.Function):
     """elo_warp_project / elo_warp_project_backward.  The forward's scratch (who won each cell) is kept for the backward."""
 

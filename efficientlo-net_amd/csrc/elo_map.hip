@@ -1,0 +1,304 @@
+// elo_map.hip -- the WORLD MAP (include/elo.h, elo_map_insert / elo_map_extract): a voxel-hashed point map, every scan carried by its
+// scan -> world pose and summed per voxel into 64-bit INTEGERS: count and the three sums of the points' 16-bit offsets inside the
+// voxel.  Sums of integers do not depend on the order of arrival, so the content of the map is a function of the points put in.
+//
+// map_insert_kernel: a streaming pass like model_splat_kernel -- a workgroup works inside one scan, so R(q) is formed once per
+// thread; a thread takes MAP_STRIP consecutive cells by 16-byte loads.  Neighbouring cells of a range image often share a voxel:
+// a thread first folds RUNS of equal keys inside its strip (cells without a point pass a run along), then the wave folds runs of
+// equal keys across its lanes -- heads where the key changes, a segmented scan of the four integers, six shuffle steps whatever the
+// keys -- and the last lane of every run probes and adds: ONE probe / claim and four adds per run.  Equal keys that are not neighbours
+// are sent apart; the sums are integers, so the table ends up the same.  (The loop over the wave's DISTINCT keys -- first lane's key,
+// ballot, butterfly sum -- costs 24 shuffles per key: slower than one add per point below ~8 cells a key; tools/micro/map_atomics.hip
+// holds all three forms.)  The counters go the same way: ballots and one add per wave and counter.
+// map_extract_kernel: one thread per slot, ballot compaction, one atomic on the cursor per wave.
+#include "elo_common.h"
+
+namespace elo {
+namespace {
+
+constexpr int MAP_STRIP = 4;                            // cells per thread: 48 bytes, three 16-byte loads
+constexpr int MAP_TILE = ELO_BLOCK * MAP_STRIP;         // cells per workgroup
+constexpr int MAP_WAVE = 64;
+constexpr unsigned long long MAP_EMPTY = ~0ull;
+constexpr double MAP_HALF = 1048576.0;                  // 2^20: indices lie in [-2^20, 2^20)
+
+struct MapInsert {
+    int H, W;
+    float voxel, min_range, max_range;
+    unsigned long long mask;        // C - 1
+    const float *xyz;               // (batch,H,W,3)
+    const double *pose;             // (batch,7)
+    unsigned long long *keys, *acc, *stats;
+    unsigned tiles;                 // workgroups per scan
+    int vec;                        // 1: H*W is a multiple of 4 and xyz is 16-byte aligned
+};
+
+enum { MAP_NONE = 0, MAP_FILTERED = 1, MAP_REJECTED = 2, MAP_POINT = 3 };
+
+// model_pose (elo_model.hip) from a double row
+__device__ __forceinline__ bool map_pose(const double *row, double (&R)[9], double (&t)[3])
+{
+    double q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
+    const double n = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    if (!(n > 0.0) || n - n != 0.0) return false;
+    q0 /= n; q1 /= n; q2 /= n; q3 /= n;
+    R[0] = 1.0 - 2.0 * (q2 * q2 + q3 * q3); R[1] = 2.0 * (q1 * q2 - q0 * q3);       R[2] = 2.0 * (q1 * q3 + q0 * q2);
+    R[3] = 2.0 * (q1 * q2 + q0 * q3);       R[4] = 1.0 - 2.0 * (q1 * q1 + q3 * q3); R[5] = 2.0 * (q2 * q3 - q0 * q1);
+    R[6] = 2.0 * (q1 * q3 - q0 * q2);       R[7] = 2.0 * (q2 * q3 + q0 * q1);       R[8] = 1.0 - 2.0 * (q1 * q1 + q2 * q2);
+    t[0] = row[4]; t[1] = row[5]; t[2] = row[6];
+    return true;
+}
+
+// one axis of the rounded p': its 21-bit field of the key and its offset inside the voxel; false: the index is out of range
+__device__ __forceinline__ bool map_axis(float c, double voxel, unsigned long long &field, unsigned &g)
+{
+    const double u = (double)c / voxel;
+    const double i = floor(u);
+    if (!(i >= -MAP_HALF && i < MAP_HALF)) return false;
+    const double f = floor((u - i) * 65536.0);          // u - i lies in [0, 1]: 1 where u is a tiny negative number
+    const unsigned o = (unsigned)f;
+    g = o < 65535u ? o : 65535u;
+    field = (unsigned long long)((long long)i + (1ll << 20));
+    return true;
+}
+
+// the per-point rule of include/elo.h -> MAP_NONE / FILTERED / REJECTED / POINT (then key and g are set)
+__device__ __forceinline__ int map_point(const MapInsert &a, const double (&R)[9], const double (&t)[3], float ax, float ay, float az,
+                                         unsigned long long &key, unsigned (&g)[3])
+{
+    if (ax == 0.0f && ay == 0.0f && az == 0.0f) return MAP_NONE;
+    const float rf = sqrtf(ax * ax + ay * ay + az * az);
+    if (rf < a.min_range || rf > a.max_range) return MAP_FILTERED;
+    const float x = (float)(R[0] * ax + R[1] * ay + R[2] * az + t[0]);
+    const float y = (float)(R[3] * ax + R[4] * ay + R[5] * az + t[1]);
+    const float z = (float)(R[6] * ax + R[7] * ay + R[8] * az + t[2]);
+    if (x - x != 0.0f || y - y != 0.0f || z - z != 0.0f) return MAP_REJECTED;
+    const double voxel = (double)a.voxel;
+    unsigned long long fx, fy, fz;
+    if (!map_axis(x, voxel, fx, g[0]) || !map_axis(y, voxel, fy, g[1]) || !map_axis(z, voxel, fz, g[2])) return MAP_REJECTED;
+    key = fx << 42 | fy << 21 | fz;
+    return MAP_POINT;
+}
+
+__device__ __forceinline__ unsigned long long map_home(unsigned long long h)
+{
+    h ^= h >> 30; h *= 0xbf58476d1ce4e5b9ull;
+    h ^= h >> 27; h *= 0x94d049bb133111ebull;
+    h ^= h >> 31;
+    return h;
+}
+
+// the slot of `key`, claimed where it has none yet; false: none within ELO_MAP_MAX_PROBE.  A slot only ever turns from empty into
+// one key, so a plain load that shows another key is final and one that shows empty is settled by the CAS.
+__device__ __forceinline__ bool map_slot(unsigned long long *keys, const unsigned long long mask, const unsigned long long key,
+                                         unsigned long long &slot, unsigned &claimed)
+{
+    const unsigned long long home = map_home(key);
+    for (int j = 0; j < ELO_MAP_MAX_PROBE; ++j) {
+        const unsigned long long s = (home + (unsigned long long)j) & mask;
+        unsigned long long cur = __atomic_load_n(keys + s, __ATOMIC_RELAXED);
+        if (cur == MAP_EMPTY) {
+            cur = atomicCAS(keys + s, MAP_EMPTY, key);
+            if (cur == MAP_EMPTY) { claimed += 1u; cur = key; }
+        }
+        if (cur == key) { slot = s; return true; }
+    }
+    return false;
+}
+
+__device__ __forceinline__ unsigned wave_sum(unsigned v)
+{
+    for (int d = MAP_WAVE / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, MAP_WAVE);
+    return v;
+}
+
+__global__ __launch_bounds__(ELO_BLOCK) void map_insert_kernel(const MapInsert a)
+{
+    const unsigned b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
+    double R[9], t[3];
+    if (!map_pose(a.pose + (long)b * 7, R, t)) return;                                  // the whole scan, by the whole workgroup
+    const long cells = (long)a.H * a.W;
+    const long i0 = ((long)tile * ELO_BLOCK + threadIdx.x) * MAP_STRIP;
+    float v[3 * MAP_STRIP];
+    if (i0 >= cells) {                                                                  // (the lane stays for the wave's ballots)
+        for (int j = 0; j < 3 * MAP_STRIP; ++j) v[j] = 0.0f;
+    } else {
+        const float *s = a.xyz + ((long)b * cells + i0) * 3;
+        if (a.vec) {                                                                    // (cells % 4 == 0: the strip is inside the image)
+            const float4 *s4 = reinterpret_cast<const float4 *>(s);
+            const float4 u0 = s4[0], u1 = s4[1], u2 = s4[2];
+            v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
+            v[8] = u2.x; v[9] = u2.y; v[10] = u2.z; v[11] = u2.w;
+        } else {
+            for (int c = 0; c < MAP_STRIP; ++c) {
+                const bool in = i0 + c < cells;
+                for (int j = 0; j < 3; ++j) v[c * 3 + j] = in ? s[c * 3 + j] : 0.0f;
+            }
+        }
+    }
+    const unsigned lane = threadIdx.x & (MAP_WAVE - 1);
+    const unsigned long long upto = (2ull << lane) - 1ull;                              // lanes 0 .. lane (lane 63: all)
+    unsigned long long key[MAP_STRIP];
+    unsigned cnt[MAP_STRIP], sx[MAP_STRIP], sy[MAP_STRIP], sz[MAP_STRIP];
+    unsigned filtered = 0, rejected = 0;                                                // wave-uniform: ballots
+    for (int c = 0; c < MAP_STRIP; ++c) {
+        unsigned g[3] = {0u, 0u, 0u};
+        key[c] = MAP_EMPTY;
+        const int kind = map_point(a, R, t, v[c * 3], v[c * 3 + 1], v[c * 3 + 2], key[c], g);
+        filtered += (unsigned)__popcll(__ballot(kind == MAP_FILTERED));
+        rejected += (unsigned)__popcll(__ballot(kind == MAP_REJECTED));
+        cnt[c] = kind == MAP_POINT ? 1u : 0u;
+        sx[c] = cnt[c] ? g[0] : 0u; sy[c] = cnt[c] ? g[1] : 0u; sz[c] = cnt[c] ? g[2] : 0u;
+        if (c > 0) {
+            // a run inside the strip moves on to its last cell; a cell without a point passes the run before it along (a hole in a
+            // wall does not end the wall's run)
+            if (!cnt[c]) key[c] = key[c - 1];
+            if (key[c] == key[c - 1]) {
+                cnt[c] += cnt[c - 1]; sx[c] += sx[c - 1]; sy[c] += sy[c - 1]; sz[c] += sz[c - 1];
+                cnt[c - 1] = 0u; sx[c - 1] = 0u; sy[c - 1] = 0u; sz[c - 1] = 0u;
+            }
+        }
+    }
+    unsigned inserted = 0, dropped = 0, claimed = 0;                                    // this lane's
+    for (int c = 0; c < MAP_STRIP; ++c) {
+        // ... and across the lanes, cell c of every strip: a lane with nothing in cell c takes the key of the nearest lane below
+        // that has, so runs pass over it; a run of lanes with one key is a segment, summed by a segmented scan (six steps, whatever
+        // the keys), and the segment's last lane sends the sums.  <= 256 points a wave: a sum stays below 2^24.
+        const unsigned long long have = __ballot(cnt[c] != 0u) & upto;
+        const unsigned long long k = __shfl(key[c], have ? 63 - __clzll((long long)have) : (int)lane, MAP_WAVE);
+        const unsigned long long mine = have ? k : MAP_EMPTY;
+        const unsigned long long below = __shfl_up(mine, 1, MAP_WAVE);
+        const unsigned long long heads = __ballot(lane == 0u || mine != below);
+        const unsigned start = 63u - (unsigned)__clzll((long long)(heads & upto));      // (lane 0 is a head)
+        unsigned n = cnt[c], gx = sx[c], gy = sy[c], gz = sz[c];
+        for (unsigned d = 1; d < MAP_WAVE; d <<= 1) {
+            const unsigned tn = __shfl_up(n, d, MAP_WAVE), tx = __shfl_up(gx, d, MAP_WAVE);
+            const unsigned ty = __shfl_up(gy, d, MAP_WAVE), tz = __shfl_up(gz, d, MAP_WAVE);
+            if (lane >= start + d) { n += tn; gx += tx; gy += ty; gz += tz; }
+        }
+        const bool last = lane == MAP_WAVE - 1 || (heads >> (lane + 1u) & 1ull) != 0ull;
+        if (last && n != 0u) {
+            unsigned long long slot;
+            if (map_slot(a.keys, a.mask, mine, slot, claimed)) {
+                unsigned long long *row = a.acc + slot * 4ull;
+                atomicAdd(row + 0, (unsigned long long)n);
+                atomicAdd(row + 1, (unsigned long long)gx);
+                atomicAdd(row + 2, (unsigned long long)gy);
+                atomicAdd(row + 3, (unsigned long long)gz);
+                inserted += n;
+            } else {
+                dropped += n;
+            }
+        }
+    }
+    inserted = wave_sum(inserted);
+    dropped = wave_sum(dropped);
+    claimed = wave_sum(claimed);
+    if (lane == 0u) {
+        if (inserted) atomicAdd(a.stats + 0, (unsigned long long)inserted);
+        if (filtered) atomicAdd(a.stats + 1, (unsigned long long)filtered);
+        if (rejected) atomicAdd(a.stats + 2, (unsigned long long)rejected);
+        if (dropped) atomicAdd(a.stats + 3, (unsigned long long)dropped);
+        if (claimed) atomicAdd(a.stats + 4, (unsigned long long)claimed);
+    }
+}
+
+__global__ void map_cursor_kernel(unsigned long long *cursor)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) *cursor = 0ull;
+}
+
+struct MapExtract {
+    float voxel;
+    unsigned long long slots;       // C
+    unsigned long long max_out;
+    const unsigned long long *keys, *acc;
+    long long *out_key, *out_count;
+    float *out_xyz;
+    unsigned long long *cursor;
+};
+
+__device__ __forceinline__ float map_centroid(unsigned long long field, unsigned long long s, unsigned long long count, double voxel)
+{
+    const double i = (double)((long long)field - (1ll << 20));
+    return (float)((i + ((double)s / (double)count + 0.5) / 65536.0) * voxel);
+}
+
+// one thread per slot; the grid covers C exactly (C is a multiple of the block)
+__global__ __launch_bounds__(ELO_BLOCK) void map_extract_kernel(const MapExtract a)
+{
+    const unsigned long long s = (unsigned long long)blockIdx.x * ELO_BLOCK + threadIdx.x;
+    const unsigned lane = threadIdx.x & (MAP_WAVE - 1);
+    const unsigned long long key = s < a.slots ? a.keys[s] : MAP_EMPTY;
+    const bool full = key != MAP_EMPTY;
+    const unsigned long long m = __ballot(full);
+    if (m == 0ull) return;
+    unsigned long long base = 0ull;
+    if (lane == 0u) base = atomicAdd(a.cursor, (unsigned long long)__popcll(m));
+    base = __shfl(base, 0, MAP_WAVE);
+    if (!full) return;
+    const unsigned long long row = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+    if (row >= a.max_out) return;
+    const unsigned long long *acc = a.acc + s * 4ull;
+    const unsigned long long count = acc[0];
+    const double voxel = (double)a.voxel;
+    a.out_key[row] = (long long)key;
+    a.out_count[row] = (long long)count;
+    a.out_xyz[row * 3 + 0] = map_centroid(key >> 42 & 0x1fffffull, acc[1], count, voxel);
+    a.out_xyz[row * 3 + 1] = map_centroid(key >> 21 & 0x1fffffull, acc[2], count, voxel);
+    a.out_xyz[row * 3 + 2] = map_centroid(key & 0x1fffffull, acc[3], count, voxel);
+}
+
+#define ELO_REQUIRE(cond, who, what) \
+    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
+
+bool map_table_ok(float voxel, int log2_capacity)
+{
+    return voxel > 0.0f && voxel - voxel == 0.0f && log2_capacity >= ELO_MAP_MIN_LOG2 && log2_capacity <= ELO_MAP_MAX_LOG2;
+}
+
+bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
+
+}  // namespace
+}  // namespace elo
+
+using namespace elo;
+
+extern "C" int elo_map_insert(const elo_map_insert_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_map_insert";
+    ELO_REQUIRE(a, who, "null argument block");
+    ELO_REQUIRE(a->batch >= 0 && a->H >= 1 && a->W >= 1, who, "bad sizes");
+    ELO_REQUIRE((long)a->H * a->W <= (1l << 31) - 1 && (long)a->batch * a->H * a->W <= (1l << 31) - 1, who, "batch * H * W beyond 2^31");
+    ELO_REQUIRE(map_table_ok(a->voxel, a->log2_capacity), who, "voxel is positive and finite, log2_capacity ELO_MAP_MIN_LOG2 .. ELO_MAP_MAX_LOG2");
+    ELO_REQUIRE(a->min_range >= 0.0f, who, "min_range is >= 0");
+    ELO_REQUIRE(a->max_range > a->min_range, who, "max_range lies above min_range");
+    ELO_REQUIRE(a->xyz && a->pose && a->keys && a->acc && a->stats, who, "null pointer");
+    ELO_REQUIRE(aligned8(a->pose) && aligned8(a->keys) && aligned8(a->acc) && aligned8(a->stats), who,
+                "pose, keys, acc and stats must be 8-byte aligned");
+    if (a->batch == 0) return ELO_OK;
+    const long cells = (long)a->H * a->W;
+    const unsigned tiles = (unsigned)((cells + MAP_TILE - 1) / MAP_TILE);
+    const MapInsert m = {a->H, a->W, a->voxel, a->min_range, a->max_range, (1ull << a->log2_capacity) - 1ull, a->xyz, a->pose, a->keys,
+                         a->acc, a->stats, tiles, (cells % MAP_STRIP == 0 && ((uintptr_t)a->xyz & 15) == 0) ? 1 : 0};
+    const dim3 grid(tiles * (unsigned)a->batch);                        // < 2^21: batch * H * W < 2^31, 1024 cells a tile
+    hipLaunchKernelGGL(map_insert_kernel, grid, dim3(ELO_BLOCK), 0, (hipStream_t)stream, m);
+    return check_launch(who);
+}
+
+extern "C" int elo_map_extract(const elo_map_extract_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_map_extract";
+    ELO_REQUIRE(a, who, "null argument block");
+    ELO_REQUIRE(map_table_ok(a->voxel, a->log2_capacity), who, "voxel is positive and finite, log2_capacity ELO_MAP_MIN_LOG2 .. ELO_MAP_MAX_LOG2");
+    ELO_REQUIRE(a->max_out >= 0, who, "max_out is >= 0");
+    ELO_REQUIRE(a->keys && a->acc && a->out_key && a->out_count && a->out_xyz && a->cursor, who, "null pointer");
+    ELO_REQUIRE(aligned8(a->keys) && aligned8(a->acc) && aligned8(a->out_key) && aligned8(a->out_count) && aligned8(a->cursor), who,
+                "keys, acc, out_key, out_count and cursor must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned long long slots = 1ull << a->log2_capacity;
+    const MapExtract e = {a->voxel, slots, (unsigned long long)a->max_out, a->keys, a->acc, a->out_key, a->out_count, a->out_xyz, a->cursor};
+    hipLaunchKernelGGL(map_cursor_kernel, dim3(1), dim3(MAP_WAVE), 0, s, a->cursor);
+    hipLaunchKernelGGL(map_extract_kernel, dim3((unsigned)(slots / ELO_BLOCK)), dim3(ELO_BLOCK), 0, s, e);    // <= 2^20 workgroups
+    return check_launch(who);
+}

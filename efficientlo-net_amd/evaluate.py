@@ -17,7 +17,8 @@ import torch
 from . import kitti, pwclo_model
 from .local_model import DeviceTracker, ModelTracker
 from .distributed import quat2mat
-from .sensor import LocalModel
+from .sensor import LocalModel, VoxelMap
+from .world_map import WorldMap
 
 
 def pose_rows(q_n4, t_n3, Tr):
@@ -38,7 +39,7 @@ def pose_rows(q_n4, t_n3, Tr):
 
 
 def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_size=1, num_points=150000, frames=None,
-                     lanes=0, sensor=None, sweep=None, fit=None, model=None):
+                     lanes=0, sensor=None, sweep=None, fit=None, model=None, world_map=None):
     """Run the network over samples `frames` (default: all scans found) of sequence `seq`; returns (q (n,4), t (n,3))
     = the l0 pose of every sample, in sample order.  Batches are padded by repeating the last sample
     (main.py:497-509 keeps stale rows instead; either way the padding rows are dropped).
@@ -64,7 +65,16 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     device (local_model.DeviceTracker) and a sample is one replay of its recorded step -- on the sequential path, and with `lanes`:
     the lanes are then captured WITHOUT a fit, chunks are collected in order as before, and every sample of a collected chunk steps
     the one tracker on the range images of the lane's clouds and the lane's pose row; its result is on the host before the lane is
-    submitted again.  Without `model` nothing changes."""
+    submitted again.  Without `model` nothing changes.
+    `world_map` (world_map.WorldMap): every sample's frame-1 range image -- the one the net saw: with `sweep` the de-skewed one -- is
+    added to the map at the pose RETURNED for that sample (the net's, the fit's or the tracker's), in sample order (WorldMap.add:
+    the poses are composed onto the map's running world pose, which the caller resets between drives).  The images come from the
+    input stage run once more on the chunk's clouds -- the same launches on the same bytes, as the resident tracker's branch gets
+    them; the forward itself is untouched, so the return values are those of a run without the argument, bit for bit.  On the
+    sequential path and with `lanes` (inside the in-order collection; the lane is not written again before the insert has read its
+    clouds)."""
+    if world_map is not None and not isinstance(world_map, WorldMap):
+        raise TypeError("world_map is a WorldMap or None (got %r)" % (type(world_map).__name__,))
     if model is not None:
         if not isinstance(model, LocalModel):
             raise TypeError("model is a LocalModel or None (got %r)" % (type(model).__name__,))
@@ -84,7 +94,8 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     frames = list(frames)
     dev = net.device
     if lanes > 0:
-        return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit, model)
+        return _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit, model,
+                                       world_map)
     eye = torch.eye(4, dtype=torch.float32, device=dev).repeat(batch_size, 1, 1)      # main.py:308-309: no augmentation
     qs, ts, fits, tracker = [], [], [], None
     skew = {} if fit is None else {"fit": fit}
@@ -98,10 +109,10 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
         for j in range(batch_size):
             pos2, pos1, _n2, _n1, T = kitti.load_pair(root, seq, chunk[min(j, len(chunk) - 1)], T_diff, num_points)
             cloud[j, :num_points], cloud[j, num_points:], T_gt[j] = pos2, pos1, T     # main.py:316-320
+        motion = {k: v for k, v in skew.items() if k != "fit"}       # (this chunk's: skew moves on below)
         if model is not None:
             if tracker is None:
                 tracker = _tracker(net, H_input, W_input, model, fit)
-            motion = {k: v for k, v in skew.items() if k != "fit"}
             with torch.no_grad():                            # forward_points(fit=)'s own first half: the range images stay at hand
                 _pts, both = pwclo_model.input_stage(torch.from_numpy(cloud).to(dev), eye, np.ones(batch_size, np.int64), H_input,
                                                      W_input, sensor=net.sensor, beam_elev=net.beam_elev, **motion)
@@ -114,8 +125,11 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
             qs.append(pose[:, :4].copy())
             ts.append(pose[:, 4:].copy())
             fits.append(rows)
+            if world_map is not None:
+                world_map.add(both[:len(chunk)], pose)
             continue
-        out = net.forward_points(torch.from_numpy(cloud).to(dev), H_input, W_input, torch.from_numpy(T_gt).to(dev),
+        cloud_dev = torch.from_numpy(cloud).to(dev)
+        out = net.forward_points(cloud_dev, H_input, W_input, torch.from_numpy(T_gt).to(dev),
                                  eye, eye, is_training=False, aug_frame=np.ones(batch_size, np.int64), **skew)
         if sweep is not None:                                # [q_norm | t] of this chunk's last pair, for every pair of the next
             last = len(chunk) - 1
@@ -125,9 +139,14 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
             qs.append(pose[:, :4].copy())
             ts.append(pose[:, 4:].copy())
             fits.append(fit_rows(out[-1], len(chunk)))
-            continue
-        qs.append(out[0][:len(chunk)].reshape(-1, 4).cpu().numpy())
-        ts.append(out[1][:len(chunk)].reshape(-1, 3).cpu().numpy())
+        else:
+            qs.append(out[0][:len(chunk)].reshape(-1, 4).cpu().numpy())
+            ts.append(out[1][:len(chunk)].reshape(-1, 3).cpu().numpy())
+        if world_map is not None:
+            with torch.no_grad():
+                _pts, both = pwclo_model.input_stage(cloud_dev, eye, np.ones(batch_size, np.int64), H_input, W_input, sensor=net.sensor,
+                                                     beam_elev=net.beam_elev, **motion)
+            world_map.add(both[:len(chunk)], np.concatenate([qs[-1], ts[-1]], 1))
     return _stacked(qs, ts, fits, fit)
 
 
@@ -172,7 +191,8 @@ def _tracker(net, H_input, W_input, model, fit):
     return ModelTracker(H_input, W_input, model, fit, **kw)
 
 
-def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit=None, model=None):
+def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size, num_points, frames, lanes, fit=None, model=None,
+                            world_map=None):
     dev = net.device
     net.capture(batch_size, H_input, W_input, lanes=lanes, num_points=num_points, fit=fit if model is None else None)
     tracker = None if model is None else _tracker(net, H_input, W_input, model, fit)      # (recorded while no lane is in flight)
@@ -183,6 +203,7 @@ def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size
     def collect(ci):                                         # the lane's stream has finished chunk ci
         lane = ci % lanes
         net.lane_stream(lane).synchronize()
+        both = None
         if tracker is not None:
             # the range images of the lane's clouds: a lane that starts from raw clouds keeps them inside its graph (lane_input() is
             # the buffer of a lane fed with range images), so the input stage runs once more on the cloud buffer -- the same launches on
@@ -197,6 +218,13 @@ def _predict_sequence_lanes(net, root, seq, T_diff, H_input, W_input, batch_size
         else:
             pose = net.lane_pose(lane)[:len(chunks[ci])].cpu().numpy()    # (b,7) = [q_norm | t] of l0
         qs[ci], ts[ci] = pose[:, :4].copy(), pose[:, 4:].copy()
+        if world_map is not None:
+            if both is None:
+                with torch.no_grad():
+                    _pts, both = pwclo_model.input_stage(net.lane_cloud(lane), None, None, H_input, W_input, sensor=net.sensor,
+                                                         beam_elev=net.beam_elev)
+            world_map.add(both[:len(chunks[ci])], pose)
+            net.lane_stream(lane).wait_stream(torch.cuda.current_stream(dev))    # the next submit writes the clouds the stage reads
 
     for ci, chunk in enumerate(chunks):
         lane = ci % lanes
@@ -217,7 +245,13 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
     `poses_gt` ((n,12) absolute camera poses, e.g. ground_truth_pose/<seq>.txt) if given.
     Returns (rows (n,12), (t_rel %, r_rel deg/100m) or None).
     `fit=PoseFit(...)` (predict_sequence): the trajectory is built from the fit's poses and `<out_dir>/<seq>_fit.txt` holds one row
-    per sample: count, rms, status and the 21 unique entries of the information matrix."""
+    per sample: count, rms, status and the 21 unique entries of the information matrix.
+    `world_map=` a sensor.VoxelMap (a WorldMap is built for it on the net's device) or a world_map.WorldMap (used as it stands: reset
+    it between drives): the scans are added to it at the poses of the trajectory (predict_sequence) and `<out_dir>/<seq>_map.bin`
+    holds its voxels, float32 rows x y z count in the frame the first sample's pose leads to (WorldMap.save)."""
+    wmap = kw.get("world_map")
+    if isinstance(wmap, VoxelMap):
+        wmap = kw["world_map"] = WorldMap(wmap, device=net.device)
     q, t, *fit_out = predict_sequence(net, root, seq, T_diff, **kw)
     Tr = kitti.read_calib(os.path.join(root, seq, "calib.txt"))["Tr"]
     rows = pose_rows(q, t, Tr)
@@ -226,6 +260,8 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
         kitti.write_pred_txt(os.path.join(out_dir, "%s_pred.txt" % seq), rows)
         if fit_out:
             np.savetxt(os.path.join(out_dir, "%s_fit.txt" % seq), fit_out[0], fmt="%.9e")
+        if wmap is not None:
+            wmap.save(os.path.join(out_dir, "%s_map.bin" % seq))
     score = None
     if poses_gt is not None:
         score = kitti.overall(kitti.sequence_errors(np.asarray(poses_gt)[:len(rows)], rows))

@@ -14,6 +14,9 @@ is found and which instant the input stage carries the points to, given the sens
 `PoseFit` asks for the geometric fit of a relative pose on the pair's own range images (elo_pose_fit): residual, information
 matrix and, with iters > 0, Gauss-Newton steps on them.  `LocalModel` asks for that fit against the last few scans rendered into
 one range image (elo_model_render; local_model.ModelTracker) instead of against the pair's other scan.
+
+`VoxelMap` asks for the map the poses are for: every scan carried by its world pose into a hash table of voxels on the device
+(elo_map_insert; world_map.WorldMap).
 """
 import math
 
@@ -171,6 +174,39 @@ class LocalModel(_Frozen):
         if self.resident:
             return "LocalModel(scans=%r, resident=True)" % (self.scans,)
         return "LocalModel(scans=%r)" % (self.scans,)
+
+
+class VoxelMap(_Frozen):
+    """VoxelMap(voxel=0.5, log2_capacity=22, min_range=0.0, max_range=inf): the world map of a trajectory -- every scan carried by
+    its world pose into a hash table of voxels, each holding the count and the centroid of its points (elo_map_insert, include/elo.h;
+    world_map.WorldMap).  Frozen and hashable.
+    voxel (m): the edge of a voxel, finite and > 0; log2_capacity: the table has 1 << log2_capacity slots, an integer in 10 .. 28 (it
+    does not grow: points that find no slot are counted as dropped); min_range / max_range (m): a point whose range in its own scan
+    lies outside [min_range, max_range] is left out, 0 <= min_range < max_range, max_range may be inf."""
+    __slots__ = ("voxel", "log2_capacity", "min_range", "max_range")
+
+    def __init__(self, voxel=0.5, log2_capacity=22, min_range=0.0, max_range=math.inf):
+        if isinstance(log2_capacity, bool) or not hasattr(log2_capacity, "__index__"):
+            raise ValueError("log2_capacity is an integer (got %r)" % (log2_capacity,))
+        log2_capacity = log2_capacity.__index__()
+        if log2_capacity < 10 or log2_capacity > 28:
+            raise ValueError("log2_capacity is 10 .. 28 (got %d)" % log2_capacity)
+        voxel, min_range, max_range = float(voxel), float(min_range), float(max_range)
+        if not (math.isfinite(voxel) and voxel > 0):
+            raise ValueError("voxel must be positive and finite (got %r)" % (voxel,))
+        if not (math.isfinite(min_range) and min_range >= 0):
+            raise ValueError("min_range must be finite and >= 0 (got %r)" % (min_range,))
+        if not (max_range > min_range):
+            raise ValueError("max_range must lie above min_range (got %r, %r)" % (max_range, min_range))
+        self._freeze(voxel, log2_capacity, min_range, max_range)
+
+    def __repr__(self):
+        far = "inf" if math.isinf(self.max_range) else repr(self.max_range)
+        return "VoxelMap(voxel=%r, log2_capacity=%r, min_range=%r, max_range=%s)" % (self.voxel, self.log2_capacity, self.min_range, far)
+
+    @property
+    def capacity(self):
+        return 1 << self.log2_capacity
 
 
 def resolve(sensor):

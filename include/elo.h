@@ -713,6 +713,86 @@ typedef struct elo_model_advance_args {
 } elo_model_advance_args;
 int elo_model_advance(const elo_model_advance_args *a, elo_stream_t stream);
 
+/* WORLD MAP (csrc/elo_map.hip): a voxel-hashed point map of a trajectory, built on the device -- every scan's range image carried
+ * by its scan -> world pose and summed, per voxel, into INTEGERS, so that the map does not depend on the order of arrival.
+ * STATE of one map of capacity C = 1 << log2_capacity, three device buffers the caller owns:
+ *   keys   unsigned long long[C]: the voxel a slot holds; all ones = empty;
+ *   acc    unsigned long long[C][4] = {count, sx, sy, sz}: the points of the slot's voxel and the sums of their offsets g (below);
+ *   stats  unsigned long long[8] = {inserted, filtered, rejected, dropped_full, occupied, 0, 0, 0}, running totals.
+ *   RESET (the caller's, by device-side fills): keys to 0xFF bytes, acc and stats to zero.
+ * elo_map_insert, ONE launch.  xyz: (batch,H,W,3) range images; a cell that is exactly (0,0,0) is empty and counts nowhere.  pose:
+ *   (batch,7) DOUBLE [q | t], scan -> world, p' = R(q) p + t.
+ * ONE POINT p = (x, y, z), in this order:
+ *   pose       q is normalised in double; a scan whose quaternion has zero or non-finite norm is skipped whole and counts nothing
+ *              (elo_model_render's rule, taken from a double row);
+ *   range gate on the SOURCE point, in float32: rf = sqrtf(x*x + y*y + z*z) (summed left to right); rf < min_range or rf >
+ *              max_range -> `filtered` (a NaN rf is neither: the point goes on and is rejected below);
+ *   carry      in double from the float32 inputs, p'_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i, R(q) as elo_model_render forms it;
+ *              each component is rounded to float32 ONCE;
+ *   rejection  a non-finite component of the rounded p' -> `rejected`;
+ *   index      per axis u = (double)x' / (double)voxel (a division, not a reciprocal multiply), i = floor(u) (floor, not
+ *              truncation: negative coordinates work); i must lie in [-2^20, 2^20) -- checked in double before any integer
+ *              conversion --, else -> `rejected`;
+ *   offset     g = min((unsigned)floor((u - i) * 65536.0), 65535) per axis;
+ *   Every step after the one rounding to float32 is a single IEEE operation with no multiply-add to contract: a float64 / uint64
+ *   restatement reproduces it bit for bit.
+ *   key        (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20); its top bit is clear, so all ones is never a key;
+ *   home slot  the splitmix64 finaliser of the key, & (C - 1):  h = key; h ^= h >> 30; h *= 0xbf58476d1ce4e5b9; h ^= h >> 27;
+ *              h *= 0x94d049bb133111eb; h ^= h >> 31;
+ *   probing    linear: slot (home + j) & (C - 1), j = 0 .. ELO_MAP_MAX_PROBE - 1.  A slot holding the key is found.  An empty slot
+ *              is claimed by a 64-bit atomicCAS(empty -> key), won if the CAS returns empty or the key; the thread that turns an
+ *              empty slot into the key adds 1 to `occupied`.  No slot within the limit -> `dropped_full`, nothing else touched;
+ *   sums       the found slot gets integer atomic adds count += 1, sx += gx, sy += gy, sz += gz; the point counts in `inserted`.
+ *   Neighbouring cells of one wave that share a key (a run; cells without a point do not end it) are summed in registers first and
+ *   sent as ONE probe and four adds (and are dropped together where the table is full); the counters are summed per wave.  Sums of
+ *   integers: the result is that of one add per point.
+ * DETERMINED: as long as dropped_full == 0, the CONTENT of the map -- the set of keys, each with its four integers -- and `stats`
+ *   are a function of the multiset of points inserted: not of launch order, scan order, batch split or races.  Two runs, and an
+ *   eager run and a graph replay, agree bit for bit in content.  NOT DETERMINED: the PLACEMENT of keys in slots (which of two
+ *   colliding keys sits nearer its home); nothing may depend on it -- compare maps after sorting by key.  With dropped_full > 0
+ *   which points were dropped depends on the races too; what is stored is still consistent (no key twice, every count that of the
+ *   points inserted for it).
+ * Every loop in the kernels has a static trip bound; nothing waits on another thread.  No host synchronisation; capturable.  The
+ *   grid is a fixed function of (batch, H, W).  16-byte loads where H * W is a multiple of 4 and xyz is 16-byte aligned, one float
+ *   at a time otherwise.
+ * ELO_ERR_ARG (nothing is launched): a NULL pointer, H < 1, W < 1, batch < 0, batch * H * W at or beyond 2^31, a voxel that is not
+ *   positive and finite, a negative or NaN min_range, max_range <= min_range (or NaN), log2_capacity outside ELO_MAP_MIN_LOG2 ..
+ *   ELO_MAP_MAX_LOG2, keys / acc / stats / pose not 8-byte aligned.  An empty batch launches nothing and is ELO_OK.
+ * elo_map_extract: the occupied slots compacted into rows, in ARBITRARY order (ballot compaction within a wave, one integer atomic
+ *   on the cursor per wave).  cursor: one device word, cleared by the call itself (its first launch), which ends at the number of
+ *   occupied slots even where that exceeds max_out; only rows < max_out are written.  Row of a slot: out_key = its key, out_count =
+ *   its count, out_xyz = the centroid, per axis, every step one IEEE operation in double,
+ *     c = ((double)i + ((double)s / (double)count + 0.5) / 65536.0) * (double)voxel,   i = the key's field - 2^20,
+ *   rounded to float32 once.  Two launches; capturable.  ELO_ERR_ARG: a NULL pointer, max_out < 0, a bad voxel or log2_capacity,
+ *   keys / acc / cursor / out_key / out_count not 8-byte aligned.
+ * LIFETIME as elo_model_render's.  Additive to ABI 26: no existing struct changes. */
+#define ELO_MAP_MAX_PROBE 128
+#define ELO_MAP_MIN_LOG2 10
+#define ELO_MAP_MAX_LOG2 28
+typedef struct elo_map_insert_args {
+    int batch, H, W;
+    float voxel, min_range, max_range;  /* m; max_range may be +inf */
+    int log2_capacity;
+    const float *xyz;             /* (batch,H,W,3); an all-zero cell is empty */
+    const double *pose;           /* (batch,7) [q | t] DOUBLE: scan -> world */
+    unsigned long long *keys;     /* [C] IN/OUT */
+    unsigned long long *acc;      /* [C][4] IN/OUT */
+    unsigned long long *stats;    /* [8] IN/OUT */
+} elo_map_insert_args;
+int elo_map_insert(const elo_map_insert_args *a, elo_stream_t stream);
+typedef struct elo_map_extract_args {
+    float voxel;
+    int log2_capacity;
+    long max_out;                 /* rows the outputs hold, >= 0 */
+    const unsigned long long *keys;
+    const unsigned long long *acc;
+    long long *out_key;           /* [max_out] OUT */
+    long long *out_count;         /* [max_out] OUT */
+    float *out_xyz;               /* [max_out][3] OUT */
+    unsigned long long *cursor;   /* one word OUT: the number of occupied slots */
+} elo_map_extract_args;
+int elo_map_extract(const elo_map_extract_args *a, elo_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * Backward passes of the feature kernels above, for TRAINING (csrc/elo_backward.hip).
  * The reference trains through TensorFlow's autodiff of its stock ops (main.py:171-176): gather_nd -> scatter-add of
