@@ -1668,27 +1668,64 @@ struct RrStream {
     __device__ __forceinline__ void prime() { commit(0); issue(RR_STAGE); }   // superstep 0 into the ring (then: rr_barrier())
 };
 
-// One layer on the wave's 16 rows.  in[p]: operand pairs, tail: the 16-k tail block (TAIL); NCB column blocks, two per
-// pass, a pass = KP pair steps (+ the tail step).  The W stream of the WHOLE kernel is one sequence of steps (layer by
-// layer, pass by pass), two steps = one superstep = one ring slot.  Every step reads its operands from the ring (fetch:
+// The biases of a chain's layers, concatenated, into the workgroup's LDS table (words RR_BIAS_OFF ...: behind the ring and the
+// set-conv grouping scratch, inside the pooling scratch -- dead, like the ring, by the time the pooling writes).  The layout comes
+// from the plan: layer l has 16 * NCB[l] floats.  One float per thread, requested at kernel start and written before the first
+// rr_barrier(): hence total() <= the workgroup's threads.
+constexpr int RR_BIAS_OFF = 8192;
+template <class PLAN>
+struct RrBiasTable {
+    static __device__ __forceinline__ constexpr int width(int l) { return 16 * PLAN::NCB[l]; }
+    static __device__ __forceinline__ constexpr int offset(int l) { int o = 0; for (int i = 0; i < l; ++i) o += width(i); return o; }
+    static __device__ __forceinline__ constexpr int total() { return offset(PLAN::NL); }
+    template <int L> static __device__ __forceinline__ const float *layer(const void *lds) { return reinterpret_cast<const float *>(lds) + RR_BIAS_OFF + offset(L); }
+    // layer 0's quads of pass 0, straight from global: the table is not there yet
+    static __device__ __forceinline__ void first_quads(const float *b0, int kq, float4 (&bias0)[2])
+    {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) bias0[t] = *reinterpret_cast<const float4 *>(b0 + t * 16 + 4 * kq);
+    }
+    static __device__ __forceinline__ float request(const float *const (&b)[PLAN::NL], int tid)      // this thread's word of the table
+    {
+        static_assert(total() <= RR_WAVES * 64, "the bias table is filled one float per thread");
+        int at = tid;
+        const float *src = b[0];                    // (clamped: every thread loads something)
+        bool found = false;
+#pragma unroll
+        for (int l = 0; l < PLAN::NL; ++l) {
+            if (!found && at < width(l)) { src = b[l] + at; found = true; }
+            at -= width(l);
+        }
+        return *src;
+    }
+    static __device__ __forceinline__ void store(float *lds, int tid, float v) { if (tid < total()) lds[RR_BIAS_OFF + tid] = v; }
+};
+
+// One layer on the wave's 16 rows: layer L of PLAN, which gives its KP pair steps (+ the tail step: TL), its NCB column blocks, its
+// first step in the W stream and its place in the bias table.  in[p]: operand pairs, tail: the 16-k tail block; two column blocks
+// per pass, a pass = KP pair steps (+ the tail step).  The W stream of the WHOLE kernel is one sequence of steps (layer by
+// layer, pass by pass), two steps = one superstep = one ring slot.  Every step reads its operands from the ring (ws.fetch:
 // the slot is complete since the last barrier); at the end of an odd step the wave moves its chunk of the NEXT superstep
-// from its staging register into the other slot, requests a later one (advance), and joins the barrier.  G0 = this
-// layer's first step.  bias0: the bias quads of pass 0 on entry, of `next_bias`'s pass 0 on exit.  The biases of later passes
-// come from the workgroup's LDS table (rr_stage_biases): as global loads one pass ahead they were a dependent L2 round trip
+// from its staging register into the other slot, requests a later one (ws.advance), and joins the barrier.
+// bias0: the bias quads of pass 0 on entry, of the next layer's pass 0 on exit (the last layer has none).  The biases of later passes
+// come from the workgroup's LDS table (RrBiasTable): as global loads one pass ahead they were a dependent L2 round trip
 // PER PASS -- a pass is 100-1000 cycles of work, the round trip ~700 under load: tools/rr_clock.sh showed ~500 + 250 k cycles
 // for a pass of k steps whatever the MFMA count, and a build without any MFMA ran as long.
 // emit(pass, t, acc): epilogue of column block 2*pass + t.
 // XMASK bit k: pair k of `in` holds exact fp16 values (lo == 0); XTAIL: so does the tail block -- see mma_pair's A_EXACT
 // init(cb, b): the accumulators' initial value for column block cb, given the block's bias quad b (default: the bias itself).
 struct RrBiasInit { __device__ __forceinline__ f32x4 operator()(int, const float4 b) const { return f32x4{b.x, b.y, b.z, b.w}; } };
-template <int KP, bool TAIL, int NCB, int G0, int MODE = MODE_SPLIT, unsigned XMASK = 0u, bool XTAIL = false, class Fetch, class Advance, class Emit,
-          class Init = RrBiasInit>
-__device__ __forceinline__ void rr_layer(const ActPair (&in)[KP > 0 ? KP : 1], const uint4 &tail, const float *bias,
-                                         const float *next_bias, float4 (&bias0)[2], Fetch fetch, Advance advance, Emit emit, Init init = Init())
-// (L.bias / next_bias: this layer's and the next one's biases IN THE LDS TABLE, see rr_stage_biases)
+template <class PLAN, int L, int MODE = MODE_SPLIT, unsigned XMASK = 0u, bool XTAIL = false, class Emit, class Init = RrBiasInit>
+__device__ __forceinline__ void rr_layer(RrStream<PLAN, MODE> &ws, const ActPair (&in)[PLAN::KP[L] > 0 ? PLAN::KP[L] : 1], const uint4 &tail,
+                                         float4 (&bias0)[2], Emit emit, Init init = Init())
 {
+    static_assert(L < PLAN::NL, "a layer of the plan");
+    constexpr int KP = PLAN::KP[L], NCB = PLAN::NCB[L], G0 = RrStream<PLAN, MODE>::first(L);
+    constexpr bool TAIL = PLAN::TL[L] != 0;
     constexpr int PASSES = NCB / 2, SPP = KP + (TAIL ? 1 : 0);
     static_assert(G0 % 2 == 0 && (PASSES * SPP) % 2 == 0, "a superstep never straddles two layers");
+    static_assert(sizeof(in) == (KP > 0 ? KP : 1) * sizeof(ActPair), "exactly max(KP, 1) operand pairs");
+    const float *bias = RrBiasTable<PLAN>::template layer<L>(ws.ring), *next_bias = RrBiasTable<PLAN>::template layer<L + 1>(ws.ring);
     const int kq = (threadIdx.x & 63) >> 4;
     f32x4 acc[1][2];
     float4 bnext[2] = {bias0[0], bias0[1]};
@@ -1699,7 +1736,10 @@ __device__ __forceinline__ void rr_layer(const ActPair (&in)[KP > 0 ? KP : 1], c
         if (pass + 1 < PASSES) {                                    // the next pass's bias quads, a pass ahead
 #pragma unroll
             for (int t = 0; t < 2; ++t) bnext[t] = *reinterpret_cast<const float4 *>(bias + (2 * (pass + 1) + t) * 16 + 4 * kq);
-        } else if (next_bias) {
+        } else if (L + 1 < PLAN::NL) {
+            // a scheduling boundary per layer (no instruction: the scheduler's regions end here).  The chain is straight-line code at
+            // 120-128 VGPRs; scheduled as ONE region cv2 <64, fp32> and mlp2 <32, fp32> spilled 4 registers each.
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < 2; ++t) bnext[t] = *reinterpret_cast<const float4 *>(next_bias + t * 16 + 4 * kq);
         }
@@ -1707,7 +1747,7 @@ __device__ __forceinline__ void rr_layer(const ActPair (&in)[KP > 0 ? KP : 1], c
         for (int k = 0; k < SPP; ++k) {
             const int g = G0 + pass * SPP + k;
             RrW cur;
-            fetch(g, cur);                                           // (the other waves of the SIMD cover the LDS round trip)
+            ws.fetch(g, cur);                                        // (the other waves of the SIMD cover the LDS round trip)
             if (k < KP) {
                 const ActPair a1[1] = {in[k < KP ? k : 0]};
                 const WPair w2[2] = {cur.w[0], cur.w[1]};
@@ -1718,7 +1758,7 @@ __device__ __forceinline__ void rr_layer(const ActPair (&in)[KP > 0 ? KP : 1], c
                 const uint4 w2[2] = {cur.w[0].hi, cur.w[1].hi};
                 mma_tail<MODE, 2, 1, 2, (KP > 0), XTAIL>(acc, 0, a1, w2);
             }
-            if (g % 2 == 1) advance(g / 2);
+            if (g % 2 == 1) ws.advance(g / 2);
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) emit(pass, t, acc[0][t]);
@@ -1750,6 +1790,88 @@ __device__ __forceinline__ float4 quad_value(unsigned h01_, unsigned h23_, unsig
     const half2v l01 = __builtin_bit_cast(half2v, l01_), l23 = __builtin_bit_cast(half2v, l23_);
     return float4{(float)h01.x + (float)l01.x, (float)h01.y + (float)l01.y, (float)h23.x + (float)l23.x, (float)h23.y + (float)l23.y};
 }
+
+// ---- the row vocabulary of the chain kernels.  Loads are only REQUESTED by rr_gather / geo_load / rr_group_row and only CONVERTED
+// by rr_quad / rr_geo_quad, so that a kernel keeps every request in front of ws.prime() and every conversion behind it.
+struct RrLane {                                    // lane (i16, kq) of wave `wave` works on row r of the workgroup's 128
+    int lane, wave, i16, kq, r;
+    __device__ __forceinline__ RrLane() : lane(threadIdx.x & 63), wave(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)),
+                                          i16(lane & 15), kq(lane >> 4), r(wave * 16 + i16) {}
+};
+
+// A row of a grouped kernel whose neighbours come from idx / mask: row r = point * K + slot of the workgroup's P points.  pt: its
+// centre, cell: its neighbour's cell of the (H, W) grid, mk: its mask (0 for a row not in use), keep2 = the neighbour counts.
+// Rows not in use read the first point's words.
+struct RrGroupRow { long pt; int cell; float mk; bool used, keep2; };
+__device__ __forceinline__ RrGroupRow rr_group_row(const int *idx, const float *mask, int r, int K, int P, long first_point, long total_points,
+                                                   int H, int W)
+{
+    const int pi = small_div(r, K);
+    long pt = first_point + pi;
+    const bool used = pi < P && pt < total_points;
+    if (!used) pt = first_point;
+    const long gr = used ? pt * K + (r - pi * K) : first_point * K;
+    const int id0 = idx[gr * 3 + 0], id1 = idx[gr * 3 + 1], id2 = idx[gr * 3 + 2];
+    float mk = mask[gr];
+    const int cell = (id0 * H + id1) * W + id2;
+    if (!used) mk = 0.0f;
+    return RrGroupRow{pt, cell, mk, used, used && mk != 0.0f};
+}
+
+// quad kq of a row's geometry block [p, g*m, g*m - p, |g*m - p|, 0 ...]: the chain form of geo_load / geo_store's rule
+template <int MODE>
+__device__ __forceinline__ uint4 rr_geo_quad(const GeoRow &row, float m, bool used, int kq, unsigned &violations)
+{
+    const float g0 = row.g[0] * m, g1 = row.g[1] * m, g2 = row.g[2] * m;
+    const float d0 = g0 - row.p[0], d1 = g1 - row.p[1], d2 = g2 - row.p[2];
+    const float e = sqrtf(d0 * d0 + d1 * d1 + d2 * d2 + 1e-20f);
+    const float4 q4 = kq == 0 ? float4{row.p[0], row.p[1], row.p[2], g0} : kq == 1 ? float4{g1, g2, d0, d1}
+                    : kq == 2 ? float4{d2, e, 0.0f, 0.0f} : float4{0.0f, 0.0f, 0.0f, 0.0f};
+    return used ? pack_quad<MODE>(q4, violations) : uint4{0u, 0u, 0u, 0u};
+}
+
+template <bool F16> using RrItem = typename std::conditional<F16, uint2, float4>::type;      // 4 channels as stored
+
+// quad kq of block 0 of row `row` of a [rows, C] tensor; rr_gather requests that quad of the row's first N 16-channel blocks
+template <bool F16>
+__device__ __forceinline__ const RrItem<F16> *rr_row(const void *base, long row, int C, int kq)
+{
+    return reinterpret_cast<const RrItem<F16> *>(base) + (row * C >> 2) + kq;
+}
+template <class Item, int N>
+__device__ __forceinline__ void rr_gather(Item (&f)[N], const Item *p)
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j) f[j] = p[j * 4];
+}
+
+template <bool F16, int MODE>
+__device__ __forceinline__ uint4 rr_quad(const RrItem<F16> &v, bool keep, unsigned &violations)
+{
+    const uint4 z{0u, 0u, 0u, 0u};
+    if constexpr (F16) return keep ? quad_of_halves(v) : z;
+    else return keep ? pack_quad<MODE>(v, violations) : z;
+}
+
+// block b of a concatenation goes to half b % 2 of pair b / 2, the last block of an odd count to the tail  (b: a constant after unrolling)
+template <int NP>
+__device__ __forceinline__ void rr_put_block(ActPair (&pairs)[NP], uint4 &tail, int b, const uint4 q)
+{
+    if (b / 2 < NP) put_quad(pairs[b / 2 < NP ? b / 2 : 0], b % 2, q);
+    else tail = q;
+}
+
+// The two epilogues of rr_layer.  RrToPairs: ReLU, operand format, column block cb becomes block cb of dst (the next layer's input);
+// RrToQuads: ReLU, plain fp32 quads (a last layer: what the pooling or the store reads).
+template <int MODE>
+struct RrToPairs {
+    ActPair *dst; int relu; unsigned &violations;
+    __device__ __forceinline__ void operator()(int pass, int t, const f32x4 acc) const { put_quad(dst[pass], t, pack_quad<MODE>(relu4(acc, relu), violations)); }
+};
+struct RrToQuads {
+    float4 *dst; int relu;
+    __device__ __forceinline__ void operator()(int pass, int t, const f32x4 acc) const { dst[2 * pass + t] = relu4(acc, relu); }
+};
 
 // The tail of a register-resident chain: masked softmax over the K rows of a point of the 64 logits, weighted sum of the
 // 64 values (two operand pairs: hi + lo is the value, as the tile kernels' act_get reads it), 32 channels at a time: the
@@ -1893,25 +2015,6 @@ __device__ __forceinline__ void rr_pool_softmax4_inwave(const float4 (&logit)[4]
     }
 }
 
-// The biases of a chain's layers, concatenated, into the workgroup's LDS table (words RR_BIAS_OFF ...: behind the ring and the
-// set-conv grouping scratch, inside the pooling scratch -- dead, like the ring, by the time the pooling writes).  One float
-// per thread (<= 512 in all), requested at kernel start and written before the first rr_barrier().
-constexpr int RR_BIAS_OFF = 8192;
-template <int NL>
-__device__ __forceinline__ float rr_bias_request(const float *const (&b)[NL], const int (&n)[NL], int tid)
-{
-    int at = tid;
-    const float *src = b[0];                        // (clamped: every thread loads something)
-    bool found = false;
-#pragma unroll
-    for (int l = 0; l < NL; ++l) {
-        if (!found && at < n[l]) { src = b[l] + at; found = true; }
-        at -= n[l];
-    }
-    return *src;
-}
-__device__ __forceinline__ void rr_bias_store(float *lds, int tid, int total, float v) { if (tid < total) lds[RR_BIAS_OFF + tid] = v; }
-
 template <int FP> struct Cv1Plan {   // CV_0 (FP pairs + geometry tail -> 128), CV_1, CV_2, CV_xyz (tail -> 64), sum_CV_0, sum_CV_1
     static constexpr int NL = 6;
     static constexpr int KP[6] = {FP, 4, 2, 0, 4, 4}, TL[6] = {1, 0, 0, 1, 0, 0}, NCB[6] = {8, 4, 4, 4, 8, 4};
@@ -1923,105 +2026,64 @@ __device__ __forceinline__ void cv1_rr_body(const elo_cv1_args &a, const unsigne
 {
     extern __shared__ __align__(16) float lds[];
     constexpr int FP = C / 16;                       // 16-channel blocks per feature tensor; CV_0's pairs: FP (feat1 | feat2 blocks paired up)
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i16 = lane & 15, kq = lane >> 4;
-    uint4 *ring = reinterpret_cast<uint4 *>(lds);    // [2 slots][8 chunks][64 lanes] x 16 bytes
+    typedef Cv1Plan<FP> PL;
+    typedef RrBiasTable<PL> Biases;
+    const RrLane ln;
     const int K = a.K, P = RR_ROWS / K;              // points per workgroup: rows r = point * K + slot, r < P * K <= 128
     const long total_points = (long)a.batch * a.npoints;
     const long first_point = (long)xcd_tile(block, nblocks) * P;
     unsigned bad = 0;
     RR_STAMP(0);
     // ---- the W stream.  Steps per layer: CV_0 4*(FP+1), CV_1 2*4, CV_2 2*2, CV_xyz 2*1, sum_CV_0 4*4, sum_CV_1 2*4
-    typedef RrStream<Cv1Plan<FP>, MODE> Stream;
-    Stream ws{{a.cv0.w_packed, a.cv1.w_packed, a.cv2.w_packed, a.cv_xyz.w_packed, a.sum_cv0.w_packed, a.sum_cv1.w_packed}, ring, wave, lane, {}};
-    constexpr int E0 = Stream::first(1), E1 = Stream::first(2), E2 = Stream::first(3), E3 = Stream::first(4), E4 = Stream::first(5);
-    auto fetch = [&](int g, RrW &dst) { ws.fetch(g, dst); };
-    auto advance = [&](int S) { ws.advance(S); };
+    RrStream<PL, MODE> ws{{a.cv0.w_packed, a.cv1.w_packed, a.cv2.w_packed, a.cv_xyz.w_packed, a.sum_cv0.w_packed, a.sum_cv1.w_packed},
+                          reinterpret_cast<uint4 *>(lds), ln.wave, ln.lane, {}};       // ring: [2 slots][8 chunks][64 lanes] x 16 bytes
     ws.start();
     float4 bias[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) bias[t] = *reinterpret_cast<const float4 *>(a.cv0.bias + t * 16 + 4 * kq);
+    Biases::first_quads(a.cv0.bias, ln.kq, bias);
     const float *const bsrc[6] = {a.cv0.bias, a.cv1.bias, a.cv2.bias, a.cv_xyz.bias, a.sum_cv0.bias, a.sum_cv1.bias};
-    constexpr int BN[6] = {128, 64, 64, 64, 128, 64}, B1 = 128, B2 = 192, B3 = 256, B4 = 320, B5 = 448;     // table offsets
-    const float bias_word = rr_bias_request(bsrc, BN, (int)threadIdx.x);
-    const float *bt = lds + RR_BIAS_OFF;
-    // ---- row metadata + gather, every load requested before the first use (this lane's row: r = wave * 16 + i16)
-    const int r = wave * 16 + i16, pi = small_div(r, K);
-    long pt = first_point + pi;
-    const bool used = pi < P && pt < total_points;
-    if (!used) pt = first_point;
-    const long gr = used ? pt * K + (r - pi * K) : first_point * K;
-    const int id0 = a.idx[gr * 3 + 0], id1 = a.idx[gr * 3 + 1], id2 = a.idx[gr * 3 + 2];
-    float mk = a.mask[gr];
-    const int cell = (id0 * a.H2 + id1) * a.W2 + id2;
-    if (!used) mk = 0.0f;
-    const bool keep2 = used && mk != 0.0f;
+    const float bias_word = Biases::request(bsrc, (int)threadIdx.x);
+    // ---- row metadata + gather, every load requested before the first use
+    const RrGroupRow row = rr_group_row(a.idx, a.mask, ln.r, K, P, first_point, total_points, a.H2, a.W2);
     ActPair in0[FP];                                 // CV_0's input pairs: [feat1 | feat2] blocks, two per pair
-    uint4 geo;                                       // its tail: quad kq of [p, g*m, g*m - p, |g*m - p|, 0 ...]
+    uint4 geo;                                       // its tail: quad kq of the geometry block
     {
-        typedef typename std::conditional<F16, uint2, float4>::type Item;     // 4 channels
-        Item f1[FP], f2[FP];
-        const Item *r1 = reinterpret_cast<const Item *>(a.feat1) + (pt * C >> 2) + kq;
-        const Item *r2 = reinterpret_cast<const Item *>(a.feat2) + ((long)cell * C >> 2) + kq;
-#pragma unroll
-        for (int j = 0; j < FP; ++j) { f1[j] = r1[j * 4]; f2[j] = r2[j * 4]; }
-        const float *c = a.xyz1 + pt * 3, *g = a.xyz2 + (long)cell * 3;
-        const float pc0 = c[0], pc1 = c[1], pc2 = c[2], pg0 = g[0], pg1 = g[1], pg2 = g[2];
+        RrItem<F16> f1[FP], f2[FP];
+        const RrItem<F16> *r1 = rr_row<F16>(a.feat1, row.pt, C, ln.kq), *r2 = rr_row<F16>(a.feat2, row.cell, C, ln.kq);
+        rr_gather(f1, r1);
+        rr_gather(f2, r2);
+        const GeoRow xyz = geo_load(a.xyz1 + row.pt * 3, a.xyz2 + (long)row.cell * 3);
         ws.prime();                                  // superstep 0 into the ring (its load went out first)
-        auto quad = [&](const Item &v, bool keep) {
-            const uint4 z{0u, 0u, 0u, 0u};
-            if constexpr (F16) return keep ? quad_of_halves(v) : z;
-            else return keep ? pack_quad<MODE>(v, bad) : z;
-        };
-        // CV_0's k-blocks in order: feat1 blocks 0..FP-1, feat2 blocks 0..FP-1, geometry; block b sits in pair b / 2, half b % 2
+        // CV_0's k-blocks in order: feat1 blocks 0..FP-1, feat2 blocks 0..FP-1, geometry (the tail)
 #pragma unroll
-        for (int j = 0; j < FP; ++j) put_quad(in0[j / 2], j % 2, quad(f1[j], used));
+        for (int j = 0; j < FP; ++j) rr_put_block(in0, geo, j, rr_quad<F16, MODE>(f1[j], row.used, bad));
 #pragma unroll
-        for (int j = 0; j < FP; ++j) put_quad(in0[(FP + j) / 2], (FP + j) % 2, quad(f2[j], keep2));
-        const float g0 = pg0 * mk, g1 = pg1 * mk, g2 = pg2 * mk;
-        const float d0 = g0 - pc0, d1 = g1 - pc1, d2 = g2 - pc2;
-        const float e = sqrtf(d0 * d0 + d1 * d1 + d2 * d2 + 1e-20f);
-        const float4 q4 = kq == 0 ? float4{pc0, pc1, pc2, g0} : kq == 1 ? float4{g1, g2, d0, d1}
-                        : kq == 2 ? float4{d2, e, 0.0f, 0.0f} : float4{0.0f, 0.0f, 0.0f, 0.0f};
-        geo = used ? pack_quad<MODE>(q4, bad) : uint4{0u, 0u, 0u, 0u};
+        for (int j = 0; j < FP; ++j) rr_put_block(in0, geo, FP + j, rr_quad<F16, MODE>(f2[j], row.keep2, bad));
+        rr_put_block(in0, geo, 2 * FP, rr_geo_quad<MODE>(xyz, row.mk, row.used, ln.kq, bad));
     }
-    rr_bias_store(lds, (int)threadIdx.x, 512, bias_word);
+    Biases::store(lds, (int)threadIdx.x, bias_word);
     RR_STAMP(1);
     rr_barrier();                                    // superstep 0 is in the ring
     RR_LAYER_STAMP(2);
     // ---- the chain
     const uint4 none{0u, 0u, 0u, 0u};
+    const ActPair unused[1] = {};                    // (the operand pairs of a layer that has only a tail)
     ActPair h128[4];                                 // CV_0's output (128 channels = 4 pairs)
-    auto emit0 = [&](int pass, int t, const f32x4 acc) { put_quad(h128[pass], t, pack_quad<MODE>(relu4(acc, a.cv0.relu), bad)); };
-    rr_layer<FP, true, 8, 0, MODE, (F16 ? ~0u : 0u)>(in0, geo, bt, bt + B1, bias, fetch, advance, emit0);
+    rr_layer<PL, 0, MODE, (F16 ? ~0u : 0u)>(ws, in0, geo, bias, RrToPairs<MODE>{h128, a.cv0.relu, bad});
     RR_LAYER_STAMP(3);
     ActPair h64[2];
-    rr_layer<4, false, 4, E0, MODE>(h128, none, bt + B1, bt + B2, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-        put_quad(h64[pass], t, pack_quad<MODE>(relu4(acc, a.cv1.relu), bad));
-    });
+    rr_layer<PL, 1, MODE>(ws, h128, none, bias, RrToPairs<MODE>{h64, a.cv1.relu, bad});
     RR_LAYER_STAMP(4);
     ActPair xe[4];                                   // [x | enc]: sum_CV_0's input; x stays alive: it is the pooling's value
-    rr_layer<2, false, 4, E1, MODE>(h64, none, bt + B2, bt + B3, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-        put_quad(xe[pass], t, pack_quad<MODE>(relu4(acc, a.cv2.relu), bad));
-    });
+    rr_layer<PL, 2, MODE>(ws, h64, none, bias, RrToPairs<MODE>{xe, a.cv2.relu, bad});
     RR_LAYER_STAMP(5);
-    {
-        ActPair unused[1];
-        rr_layer<0, true, 4, E2, MODE>(unused, geo, bt + B3, bt + B4, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-            put_quad(xe[2 + pass], t, pack_quad<MODE>(relu4(acc, a.cv_xyz.relu), bad));
-        });
-    }
+    rr_layer<PL, 3, MODE>(ws, unused, geo, bias, RrToPairs<MODE>{xe + 2, a.cv_xyz.relu, bad});
     RR_LAYER_STAMP(6);
-    rr_layer<4, false, 8, E3, MODE>(xe, none, bt + B4, bt + B5, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-        put_quad(h128[pass], t, pack_quad<MODE>(relu4(acc, a.sum_cv0.relu), bad));
-    });
+    rr_layer<PL, 4, MODE>(ws, xe, none, bias, RrToPairs<MODE>{h128, a.sum_cv0.relu, bad});
     RR_LAYER_STAMP(7);
     float4 logit[4];                                 // plain fp32, held until the ring is dead
-    rr_layer<4, false, 4, E4, MODE>(h128, none, bt + B5, nullptr, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-        logit[2 * pass + t] = relu4(acc, a.sum_cv1.relu);
-    });
+    rr_layer<PL, 5, MODE>(ws, h128, none, bias, RrToQuads{logit, a.sum_cv1.relu});
     RR_STAMP(8);
-    rr_pool<F16>(lds, logit, xe[0], xe[1], mk, r, wave, lane, K, P, first_point, total_points, a.out);
+    rr_pool<F16>(lds, logit, xe[0], xe[1], row.mk, ln.r, ln.wave, ln.lane, K, P, first_point, total_points, a.out);
     RR_STAMP(9);
     report_violations<MODE>(bad, a.range_counter);
 }
@@ -2043,89 +2105,48 @@ template <int C, bool F16, int MODE = MODE_SPLIT>
 __global__ __launch_bounds__(RR_WAVES * 64, 4) void cv2_rr_kernel(const elo_cv2_args a)
 {
     extern __shared__ __align__(16) float lds[];
-    constexpr int FP = C / 16, KP1 = 4 + C / 32;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i16 = lane & 15, kq = lane >> 4;
+    typedef Cv2Plan<C> PL;
+    typedef RrBiasTable<PL> Biases;
+    constexpr int FP = C / 16;
+    const RrLane ln;
     const int K = a.K, P = RR_ROWS / K;
     const long total_points = (long)a.batch * a.npoints;
     const long first_point = (long)xcd_tile(blockIdx.x, gridDim.x) * P;
     unsigned bad = 0;
-    typedef RrStream<Cv2Plan<C>, MODE> Stream;
-    Stream ws{{a.xyz_enc.w_packed, a.sum_cost0.w_packed, a.sum_cost1.w_packed}, reinterpret_cast<uint4 *>(lds), wave, lane, {}};
-    constexpr int E0 = Stream::first(1), E1 = Stream::first(2);
-    auto fetch = [&](int g, RrW &dst) { ws.fetch(g, dst); };
-    auto advance = [&](int S) { ws.advance(S); };
+    RrStream<PL, MODE> ws{{a.xyz_enc.w_packed, a.sum_cost0.w_packed, a.sum_cost1.w_packed}, reinterpret_cast<uint4 *>(lds), ln.wave, ln.lane, {}};
     ws.start();
     float4 bias[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) bias[t] = *reinterpret_cast<const float4 *>(a.xyz_enc.bias + t * 16 + 4 * kq);
+    Biases::first_quads(a.xyz_enc.bias, ln.kq, bias);
     const float *const bsrc[3] = {a.xyz_enc.bias, a.sum_cost0.bias, a.sum_cost1.bias};
-    constexpr int BN[3] = {64, 128, 64}, B1 = 64, B2 = 192;
-    const float bias_word = rr_bias_request(bsrc, BN, (int)threadIdx.x);
-    const float *bt = lds + RR_BIAS_OFF;
-    // ---- row metadata + gather (this lane's row: r = wave * 16 + i16 = point * K + slot)
-    const int r = wave * 16 + i16, pi = small_div(r, K);
-    long pt = first_point + pi;
-    const bool used = pi < P && pt < total_points;
-    if (!used) pt = first_point;
-    const long gr = used ? pt * K + (r - pi * K) : first_point * K;
-    const int id0 = a.idx[gr * 3 + 0], id1 = a.idx[gr * 3 + 1], id2 = a.idx[gr * 3 + 2];
-    float mk = a.mask[gr];
-    const int cell = (id0 * a.H + id1) * a.W + id2;
-    if (!used) mk = 0.0f;
-    const bool keep2 = used && mk != 0.0f;
-    ActPair in1[KP1];                                // sum_cost_volume_0's pairs: [grouped cost | encoding | feat1]
+    const float bias_word = Biases::request(bsrc, (int)threadIdx.x);
+    // ---- row metadata + gather
+    const RrGroupRow row = rr_group_row(a.idx, a.mask, ln.r, K, P, first_point, total_points, a.H, a.W);
+    ActPair in1[PL::KP[1]];                          // sum_cost_volume_0's pairs: [grouped cost | encoding | feat1]
     uint4 geo, ftail = uint4{0u, 0u, 0u, 0u};        // the geometry quad (xyz-encoding's input); feat1's quad when C == 16 (a tail block)
-    typedef typename std::conditional<F16, uint2, float4>::type Item;         // 4 channels
-    Item fc[4];                                      // the grouped cost rows
-    const Item *rc = reinterpret_cast<const Item *>(a.cost) + ((long)cell * 64 >> 2) + kq;
-    auto quad = [&](const Item &v, bool keep) {
-        const uint4 z{0u, 0u, 0u, 0u};
-        if constexpr (F16) return keep ? quad_of_halves(v) : z;
-        else return keep ? pack_quad<MODE>(v, bad) : z;
-    };
     {
-        Item f1[FP];
-        const Item *r1 = reinterpret_cast<const Item *>(a.feat1) + (pt * C >> 2) + kq;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fc[j] = rc[j * 4];
-#pragma unroll
-        for (int j = 0; j < FP; ++j) f1[j] = r1[j * 4];
-        const float *c = a.xyz1 + pt * 3, *g = a.xyz1 + (long)cell * 3;
-        const float pc0 = c[0], pc1 = c[1], pc2 = c[2], pg0 = g[0], pg1 = g[1], pg2 = g[2];
+        RrItem<F16> fc[4], f1[FP];                   // the grouped cost rows, the centre's features
+        const RrItem<F16> *rc = rr_row<F16>(a.cost, row.cell, 64, ln.kq), *r1 = rr_row<F16>(a.feat1, row.pt, C, ln.kq);
+        rr_gather(fc, rc);
+        rr_gather(f1, r1);
+        const GeoRow xyz = geo_load(a.xyz1 + row.pt * 3, a.xyz1 + (long)row.cell * 3);
         ws.prime();
 #pragma unroll
-        for (int j = 0; j < 4; ++j) put_quad(in1[j / 2], j % 2, quad(fc[j], keep2));       // cost[idx] * mask   :110
-        if constexpr (C == 16) ftail = quad(f1[0], used);
-        else {
+        for (int j = 0; j < 4; ++j) rr_put_block(in1, ftail, j, rr_quad<F16, MODE>(fc[j], row.keep2, bad));       // cost[idx] * mask   :110
 #pragma unroll
-            for (int j = 0; j < FP; ++j) put_quad(in1[4 + j / 2], j % 2, quad(f1[j], used));   // centre features    :115
-        }
-        const float g0 = pg0 * mk, g1 = pg1 * mk, g2 = pg2 * mk;
-        const float d0 = g0 - pc0, d1 = g1 - pc1, d2 = g2 - pc2;
-        const float e = sqrtf(d0 * d0 + d1 * d1 + d2 * d2 + 1e-20f);
-        const float4 q4 = kq == 0 ? float4{pc0, pc1, pc2, g0} : kq == 1 ? float4{g1, g2, d0, d1}
-                        : kq == 2 ? float4{d2, e, 0.0f, 0.0f} : float4{0.0f, 0.0f, 0.0f, 0.0f};
-        geo = used ? pack_quad<MODE>(q4, bad) : uint4{0u, 0u, 0u, 0u};
+        for (int j = 0; j < FP; ++j) rr_put_block(in1, ftail, 8 + j, rr_quad<F16, MODE>(f1[j], row.used, bad));   // centre features    :115
+        geo = rr_geo_quad<MODE>(xyz, row.mk, row.used, ln.kq, bad);
     }
-    rr_bias_store(lds, (int)threadIdx.x, 256, bias_word);
+    Biases::store(lds, (int)threadIdx.x, bias_word);
     rr_barrier();
     const uint4 none{0u, 0u, 0u, 0u};
-    {
-        ActPair unused[1];
-        rr_layer<0, true, 4, 0, MODE>(unused, geo, bt, bt + B1, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-            put_quad(in1[2 + pass], t, pack_quad<MODE>(relu4(acc, a.xyz_enc.relu), bad));      // encoding: pairs 2, 3
-        });
-    }
+    const ActPair unused[1] = {};
+    rr_layer<PL, 0, MODE>(ws, unused, geo, bias, RrToPairs<MODE>{in1 + 2, a.xyz_enc.relu, bad});                  // encoding: pairs 2, 3
     ActPair h128[4];
-    auto emit1 = [&](int pass, int t, const f32x4 acc) { put_quad(h128[pass], t, pack_quad<MODE>(relu4(acc, a.sum_cost0.relu), bad)); };
-    rr_layer<KP1, C == 16, 8, E0, MODE, (F16 ? ~0xcu : 0u), F16>(in1, ftail, bt + B1, bt + B2, bias, fetch, advance, emit1);
+    rr_layer<PL, 1, MODE, (F16 ? ~0xcu : 0u), F16>(ws, in1, ftail, bias, RrToPairs<MODE>{h128, a.sum_cost0.relu, bad});
     float4 logit[4];
-    rr_layer<4, false, 4, E1, MODE>(h128, none, bt + B2, nullptr, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-        logit[2 * pass + t] = relu4(acc, a.sum_cost1.relu);
-    });
-    if (K == 4 && a.sum_cost1.relu) rr_pool_softmax4_inwave<F16>(logit, in1[0], in1[1], mk, r, lane, first_point, total_points, a.out);
-    else rr_pool<F16>(lds, logit, in1[0], in1[1], mk, r, wave, lane, K, P, first_point, total_points, a.out);
+    rr_layer<PL, 2, MODE>(ws, h128, none, bias, RrToQuads{logit, a.sum_cost1.relu});
+    if (K == 4 && a.sum_cost1.relu) rr_pool_softmax4_inwave<F16>(logit, in1[0], in1[1], row.mk, ln.r, ln.lane, first_point, total_points, a.out);
+    else rr_pool<F16>(lds, logit, in1[0], in1[1], row.mk, ln.r, ln.wave, ln.lane, K, P, first_point, total_points, a.out);
     report_violations<MODE>(bad, a.range_counter);
 }
 // ---- two chained row-wise MLPs, register-resident (see cv1_rr_kernel): set-upconv stage 2 and the flow predictor it feeds
@@ -2149,73 +2170,48 @@ __global__ __launch_bounds__(RR_WAVES * 64, 4) void mlp2_rr_kernel(const JobPair
     }
     const elo_mlp_args &a = jobs.job[blockIdx.y];
     typedef Mlp2Plan<C> PL;
-    constexpr int FP = C / 16, KP1 = PL::KP[0], KP3 = PL::KP[2];
-    constexpr bool T1 = PL::TL[0] != 0, T3 = PL::TL[2] != 0;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i16 = lane & 15, kq = lane >> 4;
+    typedef RrBiasTable<PL> Biases;
+    constexpr int FP = C / 16;
+    const RrLane ln;
+    const int r = ln.r, kq = ln.kq;
     const long first = (long)xcd_tile(blockIdx.x, gridDim.x) * RR_ROWS;
     unsigned bad = 0;
-    typedef RrStream<PL, MODE> Stream;
-    Stream ws{{a.layers[0].w_packed, a.layers[1].w_packed, a.layers2[0].w_packed, a.layers2[1].w_packed}, reinterpret_cast<uint4 *>(lds), wave, lane, {}};
-    constexpr int E0 = Stream::first(1), E1 = Stream::first(2), E2 = Stream::first(3);
-    auto fetch = [&](int g, RrW &dst) { ws.fetch(g, dst); };
-    auto advance = [&](int S) { ws.advance(S); };
+    RrStream<PL, MODE> ws{{a.layers[0].w_packed, a.layers[1].w_packed, a.layers2[0].w_packed, a.layers2[1].w_packed}, reinterpret_cast<uint4 *>(lds),
+                          ln.wave, ln.lane, {}};
     ws.start();
     float4 bias[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) bias[t] = *reinterpret_cast<const float4 *>(a.layers[0].bias + t * 16 + 4 * kq);
+    Biases::first_quads(a.layers[0].bias, kq, bias);
     const float *const bsrc[4] = {a.layers[0].bias, a.layers[1].bias, a.layers2[0].bias, a.layers2[1].bias};
-    constexpr int BN[4] = {128, 64, 128, 64}, O1 = 128, O2 = 192, O3 = 320;
-    const float bias_word = rr_bias_request(bsrc, BN, (int)threadIdx.x);
-    const float *bt = lds + RR_BIAS_OFF;
+    const float bias_word = Biases::request(bsrc, (int)threadIdx.x);
     // ---- this lane's row
-    const int r = wave * 16 + i16;
     const bool used = first + r < a.rows;
     const long gr = used ? first + r : a.rows - 1;
-    typedef typename std::conditional<F16, uint2, float4>::type Item;         // 4 channels
-    auto quad = [&](const Item &v) {
-        const uint4 z{0u, 0u, 0u, 0u};
-        if constexpr (F16) return used ? quad_of_halves(v) : z;
-        else return used ? pack_quad<MODE>(v, bad) : z;
-    };
-    // block b of a concatenation goes to half b % 2 of pair b / 2, the last block of an odd count to the tail
-    ActPair in1[KP1];
+    ActPair in1[PL::KP[0]];                          // [pooled (blocks 0..3) | points (FP blocks)]
     uint4 tail1{0u, 0u, 0u, 0u};
     {
-        Item s0[4], s1[FP];
-        const Item *p0 = reinterpret_cast<const Item *>(a.src[0]) + (gr * 64 >> 2) + kq, *p1 = reinterpret_cast<const Item *>(a.src[1]) + (gr * C >> 2) + kq;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s0[j] = p0[j * 4];
-#pragma unroll
-        for (int j = 0; j < FP; ++j) s1[j] = p1[j * 4];
+        RrItem<F16> s0[4], s1[FP];
+        const RrItem<F16> *p0 = rr_row<F16>(a.src[0], gr, 64, kq), *p1 = rr_row<F16>(a.src[1], gr, C, kq);
+        rr_gather(s0, p0);
+        rr_gather(s1, p1);
         ws.prime();
 #pragma unroll
-        for (int j = 0; j < 4; ++j) put_quad(in1[j / 2], j % 2, quad(s0[j]));
+        for (int j = 0; j < 4; ++j) rr_put_block(in1, tail1, j, rr_quad<F16, MODE>(s0[j], used, bad));
 #pragma unroll
-        for (int j = 0; j < FP; ++j) {
-            if (T1 && j == FP - 1) tail1 = quad(s1[j]);
-            else put_quad(in1[(4 + j) / 2], (4 + j) % 2, quad(s1[j]));
-        }
+        for (int j = 0; j < FP; ++j) rr_put_block(in1, tail1, 4 + j, rr_quad<F16, MODE>(s1[j], used, bad));
     }
-    rr_bias_store(lds, (int)threadIdx.x, 384, bias_word);
+    Biases::store(lds, (int)threadIdx.x, bias_word);
     rr_barrier();
     const uint4 none{0u, 0u, 0u, 0u};
     ActPair h128[4];
-    rr_layer<KP1, T1, 8, 0, MODE, (F16 ? ~0u : 0u), F16>(in1, tail1, bt, bt + O1, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-        put_quad(h128[pass], t, pack_quad<MODE>(relu4(acc, a.layers[0].relu), bad));
-    });
+    rr_layer<PL, 0, MODE, (F16 ? ~0u : 0u), F16>(ws, in1, tail1, bias, RrToPairs<MODE>{h128, a.layers[0].relu, bad});
     // the second stage's other inputs: requested now, a layer ahead of their first use
-    Item sb[FP], sa[4];
-    {
-        const Item *pb = reinterpret_cast<const Item *>(a.before) + (gr * C >> 2) + kq, *pa = reinterpret_cast<const Item *>(a.after) + (gr * 64 >> 2) + kq;
-#pragma unroll
-        for (int j = 0; j < FP; ++j) sb[j] = pb[j * 4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sa[j] = pa[j * 4];
-    }
-    ActPair in3[KP3];
+    RrItem<F16> sb[FP], sa[4];
+    const RrItem<F16> *pb = rr_row<F16>(a.before, gr, C, kq), *pa = rr_row<F16>(a.after, gr, 64, kq);
+    rr_gather(sb, pb);
+    rr_gather(sa, pa);
+    ActPair in3[PL::KP[2]];
     uint4 tail3{0u, 0u, 0u, 0u};
-    rr_layer<4, false, 4, E0, MODE>(h128, none, bt + O1, bt + O2, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
+    rr_layer<PL, 1, MODE>(ws, h128, none, bias, [&](int pass, int t, const f32x4 acc) {
         const float4 v = relu4(acc, a.layers[1].relu);
         const long at = (first + r) * 64 + (2 * pass + t) * 16 + 4 * kq;
         if constexpr (F16) {
@@ -2230,17 +2226,11 @@ __global__ __launch_bounds__(RR_WAVES * 64, 4) void mlp2_rr_kernel(const JobPair
     });
     // [out (blocks 0..3) | before (FP blocks) | after (4 blocks)]
 #pragma unroll
-    for (int j = 0; j < FP; ++j) put_quad(in3[(4 + j) / 2], (4 + j) % 2, quad(sb[j]));
+    for (int j = 0; j < FP; ++j) rr_put_block(in3, tail3, 4 + j, rr_quad<F16, MODE>(sb[j], used, bad));
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        constexpr int B0 = 4 + FP;
-        if (T3 && j == 3) tail3 = quad(sa[j]);
-        else put_quad(in3[(B0 + j) / 2], (B0 + j) % 2, quad(sa[j]));
-    }
-    rr_layer<KP3, T3, 8, E1, MODE, (F16 ? ~0u : 0u), F16>(in3, tail3, bt + O2, bt + O3, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-        put_quad(h128[pass], t, pack_quad<MODE>(relu4(acc, a.layers2[0].relu), bad));
-    });
-    rr_layer<4, false, 4, E2, MODE>(h128, none, bt + O3, nullptr, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
+    for (int j = 0; j < 4; ++j) rr_put_block(in3, tail3, 4 + FP + j, rr_quad<F16, MODE>(sa[j], used, bad));
+    rr_layer<PL, 2, MODE, (F16 ? ~0u : 0u), F16>(ws, in3, tail3, bias, RrToPairs<MODE>{h128, a.layers2[0].relu, bad});
+    rr_layer<PL, 3, MODE>(ws, h128, none, bias, [&](int pass, int t, const f32x4 acc) {
         if (used) feat_store4(a.out2, (first + r) * 64 + (2 * pass + t) * 16 + 4 * kq, relu4(acc, a.layers2[1].relu), F16);
     });
     report_violations<MODE>(bad, a.range_counter);
@@ -2297,29 +2287,24 @@ __device__ __forceinline__ void setconv_rr_body(const elo_setconv_args &a, const
 {
     extern __shared__ __align__(16) float lds[];
     constexpr int C = 16 * FPB, NOUT = N3 ? N3 : N2;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i16 = lane & 15, kq = lane >> 4, tid = threadIdx.x;
+    typedef ScPlan<FPB, N1, N2, N3> PL;
+    typedef RrBiasTable<PL> Biases;
+    const RrLane ln;
+    const int lane = ln.lane, wave = ln.wave, kq = ln.kq, r = ln.r, tid = threadIdx.x;
     const int K = a.K, P = RR_ROWS / K;
     const long total_points = (long)a.batch * a.npoints;
     const long first_point = (long)xcd_tile(block, nblocks) * P;
     unsigned bad = 0;
     RR_STAMP(0);
-    typedef RrStream<ScPlan<FPB, N1, N2, N3>, MODE> Stream;
-    Stream ws{};
-    ws.w[0] = a.layers[0].w_packed; ws.w[1] = a.layers[1].w_packed;
-    if constexpr (N3 != 0) ws.w[2] = a.layers[2].w_packed;
+    RrStream<PL, MODE> ws{};
+    const float *bsrc[PL::NL];
+#pragma unroll
+    for (int l = 0; l < PL::NL; ++l) { ws.w[l] = a.layers[l].w_packed; bsrc[l] = a.layers[l].bias; }
     ws.ring = reinterpret_cast<uint4 *>(lds); ws.wave = wave; ws.lane = lane;
-    constexpr int E0 = Stream::first(1), E1 = N3 ? Stream::first(N3 ? 2 : 1) : 0;
-    auto fetch = [&](int g, RrW &dst) { ws.fetch(g, dst); };
-    auto advance = [&](int S) { ws.advance(S); };
     ws.start();
     float4 bias[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) bias[t] = *reinterpret_cast<const float4 *>(a.layers[0].bias + t * 16 + 4 * kq);
-    const float *const bsrc[3] = {a.layers[0].bias, a.layers[1].bias, N3 ? a.layers[2].bias : a.layers[1].bias};
-    constexpr int BN[3] = {N1, N2, N3}, B1 = N1, B2 = N1 + N2;
-    const float bias_word = rr_bias_request(bsrc, BN, tid);
-    const float *bt = lds + RR_BIAS_OFF;
+    Biases::first_quads(a.layers[0].bias, kq, bias);
+    const float bias_word = Biases::request(bsrc, tid);
     // ---- grouping.  Scratch behind the 16 KB ring: [KT] visiting order | [128] cell | [128] mask | [P] centres (hw, xyz)
     int *lds_off = reinterpret_cast<int *>(lds + 4096);
     const int KT = a.group.kernel_h * a.group.kernel_w;
@@ -2391,56 +2376,41 @@ __device__ __forceinline__ void setconv_rr_body(const elo_setconv_args &a, const
     __syncthreads();
     RR_STAMP(3);
     // ---- this lane's row: gather [features | xyz difference]
-    const int r = wave * 16 + i16, pi = small_div(r, K);
+    const int pi = small_div(r, K);
     const int cell = cell_row[r];
     const bool used = cell >= 0;                     // (rows of points beyond the end keep -1)
     const float mk = mask_row[r];
     const float c0 = cxyz[(pi < P ? pi : 0) * 3 + 0], c1 = cxyz[(pi < P ? pi : 0) * 3 + 1], c2 = cxyz[(pi < P ? pi : 0) * 3 + 2];
-    ActPair in0[FPB / 2];
+    ActPair in0[FPB / 2];                            // [features (FPB blocks) | xyz difference (the tail)]
     uint4 dxyz;
     const bool keep = used && mk != 0.0f;
     {
-        typedef typename std::conditional<F16, uint2, float4>::type Item;
-        Item f[FPB];
+        RrItem<F16> f[FPB];
         const long cc = used ? cell : 0;
-        const Item *rf = reinterpret_cast<const Item *>(a.src_feat) + (cc * C >> 2) + kq;
-#pragma unroll
-        for (int j = 0; j < FPB; ++j) f[j] = rf[j * 4];
+        rr_gather(f, rr_row<F16>(a.src_feat, cc, C, kq));
         const float *g = a.src_xyz + cc * 3;
         const float x = g[0], y = g[1], z = g[2];
         ws.prime();
-        auto quad = [&](const Item &v) {
-            const uint4 zq{0u, 0u, 0u, 0u};
-            if constexpr (F16) return keep ? quad_of_halves(v) : zq;
-            else return keep ? pack_quad<MODE>(v, bad) : zq;
-        };
 #pragma unroll
-        for (int j = 0; j < FPB; ++j) put_quad(in0[j / 2], j % 2, quad(f[j]));
+        for (int j = 0; j < FPB; ++j) rr_put_block(in0, dxyz, j, rr_quad<F16, MODE>(f[j], keep, bad));
         const float4 d = kq == 0 ? float4{x * mk - c0, y * mk - c1, z * mk - c2, 0.0f} : float4{0.0f, 0.0f, 0.0f, 0.0f};
         dxyz = used ? pack_quad<MODE>(d, bad) : uint4{0u, 0u, 0u, 0u};
     }
-    rr_bias_store(lds, tid, N1 + N2 + N3, bias_word);
+    Biases::store(lds, tid, bias_word);
     RR_STAMP(4);
     rr_barrier();
     RR_STAMP(5);
     const uint4 none{0u, 0u, 0u, 0u};
     ActPair h1[N1 / 32];
-    auto emit0 = [&](int pass, int t, const f32x4 acc) { put_quad(h1[pass], t, pack_quad<MODE>(relu4(acc, a.layers[0].relu), bad)); };
-    rr_layer<FPB / 2, true, N1 / 16, 0, MODE, (F16 ? ~0u : 0u)>(in0, dxyz, bt, bt + B1, bias, fetch, advance, emit0);
+    rr_layer<PL, 0, MODE, (F16 ? ~0u : 0u)>(ws, in0, dxyz, bias, RrToPairs<MODE>{h1, a.layers[0].relu, bad});
     RR_STAMP(6);
     float4 last[NOUT / 16];
     if constexpr (N3 == 0) {
-        rr_layer<N1 / 32, false, N2 / 16, E0, MODE>(h1, none, bt + B1, nullptr, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-            last[2 * pass + t] = relu4(acc, a.layers[1].relu);
-        });
+        rr_layer<PL, 1, MODE>(ws, h1, none, bias, RrToQuads{last, a.layers[1].relu});
     } else {
         ActPair h2[N2 / 32];
-        rr_layer<N1 / 32, false, N2 / 16, E0, MODE>(h1, none, bt + B1, bt + B2, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-            put_quad(h2[pass], t, pack_quad<MODE>(relu4(acc, a.layers[1].relu), bad));
-        });
-        rr_layer<N2 / 32, false, NOUT / 16, E1, MODE>(h2, none, bt + B2, nullptr, bias, fetch, advance, [&](int pass, int t, const f32x4 acc) {
-            last[2 * pass + t] = relu4(acc, a.layers[2].relu);
-        });
+        rr_layer<PL, 1, MODE>(ws, h1, none, bias, RrToPairs<MODE>{h2, a.layers[1].relu, bad});
+        rr_layer<PL, 2, MODE>(ws, h2, none, bias, RrToQuads{last, a.layers[2].relu});
     }
     RR_STAMP(7);
     if ((K == 8 || K == 16) && a.layers[N3 ? 2 : 1].relu) rr_pool_max_inwave<NOUT, F16>(last, mk, r, lane, K, first_point, total_points, a.out);
