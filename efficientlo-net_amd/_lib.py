@@ -131,6 +131,10 @@ MapExtractArgs = _struct("elo_map_extract_args", [
     ("voxel", _f), ("log2_capacity", _i), ("max_out", ctypes.c_long), ("keys", _vp), ("acc", _vp), ("out_key", _vp), ("out_count", _vp),
     ("out_xyz", _vp), ("cursor", _vp)])
 MAP_MAX_PROBE, MAP_MIN_LOG2, MAP_MAX_LOG2 = 128, 10, 28        # ELO_MAP_*
+MapFitArgs = _struct("elo_map_fit_args", [
+    ("batch", _i), ("H", _i), ("W", _i), ("voxel", _f), ("log2_capacity", _i), ("keys", _vp), ("acc", _vp), ("xyz", _vp),
+    ("pose_in", _vp), ("iters", _i), ("gate", _f), ("huber", _f), ("jump_rel", _f), ("min_count", _i), ("damping", _f),
+    ("min_points", _i), ("pose_out", _vp), ("info", _vp), ("grad", _vp), ("stats", _vp), ("match", _vp), ("scratch", _vp)])
 
 # backward passes (csrc/elo_backward.hip)
 GroupConcatBwdArgs = _struct("elo_group_concat_bwd_args", [
@@ -257,6 +261,9 @@ SYMBOLS = [
     ("elo_model_advance", ctypes.c_int, [ctypes.POINTER(ModelAdvanceArgs), _vp]),
     ("elo_map_insert", ctypes.c_int, [ctypes.POINTER(MapInsertArgs), _vp]),
     ("elo_map_extract", ctypes.c_int, [ctypes.POINTER(MapExtractArgs), _vp]),
+    ("elo_map_fit", ctypes.c_int, [ctypes.POINTER(MapFitArgs), _vp]),
+    ("elo_map_fit_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
+    ("elo_map_fit_parts", ctypes.c_int, [ctypes.c_int] * 2),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),
     ("elo_masked_maxpool_backward", ctypes.c_int, [ctypes.POINTER(MaskedMaxpoolBwdArgs), _vp]),
     ("elo_cv_encode1_backward", ctypes.c_int, [ctypes.POINTER(CvEncode1BwdArgs), _vp]),

@@ -973,6 +973,55 @@ def map_extract(keys, acc, spec, max_out):
     return key[:max_out], count[:max_out], xyz[:max_out], n
 
 
+class MapFitResult(PoseFitResult):
+    """What elo_map_fit wrote for a batch: PoseFitResult's fields, with `pose` (B,7) FLOAT64 [q | t], scan -> world, `info` / `grad`
+    for the perturbation about the sensor's position (rotation first, then translation), and `match` (B,H,W) int64 -- the key of
+    the voxel each cell's term went to at `pose`, -1 where it gave none -- or None."""
+    __slots__ = ("match",)
+
+    def __init__(self, pose, info, grad, stats, scratch=None, match=None):
+        PoseFitResult.__init__(self, pose, info, grad, stats, scratch)
+        self.match = match
+
+
+def map_fit(keys, acc, xyz, pose64, spec, fit, match=False):
+    """elo_map_fit: the range images xyz (B,H,W,3) float32, each at its row of pose64 (B,7) float64 [q | t] (scan -> world), fitted
+    against the voxel map (keys (C,), acc (C,4) int64, spec: sensor.VoxelMap; only read) -> MapFitResult.  `fit`: a sensor.MapFit
+    (gate None: the map's voxel).  match=True: the per-cell association is written too.  2 (iters + 1) launches on the current
+    stream, no host synchronisation, capturable; inputs are contiguous and used in place, and pose64 is read when the launches RUN.
+    Bad types, shapes or layouts are refused here, before anything is launched."""
+    _check_map(keys, acc, spec)
+    if not isinstance(fit, _sensor.MapFit):
+        raise TypeError("fit is a MapFit (got %r)" % (type(fit).__name__,))
+    gate = fit.gate_for(spec)
+    _check_tensors((("xyz", xyz, torch.float32), ("pose64", pose64, torch.float64)))
+    if xyz.dim() != 4 or xyz.shape[-1] != 3:
+        raise L.EloError("xyz is (B,H,W,3): one range image per scan (got %s)" % (tuple(xyz.shape),))
+    B, H, W, _ = xyz.shape
+    if H < 3 or W < 1:
+        raise L.EloError("a normal needs three rows: H >= 3, W >= 1 (got %d x %d)" % (H, W))
+    if B * H * W >= 2 ** 31:
+        raise L.EloError("B*H*W stays below 2^31 (got B, H, W = %d, %d, %d)" % (B, H, W))
+    if tuple(pose64.shape) != (B, 7):
+        raise L.EloError("pose64 is one [q0 q1 q2 q3 | t0 t1 t2] row per scan: (%d, 7) (got %s)" % (B, tuple(pose64.shape)))
+    if xyz.device != keys.device or pose64.device != keys.device:
+        raise L.EloError("the map, the images and the poses live on one device")
+    L.require_gpu(keys, acc, xyz, pose64)
+    dev = xyz.device
+    words = L.lib().elo_map_fit_scratch_words(B, H, W)
+    if words < 0:
+        raise L.EloError("elo_map_fit refuses a (%d,%d,%d) batch of images" % (B, H, W))
+    res = MapFitResult(torch.empty((B, 7), dtype=torch.float64, device=dev), torch.empty((B, 6, 6), dtype=torch.float32, device=dev),
+                       torch.empty((B, 6), dtype=torch.float32, device=dev), torch.empty((B, 4), dtype=torch.float32, device=dev),
+                       torch.empty((max(words, 1),), dtype=torch.int32, device=dev),
+                       torch.empty((B, H, W), dtype=torch.int64, device=dev) if match else None)
+    a = L.MapFitArgs(B, H, W, spec.voxel, spec.log2_capacity, keys.data_ptr(), acc.data_ptr(), xyz.data_ptr(), pose64.data_ptr(),
+                     fit.iters, gate, fit.huber, fit.jump_rel, fit.min_count, fit.damping, fit.min_points, res.pose.data_ptr(),
+                     res.info.data_ptr(), res.grad.data_ptr(), res.stats.data_ptr(), _ptr(res.match), res.scratch.data_ptr())
+    L.call("elo_map_fit", a, keys)
+    return res
+
+
 class _WarpProject(torch.autograd.Function):
     """elo_warp_project / elo_warp_project_backward.  The forward's scratch (who won each cell) is kept for the backward."""
 

@@ -11,7 +11,7 @@
 // ballot, butterfly sum -- costs 24 shuffles per key: slower than one add per point below ~8 cells a key; tools/micro/map_atomics.hip
 // holds all three forms.)  The counters go the same way: ballots and one add per wave and counter.
 // map_extract_kernel: one thread per slot, ballot compaction, one atomic on the cursor per wave.
-#include "elo_common.h"
+#include "elo_map_device.h"
 
 namespace elo {
 namespace {
@@ -19,8 +19,6 @@ namespace {
 constexpr int MAP_STRIP = 4;                            // cells per thread: 48 bytes, three 16-byte loads
 constexpr int MAP_TILE = ELO_BLOCK * MAP_STRIP;         // cells per workgroup
 constexpr int MAP_WAVE = 64;
-constexpr unsigned long long MAP_EMPTY = ~0ull;
-constexpr double MAP_HALF = 1048576.0;                  // 2^20: indices lie in [-2^20, 2^20)
 
 struct MapInsert {
     int H, W;
@@ -34,33 +32,6 @@ struct MapInsert {
 };
 
 enum { MAP_NONE = 0, MAP_FILTERED = 1, MAP_REJECTED = 2, MAP_POINT = 3 };
-
-// model_pose (elo_model.hip) from a double row
-__device__ __forceinline__ bool map_pose(const double *row, double (&R)[9], double (&t)[3])
-{
-    double q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
-    const double n = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    if (!(n > 0.0) || n - n != 0.0) return false;
-    q0 /= n; q1 /= n; q2 /= n; q3 /= n;
-    R[0] = 1.0 - 2.0 * (q2 * q2 + q3 * q3); R[1] = 2.0 * (q1 * q2 - q0 * q3);       R[2] = 2.0 * (q1 * q3 + q0 * q2);
-    R[3] = 2.0 * (q1 * q2 + q0 * q3);       R[4] = 1.0 - 2.0 * (q1 * q1 + q3 * q3); R[5] = 2.0 * (q2 * q3 - q0 * q1);
-    R[6] = 2.0 * (q1 * q3 - q0 * q2);       R[7] = 2.0 * (q2 * q3 + q0 * q1);       R[8] = 1.0 - 2.0 * (q1 * q1 + q2 * q2);
-    t[0] = row[4]; t[1] = row[5]; t[2] = row[6];
-    return true;
-}
-
-// one axis of the rounded p': its 21-bit field of the key and its offset inside the voxel; false: the index is out of range
-__device__ __forceinline__ bool map_axis(float c, double voxel, unsigned long long &field, unsigned &g)
-{
-    const double u = (double)c / voxel;
-    const double i = floor(u);
-    if (!(i >= -MAP_HALF && i < MAP_HALF)) return false;
-    const double f = floor((u - i) * 65536.0);          // u - i lies in [0, 1]: 1 where u is a tiny negative number
-    const unsigned o = (unsigned)f;
-    g = o < 65535u ? o : 65535u;
-    field = (unsigned long long)((long long)i + (1ll << 20));
-    return true;
-}
 
 // the per-point rule of include/elo.h -> MAP_NONE / FILTERED / REJECTED / POINT (then key and g are set)
 __device__ __forceinline__ int map_point(const MapInsert &a, const double (&R)[9], const double (&t)[3], float ax, float ay, float az,
@@ -78,14 +49,6 @@ __device__ __forceinline__ int map_point(const MapInsert &a, const double (&R)[9
     if (!map_axis(x, voxel, fx, g[0]) || !map_axis(y, voxel, fy, g[1]) || !map_axis(z, voxel, fz, g[2])) return MAP_REJECTED;
     key = fx << 42 | fy << 21 | fz;
     return MAP_POINT;
-}
-
-__device__ __forceinline__ unsigned long long map_home(unsigned long long h)
-{
-    h ^= h >> 30; h *= 0xbf58476d1ce4e5b9ull;
-    h ^= h >> 27; h *= 0x94d049bb133111ebull;
-    h ^= h >> 31;
-    return h;
 }
 
 // the slot of `key`, claimed where it has none yet; false: none within ELO_MAP_MAX_PROBE.  A slot only ever turns from empty into
@@ -218,12 +181,6 @@ struct MapExtract {
     unsigned long long *cursor;
 };
 
-__device__ __forceinline__ float map_centroid(unsigned long long field, unsigned long long s, unsigned long long count, double voxel)
-{
-    const double i = (double)((long long)field - (1ll << 20));
-    return (float)((i + ((double)s / (double)count + 0.5) / 65536.0) * voxel);
-}
-
 // one thread per slot; the grid covers C exactly (C is a multiple of the block)
 __global__ __launch_bounds__(ELO_BLOCK) void map_extract_kernel(const MapExtract a)
 {
@@ -251,13 +208,6 @@ __global__ __launch_bounds__(ELO_BLOCK) void map_extract_kernel(const MapExtract
 
 #define ELO_REQUIRE(cond, who, what) \
     do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
-bool map_table_ok(float voxel, int log2_capacity)
-{
-    return voxel > 0.0f && voxel - voxel == 0.0f && log2_capacity >= ELO_MAP_MIN_LOG2 && log2_capacity <= ELO_MAP_MAX_LOG2;
-}
-
-bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
 
 }  // namespace
 }  // namespace elo

@@ -1,0 +1,61 @@
+// elo_map_device.h -- the world map's rules that more than one file states (include/elo.h, WORLD MAP): the pose row, the voxel index
+// of a rounded coordinate, the hash, the centroid.  elo_map.hip writes the table by them and elo_mapfit.hip reads it by them.
+#pragma once
+#include "elo_common.h"
+
+namespace elo {
+namespace {
+
+constexpr unsigned long long MAP_EMPTY = ~0ull;
+constexpr double MAP_HALF = 1048576.0;                  // 2^20: indices lie in [-2^20, 2^20)
+
+// model_pose (elo_model.hip) from a double row
+__device__ __forceinline__ bool map_pose(const double *row, double (&R)[9], double (&t)[3])
+{
+    double q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
+    const double n = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    if (!(n > 0.0) || n - n != 0.0) return false;
+    q0 /= n; q1 /= n; q2 /= n; q3 /= n;
+    R[0] = 1.0 - 2.0 * (q2 * q2 + q3 * q3); R[1] = 2.0 * (q1 * q2 - q0 * q3);       R[2] = 2.0 * (q1 * q3 + q0 * q2);
+    R[3] = 2.0 * (q1 * q2 + q0 * q3);       R[4] = 1.0 - 2.0 * (q1 * q1 + q3 * q3); R[5] = 2.0 * (q2 * q3 - q0 * q1);
+    R[6] = 2.0 * (q1 * q3 - q0 * q2);       R[7] = 2.0 * (q2 * q3 + q0 * q1);       R[8] = 1.0 - 2.0 * (q1 * q1 + q2 * q2);
+    t[0] = row[4]; t[1] = row[5]; t[2] = row[6];
+    return true;
+}
+
+// one axis of the rounded p': its 21-bit field of the key and its offset inside the voxel; false: the index is out of range
+__device__ __forceinline__ bool map_axis(float c, double voxel, unsigned long long &field, unsigned &g)
+{
+    const double u = (double)c / voxel;
+    const double i = floor(u);
+    if (!(i >= -MAP_HALF && i < MAP_HALF)) return false;
+    const double f = floor((u - i) * 65536.0);          // u - i lies in [0, 1]: 1 where u is a tiny negative number
+    const unsigned o = (unsigned)f;
+    g = o < 65535u ? o : 65535u;
+    field = (unsigned long long)((long long)i + (1ll << 20));
+    return true;
+}
+
+__device__ __forceinline__ unsigned long long map_home(unsigned long long h)
+{
+    h ^= h >> 30; h *= 0xbf58476d1ce4e5b9ull;
+    h ^= h >> 27; h *= 0x94d049bb133111ebull;
+    h ^= h >> 31;
+    return h;
+}
+
+__device__ __forceinline__ float map_centroid(unsigned long long field, unsigned long long s, unsigned long long count, double voxel)
+{
+    const double i = (double)((long long)field - (1ll << 20));
+    return (float)((i + ((double)s / (double)count + 0.5) / 65536.0) * voxel);
+}
+
+inline bool map_table_ok(float voxel, int log2_capacity)
+{
+    return voxel > 0.0f && voxel - voxel == 0.0f && log2_capacity >= ELO_MAP_MIN_LOG2 && log2_capacity <= ELO_MAP_MAX_LOG2;
+}
+
+inline bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
+
+}  // namespace
+}  // namespace elo

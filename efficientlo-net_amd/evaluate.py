@@ -248,10 +248,15 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
     per sample: count, rms, status and the 21 unique entries of the information matrix.
     `world_map=` a sensor.VoxelMap (a WorldMap is built for it on the net's device) or a world_map.WorldMap (used as it stands: reset
     it between drives): the scans are added to it at the poses of the trajectory (predict_sequence) and `<out_dir>/<seq>_map.bin`
-    holds its voxels, float32 rows x y z count in the frame the first sample's pose leads to (WorldMap.save)."""
-    wmap = kw.get("world_map")
+    holds its voxels, float32 rows x y z count in the frame the first sample's pose leads to (WorldMap.save).
+    `map_fit=MapFit(...)` with `world_map=VoxelMap(...)`: the map TRACKS -- every scan's composed pose is fitted against the map
+    before the scan goes in (WorldMap(fit=)).  What predict_sequence returns does not change; `<out_dir>/<seq>_map_poses.txt`, beside
+    the map, holds one row per sample: the world pose q t the scan was inserted at, then count, rms and status of its fit."""
+    wmap, map_fit = kw.get("world_map"), kw.pop("map_fit", None)
+    if map_fit is not None and not isinstance(wmap, VoxelMap):
+        raise ValueError("map_fit= builds the tracking map itself: pass world_map=VoxelMap(...) with it")
     if isinstance(wmap, VoxelMap):
-        wmap = kw["world_map"] = WorldMap(wmap, device=net.device)
+        wmap = kw["world_map"] = WorldMap(wmap, device=net.device, fit=map_fit)
     q, t, *fit_out = predict_sequence(net, root, seq, T_diff, **kw)
     Tr = kitti.read_calib(os.path.join(root, seq, "calib.txt"))["Tr"]
     rows = pose_rows(q, t, Tr)
@@ -262,6 +267,10 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
             np.savetxt(os.path.join(out_dir, "%s_fit.txt" % seq), fit_out[0], fmt="%.9e")
         if wmap is not None:
             wmap.save(os.path.join(out_dir, "%s_map.bin" % seq))
+            if map_fit is not None:
+                log = wmap.fit_log().cpu().numpy().astype(np.float64)
+                table = np.concatenate([wmap.trajectory().cpu().numpy(), log[:, (0, 2, 3)]], 1)
+                np.savetxt(os.path.join(out_dir, "%s_map_poses.txt" % seq), table, fmt="%.17g")
     score = None
     if poses_gt is not None:
         score = kitti.overall(kitti.sequence_errors(np.asarray(poses_gt)[:len(rows)], rows))

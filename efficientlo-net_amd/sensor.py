@@ -16,7 +16,8 @@ matrix and, with iters > 0, Gauss-Newton steps on them.  `LocalModel` asks for t
 one range image (elo_model_render; local_model.ModelTracker) instead of against the pair's other scan.
 
 `VoxelMap` asks for the map the poses are for: every scan carried by its world pose into a hash table of voxels on the device
-(elo_map_insert; world_map.WorldMap).
+(elo_map_insert; world_map.WorldMap).  `MapFit` asks for a scan's world pose to be fitted against that map before the scan goes
+in (elo_map_fit; WorldMap(fit=)).
 """
 import math
 
@@ -207,6 +208,34 @@ class VoxelMap(_Frozen):
     @property
     def capacity(self):
         return 1 << self.log2_capacity
+
+
+class MapFit(_Frozen):
+    """MapFit(iters=0, gate=None, huber=0.1, jump_rel=0.1, min_count=50, damping=0.0, min_points=1): the point-to-plane fit of a
+    scan's world pose against the voxel map (elo_map_fit, include/elo.h; world_map.WorldMap(fit=)).  Frozen and hashable.
+    iters, huber, jump_rel, min_count, damping: as PoseFit's.  gate (m): a carried point further than this from the nearest voxel
+    centroid gives no term; it may not exceed the map's voxel (the search looks at the 27 voxels about the point), and None means
+    the map's voxel.  min_points: a voxel holding fewer points is no target, an integer >= 1."""
+    __slots__ = ("iters", "gate", "huber", "jump_rel", "min_count", "damping", "min_points")
+
+    def __init__(self, iters=0, gate=None, huber=0.1, jump_rel=0.1, min_count=50, damping=0.0, min_points=1):
+        base = PoseFit(iters, 1.0 if gate is None else gate, huber, jump_rel, min_count, damping)
+        if isinstance(min_points, bool) or not hasattr(min_points, "__index__"):
+            raise ValueError("min_points is an integer (got %r)" % (min_points,))
+        min_points = min_points.__index__()
+        if min_points < 1 or min_points >= 2 ** 31:
+            raise ValueError("min_points is a positive 32-bit count (got %d)" % min_points)
+        self._freeze(base.iters, None if gate is None else base.gate, base.huber, base.jump_rel, base.min_count, base.damping, min_points)
+
+    def __repr__(self):
+        return "MapFit(iters=%r, gate=%r, huber=%r, jump_rel=%r, min_count=%r, damping=%r, min_points=%r)" % self._key()
+
+    def gate_for(self, spec):
+        """The gate against the map `spec` (a VoxelMap): this value's, or the map's voxel; a gate beyond the voxel is an error."""
+        gate = spec.voxel if self.gate is None else self.gate
+        if gate > spec.voxel:
+            raise ValueError("the gate (%r) may not exceed the map's voxel (%r)" % (gate, spec.voxel))
+        return gate
 
 
 def resolve(sensor):

@@ -7,6 +7,10 @@
     xyz, count, key = wmap.points()            # sorted by key: canonical
     wmap.save("04_map.bin")                    # x y z count float32 rows, readable as a KITTI scan
 
+    wmap = WorldMap(VoxelMap(voxel=0.5), fit=MapFit(iters=2))      # TRACKING: every scan's composed pose is first fitted against
+    wmap.add(xyz1, pose7)                      # the map as it stands (elo_map_fit), and the scan goes in at the fitted pose
+    res = wmap.fit(xyz, pose64)                # the raw fit of scans against this map: localising in a map built earlier
+
 DIRECTION.  A sample's pose carries frame 1 = scan n into frame 2 = scan n-1 (kitti.load_pair; local_model), so the running
 product W_n = T_0 o T_1 o ... o T_n carries scan n into the frame sample 0's pose leads to: what evaluate.pose_rows forms, with Tr
 the identity.  Scan n is inserted at W_n.
@@ -19,7 +23,7 @@ import torch
 
 from . import _ops
 from .local_model import _qmul
-from .sensor import VoxelMap
+from .sensor import MapFit, VoxelMap
 
 
 def compose(world64, pose7):
@@ -40,18 +44,26 @@ def compose(world64, pose7):
 
 
 class WorldMap:
-    """WorldMap(spec, device="cuda:0"): one voxel map and the running world pose of the drive that fills it.
+    """WorldMap(spec, device="cuda:0", fit=None): one voxel map and the running world pose of the drive that fills it.
     spec: sensor.VoxelMap.  State, all on the device: `keys` (C,) int64 -- the table's unsigned 64-bit words; an empty slot, all ones,
     reads -1 --, `acc` (C,4) int64 {count, sx, sy, sz}, `stat_words` (8,) int64, and `world64` (7) float64 [q | t], the pose of the
     last scan added -> world (the identity after reset()).  insert() and add() enqueue launches and device-side float64 operators
-    only: the host never waits for the device."""
+    only: the host never waits for the device.
+    fit: a sensor.MapFit -- add() then holds the running pose to the map: each scan's composed pose is the guess of a fit against
+    the map as it stands, the scan is inserted at the fitted pose and `world64` becomes that pose.  A flagged scan (the first one,
+    against an empty map; a starved one) goes in at its guess.  `last_fit`: the _ops.MapFitResult rows of the last add()."""
 
     STATS = ("inserted", "filtered", "rejected", "dropped_full", "occupied")
 
-    def __init__(self, spec, device="cuda:0"):
+    def __init__(self, spec, device="cuda:0", fit=None):
         if not isinstance(spec, VoxelMap):
             raise TypeError("spec is a VoxelMap (got %r)" % (type(spec).__name__,))
-        self.spec, self.device = spec, torch.device(device)
+        if fit is not None:
+            if not isinstance(fit, MapFit):
+                raise TypeError("fit is a MapFit or None (got %r)" % (type(fit).__name__,))
+            fit.gate_for(spec)                               # a gate beyond the voxel is refused here, not at the first scan
+        self.spec, self.device, self.tracking = spec, torch.device(device), fit
+        self.last_fit, self._rows, self._log = None, [], []
         C = spec.capacity
         self.keys = torch.empty((C,), dtype=torch.int64, device=self.device)
         self.acc = torch.empty((C, 4), dtype=torch.int64, device=self.device)
@@ -66,16 +78,39 @@ class WorldMap:
         self.stat_words.zero_()
         self.world64.zero_()
         self.world64[0].fill_(1.0)
+        self.last_fit, self._rows, self._log = None, [], []
 
     def insert(self, xyz, pose64):
         """The raw insert: range images xyz (n,H,W,3) float32 at the poses pose64 (n,7) float64 [q | t], scan -> world.  The running
         world pose is neither read nor moved."""
         _ops.map_insert(self.keys, self.acc, self.stat_words, xyz, pose64, self.spec)
 
+    def fit(self, xyz, pose64, match=False, fit=None):
+        """The raw fit against this map: range images xyz (n,H,W,3) float32 at the guesses pose64 (n,7) float64 [q | t], scan ->
+        world -> the _ops.MapFitResult (pose: the fitted world poses, float64).  `fit`: a sensor.MapFit (None: the one this map
+        was built with).  The map and the running world pose are only read."""
+        fit = self.tracking if fit is None else fit
+        if fit is None:
+            raise ValueError("this map was built without a MapFit: pass fit=MapFit(...)")
+        return _ops.map_fit(self.keys, self.acc, xyz, pose64, self.spec, fit, match=match)
+
+    def trajectory(self):
+        """(n,7) float64 on the device: the world pose every scan added since reset() was inserted at, in order."""
+        if not self._rows:
+            return torch.empty((0, 7), dtype=torch.float64, device=self.device)
+        return torch.cat(self._rows)
+
+    def fit_log(self):
+        """(n,4) float32 on the device: [count, cost, rms, status] of the fit of every scan added since reset() (tracking maps)."""
+        if not self._log:
+            return torch.empty((0, 4), dtype=torch.float32, device=self.device)
+        return torch.cat(self._log)
+
     def add(self, xyz, pose7):
         """n consecutive samples: xyz (n,H,W,3) float32 range images (each sample's frame 1) and pose7 (n,7) their relative poses
         [q | t], frame 1 -> frame 2, any float dtype.  The poses are composed in order onto `world64` and scan j is inserted at the
-        world pose AFTER its own pose; one insert launch for all n."""
+        world pose AFTER its own pose; one insert launch for all n.  With a MapFit the scans are taken one at a time: compose, fit
+        against the map as it stands, insert at the fitted pose.  Everything is enqueued; the host never waits."""
         if not isinstance(xyz, torch.Tensor) or xyz.dim() != 4:
             raise ValueError("xyz is an (n,H,W,3) tensor of range images")
         pose7 = torch.as_tensor(pose7).to(device=self.device, dtype=torch.float64)
@@ -85,10 +120,26 @@ class WorldMap:
         if n == 0:
             return
         rows, world = [], self.world64
-        for j in range(n):
-            world = compose(world, pose7[j])
-            rows.append(world)
-        self.insert(xyz, torch.stack(rows).contiguous())
+        if self.tracking is None:
+            for j in range(n):
+                world = compose(world, pose7[j])
+                rows.append(world)
+            rows = torch.stack(rows).contiguous()
+            self.insert(xyz, rows)
+        else:
+            fits = []
+            for j in range(n):
+                guess = compose(world, pose7[j]).reshape(1, 7).contiguous()
+                res = self.fit(xyz[j:j + 1], guess)
+                self.insert(xyz[j:j + 1], res.pose)
+                world = res.pose[0]
+                fits.append(res)
+                rows.append(res.pose)
+                self._log.append(res.stats)
+            rows = torch.cat(rows)
+            self.last_fit = fits[0] if n == 1 else _ops.MapFitResult(rows, *(torch.cat([getattr(f, name) for f in fits])
+                                                                            for name in ("info", "grad", "stats")))
+        self._rows.append(rows)
         self.world64.copy_(world)
 
     def stats(self):

@@ -793,6 +793,90 @@ typedef struct elo_map_extract_args {
 } elo_map_extract_args;
 int elo_map_extract(const elo_map_extract_args *a, elo_stream_t stream);
 
+/* SCAN-TO-MAP REGISTRATION (csrc/elo_mapfit.hip): the point-to-plane fit of a scan's WORLD pose against the voxel map above -- every
+ * cell of a range image carried by the scan -> world pose, matched to the nearest voxel centroid of the map, and -- on request -- a
+ * few Gauss-Newton steps on the pose.  The table (keys, acc; voxel and log2_capacity as elo_map_insert_args) is only READ.
+ * xyz: (batch,H,W,3) range images, an all-zero cell is empty.  pose_in: (batch,7) DOUBLE [q | t], scan -> world, p' = R(q) p + t:
+ * the layout and convention of elo_map_insert_args.pose.
+ * ONE EVALUATION at a pose (R, t), per cell (h,w) of a scan, in this order:
+ *   pose row   q is normalised in double, R(q) as elo_map_insert forms it.  A row whose quaternion has zero or non-finite norm, or
+ *              whose t has a non-finite component, gives NO terms at all (the insert's rule for a scan, not elo_pose_fit's identity).
+ *   normal     elo_pose_fit's rule for a frame-2 cell, applied to xyz at the cell ITSELF, in the scan's frame, in double:
+ *              n_s = normalise((x[h,w+1] - x[h,w-1]) x (x[h+1,w] - x[h-1,w])), columns wrap; none in rows 0 and H-1, where the cell
+ *              or one of the four neighbours is empty, where a neighbour's range differs from the cell's range r by more than
+ *              jump_rel * r, where the cross product has no length; oriented towards the sensor (n_s . x <= 0).  n = R n_s.
+ *              A cell without a normal gives no term and makes no table access.
+ *   carry      p_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i in double from the float32 cell: elo_map_insert's carry.
+ *   voxel      (ix, iy, iz) from p rounded to float32 ONCE per component, by the insert's rule: u = (double)p32 / (double)voxel,
+ *              i = floor(u), in [-2^20, 2^20).  A non-finite rounded component or an index out of range: no term.  A scan inserted
+ *              at a pose therefore finds its own voxels at that pose.
+ *   candidates the 27 voxels (ix + dx, iy + dy, iz + dz), d* in {-1, 0, 1}, whose indices lie in [-2^20, 2^20).
+ *   lookup     read only: key as elo_map_insert packs it, home slot = the splitmix64 finaliser & (C - 1), slots (home + j) & (C - 1),
+ *              j = 0 .. ELO_MAP_MAX_PROBE - 1; found where a slot holds the key, absent at the first empty slot or after the last
+ *              probe.  A slot only ever turns from empty into one key, so this finds every key an insert stored.  A voxel whose
+ *              count < min_points is no candidate.
+ *   centroid   the float32 value elo_map_extract writes for the voxel, per axis, widened to double: the rows of the extract are
+ *              exactly the targets of the fit.
+ *   choice     the candidate with the smallest d2 = ((px - cx)^2 + (py - cy)^2) + (pz - cz)^2, in double from the unrounded p;
+ *              equal d2: the smaller key.  No term unless sqrt(d2) <= gate.
+ *   gate       gate <= voxel is REQUIRED: a centroid lies inside its voxel, and every voxel outside the 3x3x3 block is at least one
+ *              voxel away from p.  The target is therefore the nearest centroid OF THE WHOLE MAP within the gate (among voxels of
+ *              min_points points or more), not merely of the block.  (Candidates whose voxel box lies beyond the gate are not looked
+ *              up; the margin of that test covers every rounding, so the result is this rule's.)
+ *   term       with c the chosen centroid:  r = n . (p - c),   J = [ (c - t) x n | n ],   w = 1 where |r| <= huber, else huber / |r|.
+ *              The perturbation d = (omega, v) is about the SENSOR's position t, not the world origin: p(d) = R(dq) (p - t) + t + v
+ *              and the normal turns with the scan, n(d) = R(dq) n; so dr/domega = (c - t) x n and the numbers of a term are sensor-
+ *              relative however far the drive is from the world origin (about the origin the rotation block grows with |t|^2 and
+ *              float32 sums lose the fit after a few kilometres).
+ *   sums per image:  A = sum w J J^T,  b = sum w J r,  cost = sum w r^2,  sum w,  count (an integer).
+ * ARITHMETIC: as elo_pose_fit's.  The geometry of a term is double precision; each product is rounded to float32 ONCE and summed in
+ * float32 in a FIXED order: a thread over its strip of cells, a wave by DPP, the four waves of a workgroup through LDS; the workgroup
+ * stores one partial row; the elo_map_fit_parts(H, W) partial rows of an image are added in a fixed order, in double.  No
+ * floating-point atomic: two runs, and an eager run and a graph replay, agree bit for bit.  The grid is a fixed function of
+ * (batch, H, W).
+ * SOLVE, FLAGS, iters, REPORT: elo_pose_fit's, by the same code, on a double pose:  (A + damping * diag(A)) d = -b by Cholesky in
+ * double;  q <- dq(omega) (x) q, normalised,  t <- t + v.  ELO_FIT_FEW / ELO_FIT_SINGULAR flag an image: its pose_out row is
+ * pose_in's, every bit of the doubles, from then on.  pose_out is double and is NOT rounded to float32 between steps.  iters = 0:
+ * one evaluation at pose_in, pose_out = pose_in (bits); iters = k: k times (evaluate, solve), then one evaluation at pose_out,
+ * reported (ELO_FIT_FEW_FINAL where its count < min_count): 2 (k + 1) launches from this one call, capturable.  No NaN leaves the
+ * kernels.
+ * OUT: pose_out (batch,7) double; info (batch,6,6), grad (batch,6), stats (batch,4) = [count, cost, rms, status] as elo_pose_fit's;
+ * match (batch,H,W) or NULL: the key of the voxel the cell's term went to, -1 where the cell gave none; written by EVERY
+ * evaluation, so it holds the association of the last one, which ran at pose_out.
+ * scratch: elo_map_fit_scratch_words(batch, H, W) 32-bit device words.
+ * ELO_ERR_ARG (nothing is launched): a NULL pointer other than match, H < 3, W < 1, batch * H * W beyond 2^31, a bad voxel or
+ * log2_capacity (as elo_map_insert), gate not positive or gate > voxel, huber not positive, a negative or NaN jump_rel or damping,
+ * iters < 0, min_points < 1, pose_out == pose_in, keys / acc / pose_in / pose_out / match not 8-byte aligned.  An empty batch
+ * launches nothing and is ELO_OK.
+ * LIFETIME AND ORDER: the launches read the table, xyz and pose_in when they RUN; the caller orders them against inserts into the
+ * same table (one stream does).  Every buffer named here stays alive for as long as a graph recorded with it may be replayed.
+ * Additive to ABI 26: no existing struct changes. */
+typedef struct elo_map_fit_args {
+    int batch, H, W;
+    float voxel;                  /* the table's, as elo_map_insert_args */
+    int log2_capacity;
+    const unsigned long long *keys;     /* [C] READ ONLY */
+    const unsigned long long *acc;      /* [C][4] READ ONLY */
+    const float *xyz;             /* (batch,H,W,3); an all-zero cell is empty */
+    const double *pose_in;        /* (batch,7) [q | t] DOUBLE: scan -> world */
+    int iters;                    /* Gauss-Newton steps, >= 0 */
+    float gate;                   /* m: no term beyond this distance to the centroid; <= voxel */
+    float huber;                  /* m */
+    float jump_rel;               /* as elo_pose_fit_args */
+    int min_count;
+    float damping;                /* Levenberg factor on diag(A), >= 0 */
+    int min_points;               /* a voxel with fewer points is no target, >= 1 */
+    double *pose_out;             /* (batch,7) OUT */
+    float *info;                  /* (batch,6,6) OUT */
+    float *grad;                  /* (batch,6) OUT */
+    float *stats;                 /* (batch,4) OUT */
+    long long *match;             /* (batch,H,W) OUT, or NULL */
+    unsigned *scratch;
+} elo_map_fit_args;
+long elo_map_fit_scratch_words(int batch, int H, int W);    /* < 0: sizes the entry refuses */
+int elo_map_fit_parts(int H, int W);                        /* partial rows (workgroups) per image of an evaluation */
+int elo_map_fit(const elo_map_fit_args *a, elo_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * Backward passes of the feature kernels above, for TRAINING (csrc/elo_backward.hip).
  * The reference trains through TensorFlow's autodiff of its stock ops (main.py:171-176): gather_nd -> scatter-add of
