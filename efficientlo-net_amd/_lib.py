@@ -76,6 +76,38 @@ def tail_form_name(value):
                                 "+warp" if warp else "")
 
 
+# ... and the grouping entry points': the ELO_RANDOM_* / ELO_RANDOM_DENSE_* enumerators by value, ELO_SELECT_FORM(store, path) and
+# ELO_SELECT_DENSE_FORM(waves, counts)
+RANDOM_FORMS = ("g16u1", "g32u1", "g16u4", "g32u2")
+RANDOM_DENSE_FORMS = ("rows2", "rows4")
+SELECT_STORES = ("reg2", "reg3", "reg8", "lds4", "lds2", "lds1")
+SELECT_PATHS = ("swaps", "small", "mid", "rounds")
+SELECT_DENSE_WAVES = ("w4", "w8", "w16")
+GROUPING_QUERIES = ("elo_fused_conv_random_k_form", "elo_fused_conv_select_k_form", "elo_fused_conv_random_k_dense_form",
+                    "elo_fused_conv_select_k_dense_form")
+
+
+def grouping_form_name(query, value):
+    """An answer of one of GROUPING_QUERIES by name: 'g16u4', 'rows2', 'reg3/mid', 'lds2', 'w8', 'w16+counts'."""
+    if query == "elo_fused_conv_random_k_form":
+        return RANDOM_FORMS[value]
+    if query == "elo_fused_conv_random_k_dense_form":
+        return RANDOM_DENSE_FORMS[value]
+    if query == "elo_fused_conv_select_k_dense_form":
+        return SELECT_DENSE_WAVES[value & 15] + ("+counts" if value >> 4 else "")
+    store, path = SELECT_STORES[value & 15], SELECT_PATHS[value >> 4]
+    return store if store.startswith("lds") else "%s/%s" % (store, path)
+
+
+def grouping_form(query, args):
+    """What `query` (one of GROUPING_QUERIES) answers for a GroupArgs block, as grouping_form_name spells it; raises where the
+    entry point would refuse the block.  Host only: nothing is launched."""
+    rc = getattr(lib(), query)(ctypes.byref(args))
+    if rc < 0:
+        check(rc)
+    return grouping_form_name(query, rc)
+
+
 SoftmaxValidArgs = _struct("elo_softmax_valid_args", [
     ("batch", _i), ("npoints", _i), ("C", _i), ("feature", _vp), ("weight", _vp), ("xyz", _vp), ("out", _vp),
     ("scratch", _vp), ("stats", _vp)])
@@ -235,6 +267,10 @@ SYMBOLS = [
     ("elo_fused_conv_random_k_dense_fits", ctypes.c_int, [ctypes.c_int] * 5),
     ("elo_fused_conv_select_k_dense_fits", ctypes.c_int, [ctypes.c_int] * 6),
     ("elo_debug_select_dense_waves", ctypes.c_int, [ctypes.c_int]),
+    ("elo_fused_conv_random_k_form", ctypes.c_int, [ctypes.POINTER(GroupArgs)]),
+    ("elo_fused_conv_select_k_form", ctypes.c_int, [ctypes.POINTER(GroupArgs)]),
+    ("elo_fused_conv_random_k_dense_form", ctypes.c_int, [ctypes.POINTER(GroupArgs)]),
+    ("elo_fused_conv_select_k_dense_form", ctypes.c_int, [ctypes.POINTER(GroupArgs)]),
     ("elo_perm_refresh", ctypes.c_int, [ctypes.POINTER(PermRefreshArgs), _vp]),
     ("elo_group_concat", ctypes.c_int, [ctypes.POINTER(GroupConcatArgs), _vp]),
     ("elo_masked_maxpool", ctypes.c_int, [ctypes.POINTER(MaskedMaxpoolArgs), _vp]),

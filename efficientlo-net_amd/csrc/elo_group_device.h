@@ -151,6 +151,24 @@ __host__ __device__ __forceinline__ bool select_in_registers(int KT, int K)
     return (KT <= 512 && K <= 8) || (KT <= 192 && K <= 32);
 }
 
+// J of the register form for a window of KT slots (wave_select_k instantiates select_rounds_in_registers<J> by these bounds)
+__host__ __device__ __forceinline__ int select_register_window(int KT) { return KT <= 128 ? 2 : KT <= 192 ? 3 : 8; }
+
+// How select_rounds_in_registers<J> selects `rounds` = min(K, KT) elements (`cand`: the caller lent it 128 words of wave-private
+// LDS), as a predicate: elo_fused_conv_select_k_form answers with it.  The kernel's own ladder further down keeps its measured
+// spelling (routing it through this function changed the generated code of every kernel that groups in-kernel); the two are
+// to be changed together.  SMALL and MID hand over to the swap rounds (MID: to RANK first) when their rank check fails.
+// SMALL, MID and ROUNDS carry the values of ELO_SELECT_PATH_* (include/elo.h).  RANK -- a caller that lends no scratch, or 64
+// rounds and more -- is never an answer of the query: group_select_k always lends scratch and takes K <= 32 in registers.
+enum SelectPath { SELECT_PATH_SMALL = 1, SELECT_PATH_MID = 2, SELECT_PATH_ROUNDS = 3, SELECT_PATH_RANK = 4 };
+__host__ __device__ __forceinline__ int select_register_path(int J, int rounds, bool cand)
+{
+    if (rounds <= 7 && cand) return SELECT_PATH_SMALL;
+    if (J <= 3 && rounds < 64 && cand) return SELECT_PATH_MID;
+    if (J <= 3) return SELECT_PATH_RANK;
+    return SELECT_PATH_ROUNDS;
+}
+
 // wave-private LDS words select-k needs per wave: the two [KT] arrays of the LDS form, or the 2 x 64 candidate slots of
 // the register form's small-K rank path
 __host__ __device__ __forceinline__ int select_scratch_words(int KT, int K)
@@ -336,6 +354,7 @@ __device__ __forceinline__ int select_rounds_in_registers(const Grid &grid2, int
     {
         int count = 0;
         bool done = false;
+        // (select_register_path states this ladder for the host; the branches themselves stay as they were measured)
         if (rounds <= 7 && cand) done = select_small_k<J>(d, pw, rounds, cand, emit, count);
         else if (J <= 3 && rounds < 64 && cand) {
             done = select_mid_k<J>(d, pw, rounds, cand, emit, count);
@@ -417,7 +436,7 @@ __device__ __forceinline__ int wave_select_k(const Grid &grid2, int H2, int W2, 
     const int rounds = K < KT ? K : KT;
     if (select_in_registers(KT, K)) {
         unsigned *cand = dist;                          // wave-private scratch of the caller: >= 128 words (or null)
-        if (KT <= 128)
+        if (KT <= 128)                                  // (J by window size: select_register_window says the same to the host)
             return select_rounds_in_registers<2>(grid2, H2, W2, KT, rounds, lds_off, base_h, base_w, cx, cy, cz, r2, cand, emit, seen, taken);
         if (KT <= 192)
             return select_rounds_in_registers<3>(grid2, H2, W2, KT, rounds, lds_off, base_h, base_w, cx, cy, cz, r2, cand, emit, seen, taken);

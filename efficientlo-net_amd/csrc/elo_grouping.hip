@@ -669,6 +669,21 @@ int check_args(const elo_group_args *a, const char *who, bool dense = false)
 }  // namespace
 }  // namespace elo
 
+// the form of the general random-k kernel: G lanes per centre, U window slots per lane and step (see group_random_k)
+static int random_form(int KT, int K)
+{
+    if (KT <= 16) return ELO_RANDOM_G16U1;
+    if (KT <= 32) return ELO_RANDOM_G32U1;
+    return K <= 16 ? ELO_RANDOM_G16U4 : ELO_RANDOM_G32U2;
+}
+
+extern "C" int elo_fused_conv_random_k_form(const elo_group_args *a)
+{
+    using namespace elo;
+    if (int rc = check_args(a, "elo_fused_conv_random_k_form")) return rc;
+    return random_form(a->kernel_h * a->kernel_w, a->K);
+}
+
 extern "C" int elo_fused_conv_random_k(const elo_group_args *a, elo_stream_t stream)
 {
     using namespace elo;
@@ -679,14 +694,12 @@ extern "C" int elo_fused_conv_random_k(const elo_group_args *a, elo_stream_t str
     const size_t lds = sizeof(int) * KT;
     hipStream_t s = (hipStream_t)stream;
     const auto grid = [&](int G) { return dim3((unsigned)((total + ELO_BLOCK / G - 1) / (ELO_BLOCK / G))); };
-    if (KT <= 16)
-        hipLaunchKernelGGL((group_random_k<16, 1>), grid(16), dim3(ELO_BLOCK), lds, s, *a, total);
-    else if (KT <= 32)
-        hipLaunchKernelGGL((group_random_k<32, 1>), grid(32), dim3(ELO_BLOCK), lds, s, *a, total);
-    else if (a->K <= 16)
-        hipLaunchKernelGGL((group_random_k<16, 4>), grid(16), dim3(ELO_BLOCK), lds, s, *a, total);
-    else
-        hipLaunchKernelGGL((group_random_k<32, 2>), grid(32), dim3(ELO_BLOCK), lds, s, *a, total);
+    switch (random_form(KT, a->K)) {
+    case ELO_RANDOM_G16U1: hipLaunchKernelGGL((group_random_k<16, 1>), grid(16), dim3(ELO_BLOCK), lds, s, *a, total); break;
+    case ELO_RANDOM_G32U1: hipLaunchKernelGGL((group_random_k<32, 1>), grid(32), dim3(ELO_BLOCK), lds, s, *a, total); break;
+    case ELO_RANDOM_G16U4: hipLaunchKernelGGL((group_random_k<16, 4>), grid(16), dim3(ELO_BLOCK), lds, s, *a, total); break;
+    default: hipLaunchKernelGGL((group_random_k<32, 2>), grid(32), dim3(ELO_BLOCK), lds, s, *a, total); break;
+    }
     return check_launch("elo_fused_conv_random_k");
 }
 
@@ -711,26 +724,77 @@ extern "C" int elo_fused_conv_random_k_dense_fits(int kernel_h, int kernel_w, in
     return dense_lds_bytes(kernel_h, kernel_w, K, stride_h, stride_w, 2) != 0;
 }
 
-extern "C" int elo_fused_conv_random_k_dense(const elo_group_args *a, elo_stream_t stream)
+// rows of 64 centres per workgroup of the dense random-k form for a checked block (2 or 4), 0 = no tile fits / a bad forced value
+static int random_dense_rows(const elo_group_args *a)
 {
     using namespace elo;
-    const char *who = "elo_fused_conv_random_k_dense";
-    if (int rc = check_args(a, who, true)) return rc;
-    if (a->batch == 0) return ELO_OK;
     // 4 rows per workgroup share more of the window; 2 rows give twice the workgroups (small grids, large windows)
     const int forced = tuning().random_dense_rows;
     const long tiles4 = (long)((a->W + DENSE_COLS - 1) / DENSE_COLS) * ((a->H + 3) / 4) * a->batch;
     const auto lds_of = [&](int rows) { return dense_lds_bytes(a->kernel_h, a->kernel_w, a->K, a->stride_h, a->stride_w, rows); };
     int rows = forced ? forced : (tiles4 >= 1024 && lds_of(4) ? 4 : 2);
     if (rows == 4 && !lds_of(4)) rows = 2;
-    const size_t lds = lds_of(rows);
-    if ((rows != 2 && rows != 4) || lds == 0)
-        return fail(ELO_ERR_LIMIT, "%s: window %dx%d with K = %d does not fit the LDS tile (use elo_fused_conv_random_k)",
-                    who, a->kernel_h, a->kernel_w, a->K);
+    return (rows != 2 && rows != 4) || lds_of(rows) == 0 ? 0 : rows;
+}
+
+static int random_dense_refusal(const elo_group_args *a, const char *who)
+{
+    return elo::fail(ELO_ERR_LIMIT, "%s: window %dx%d with K = %d does not fit the LDS tile (use elo_fused_conv_random_k)",
+                     who, a->kernel_h, a->kernel_w, a->K);
+}
+
+extern "C" int elo_fused_conv_random_k_dense_form(const elo_group_args *a)
+{
+    using namespace elo;
+    const char *who = "elo_fused_conv_random_k_dense_form";
+    if (int rc = check_args(a, who, true)) return rc;
+    const int rows = random_dense_rows(a);
+    if (!rows) return random_dense_refusal(a, who);
+    return rows == 4 ? ELO_RANDOM_DENSE_ROWS4 : ELO_RANDOM_DENSE_ROWS2;
+}
+
+extern "C" int elo_fused_conv_random_k_dense(const elo_group_args *a, elo_stream_t stream)
+{
+    using namespace elo;
+    const char *who = "elo_fused_conv_random_k_dense";
+    if (int rc = check_args(a, who, true)) return rc;
+    if (a->batch == 0) return ELO_OK;
+    const int rows = random_dense_rows(a);
+    if (!rows) return random_dense_refusal(a, who);
+    const size_t lds = dense_lds_bytes(a->kernel_h, a->kernel_w, a->K, a->stride_h, a->stride_w, rows);
     const dim3 grid((unsigned)((a->W + DENSE_COLS - 1) / DENSE_COLS), (unsigned)((a->H + rows - 1) / rows), (unsigned)a->batch);
     if (rows == 4) hipLaunchKernelGGL(group_random_k_dense<4>, grid, dim3(256), lds, (hipStream_t)stream, *a);
     else hipLaunchKernelGGL(group_random_k_dense<2>, grid, dim3(128), lds, (hipStream_t)stream, *a);
     return check_launch(who);
+}
+
+// waves per block of group_select_k: 4 while the per-wave window state fits comfortably in LDS
+static int select_waves_per_block(int KT)
+{
+    int wpb = 4;
+    const size_t per_wave = (size_t)elo::select_wave_words(KT), order = ((size_t)KT + 3) & ~(size_t)3;
+    while (wpb > 1 && sizeof(int) * (order + per_wave * wpb) > 64 * 1024) wpb >>= 1;
+    return wpb;
+}
+
+// select_register_path (elo_group_device.h) answers in the header's values: the query hands them out unconverted
+static_assert(elo::SELECT_PATH_SMALL == ELO_SELECT_PATH_SMALL && elo::SELECT_PATH_MID == ELO_SELECT_PATH_MID &&
+              elo::SELECT_PATH_ROUNDS == ELO_SELECT_PATH_ROUNDS, "SelectPath and ELO_SELECT_PATH_* have drifted apart");
+static_assert(elo::SELECT_PATH_RANK != ELO_SELECT_PATH_SWAPS && elo::SELECT_PATH_RANK > ELO_SELECT_PATH_ROUNDS,
+              "SELECT_PATH_RANK must not collide with an enumerator of ELO_SELECT_PATH_*");
+
+extern "C" int elo_fused_conv_select_k_form(const elo_group_args *a)
+{
+    using namespace elo;
+    if (int rc = check_args(a, "elo_fused_conv_select_k_form")) return rc;
+    const int KT = a->kernel_h * a->kernel_w, K = a->K;
+    if (a->flag_copy == 0 && select_in_registers(KT, K)) {      // (group_select_k's own test, for every centre that is not at the origin)
+        const int J = select_register_window(KT);
+        return ELO_SELECT_FORM(J == 2 ? ELO_SELECT_REG2 : J == 3 ? ELO_SELECT_REG3 : ELO_SELECT_REG8,
+                               select_register_path(J, K < KT ? K : KT, true));
+    }
+    const int wpb = select_waves_per_block(KT);
+    return ELO_SELECT_FORM(wpb == 4 ? ELO_SELECT_LDS4 : wpb == 2 ? ELO_SELECT_LDS2 : ELO_SELECT_LDS1, ELO_SELECT_PATH_SWAPS);
 }
 
 extern "C" int elo_fused_conv_select_k(const elo_group_args *a, elo_stream_t stream)
@@ -740,10 +804,8 @@ extern "C" int elo_fused_conv_select_k(const elo_group_args *a, elo_stream_t str
     const long total = (long)a->batch * a->npoints;
     if (total == 0) return ELO_OK;
     const int KT = a->kernel_h * a->kernel_w;
-    // 4 waves per block while the per-wave window state fits comfortably in LDS
-    int wpb = 4;
+    const int wpb = select_waves_per_block(KT);
     const size_t per_wave = (size_t)select_wave_words(KT), order = ((size_t)KT + 3) & ~(size_t)3;
-    while (wpb > 1 && sizeof(int) * (order + per_wave * wpb) > 64 * 1024) wpb >>= 1;
     const size_t lds = sizeof(int) * (order + per_wave * wpb);
     const unsigned grid = (unsigned)((total + wpb - 1) / wpb);
     hipLaunchKernelGGL(group_select_k, dim3(grid), dim3(wpb * ELO_WAVE), lds, (hipStream_t)stream, *a, total, wpb);
@@ -771,25 +833,47 @@ extern "C" int elo_fused_conv_select_k_dense_fits(int kernel_h, int kernel_w, in
            sizeof(int) * select_dense_lds_words(16, kernel_h, kernel_w, stride_h, stride_w, true) <= LDS_LIMIT;
 }
 
+// the dense select-k form of a checked block: waves per tile (4 / 8 / 16) and whether the count masks are kept; a refusal is
+// reported under `who` and returned (negative)
+static int select_dense_waves(const elo_group_args *a, const char *who, bool *counts)
+{
+    using namespace elo;
+    const int KT = a->kernel_h * a->kernel_w;
+    if (!select_dense_shape(a->K, a->flag_copy, KT))
+        return fail(ELO_ERR_LIMIT, "%s: K = %d, flag_copy = %d, window %dx%d outside the dense form (K <= 7, flag_copy 0, <= 512 slots): "
+                    "use elo_fused_conv_select_k", who, a->K, a->flag_copy, a->kernel_h, a->kernel_w);
+    *counts = a->valid_idx || a->valid_in_dis_idx;
+    const long tiles = (long)((a->W + DENSE_COLS - 1) / DENSE_COLS) * a->H * a->batch;
+    // waves per tile: few tiles -> many waves each (latency: a wave's walk is KT / P probes, twice), many tiles -> 4
+    const int forced = tuning().select_dense_waves;
+    const int P = forced ? forced : tiles >= 1024 ? 4 : tiles >= 256 ? 8 : 16;
+    if (P != 4 && P != 8 && P != 16) return fail(ELO_ERR_ARG, "%s: elo_tuning.select_dense_waves must be 4, 8 or 16", who);
+    if (sizeof(int) * select_dense_lds_words(P, a->kernel_h, a->kernel_w, a->stride_h, a->stride_w, *counts) > LDS_LIMIT)
+        return fail(ELO_ERR_LIMIT, "%s: window %dx%d does not fit the LDS tile (use elo_fused_conv_select_k)", who, a->kernel_h, a->kernel_w);
+    return P;
+}
+
+extern "C" int elo_fused_conv_select_k_dense_form(const elo_group_args *a)
+{
+    using namespace elo;
+    const char *who = "elo_fused_conv_select_k_dense_form";
+    if (int rc = check_args(a, who, true)) return rc;
+    bool counts = false;
+    const int P = select_dense_waves(a, who, &counts);
+    if (P < 0) return P;
+    return ELO_SELECT_DENSE_FORM(P == 4 ? ELO_SELECT_DENSE_W4 : P == 8 ? ELO_SELECT_DENSE_W8 : ELO_SELECT_DENSE_W16, counts ? 1 : 0);
+}
+
 extern "C" int elo_fused_conv_select_k_dense(const elo_group_args *a, elo_stream_t stream)
 {
     using namespace elo;
     const char *who = "elo_fused_conv_select_k_dense";
     if (int rc = check_args(a, who, true)) return rc;
     if (a->batch == 0) return ELO_OK;
-    const int KT = a->kernel_h * a->kernel_w;
-    if (!select_dense_shape(a->K, a->flag_copy, KT))
-        return fail(ELO_ERR_LIMIT, "%s: K = %d, flag_copy = %d, window %dx%d outside the dense form (K <= 7, flag_copy 0, <= 512 slots): "
-                    "use elo_fused_conv_select_k", who, a->K, a->flag_copy, a->kernel_h, a->kernel_w);
-    const bool counts = a->valid_idx || a->valid_in_dis_idx;
-    const long tiles = (long)((a->W + DENSE_COLS - 1) / DENSE_COLS) * a->H * a->batch;
-    // waves per tile: few tiles -> many waves each (latency: a wave's walk is KT / P probes, twice), many tiles -> 4
-    const int forced = tuning().select_dense_waves;
-    int P = forced ? forced : tiles >= 1024 ? 4 : tiles >= 256 ? 8 : 16;
-    if (P != 4 && P != 8 && P != 16) return fail(ELO_ERR_ARG, "%s: elo_tuning.select_dense_waves must be 4, 8 or 16", who);
+    bool counts = false;
+    const int P = select_dense_waves(a, who, &counts);
+    if (P < 0) return P;
     const size_t lds = sizeof(int) * select_dense_lds_words(P, a->kernel_h, a->kernel_w, a->stride_h, a->stride_w, counts);
-    if (lds > LDS_LIMIT)
-        return fail(ELO_ERR_LIMIT, "%s: window %dx%d does not fit the LDS tile (use elo_fused_conv_select_k)", who, a->kernel_h, a->kernel_w);
     const dim3 grid((unsigned)((a->W + DENSE_COLS - 1) / DENSE_COLS), (unsigned)a->H, (unsigned)a->batch);
     hipStream_t s = (hipStream_t)stream;
 #define ELO_SD(PW)                                                                                              \

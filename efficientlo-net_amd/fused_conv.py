@@ -96,6 +96,19 @@ def grouping_entry(kind, kH, kW, K, flag_copy, stride_h, stride_w, dense_ok):
     return "elo_fused_conv_%s_k%s" % (kind, "_dense" if dense_ok and fits else "")
 
 
+def grouping_form(kind, B, H, W, npoints, kernel_size_H, kernel_size_W, K, flag_copy=0, distance=1.0, stride_h=1, stride_w=1,
+                  want_valid=True, dense=False):
+    """The kernel form (as _lib.grouping_form_name spells it) that a "random" / "select" grouping call of these sizes takes
+    through its general (dense=False) or LDS-tiled (dense=True) entry point, under the current tuning; raises _lib.EloError
+    where that entry point would refuse the call.  Host only: the queries read no tensor, so the block carries placeholder
+    addresses (want_valid says whether the two prefix masks are asked for, which the dense select-k form depends on)."""
+    H2, W2 = -(-H // stride_h) if stride_h > 0 else 0, -(-W // stride_w) if stride_w > 0 else 0
+    there = 1 << 12                                            # any non-NULL address: never read
+    args = _lib.GroupArgs(B, H, W, H2, W2, npoints, kernel_size_H, kernel_size_W, K, flag_copy, float(distance), stride_h, stride_w,
+                          there, there, there, there, there, there if want_valid else None, there if want_valid else None, there)
+    return _lib.grouping_form("elo_fused_conv_%s_k%s_form" % (kind, "_dense" if dense else ""), args)
+
+
 def _launch(kind, name, xyz1, xyz2, idx_n2, random_hw, H, W, npoints, kernel_size_H, kernel_size_W, K,
             flag_copy, distance, stride_h, stride_w, want_valid, dense=None):
     # H, W attributes are unused by the reference's Compute as well: the real

@@ -159,6 +159,36 @@ int elo_fused_conv_select_k_dense_fits(int kernel_h, int kernel_w, int K, int fl
 /* debugging hook: force 4, 8 or 16 waves per tile in elo_fused_conv_select_k_dense (0 = chosen by grid size; also
  * ELO_SELECT_DENSE_WAVES); returns the previous setting */
 int elo_debug_select_dense_waves(int waves);
+/* WHICH KERNEL FORM the four grouping entry points take for an argument block.  Host arithmetic only: nothing is launched and no
+ * memory behind the block's pointers is read (only their being NULL or not); the two dense queries also read the current
+ * elo_tuning (random_dense_rows / select_dense_waves).  Each entry point switches on the same function as its query, so the answer
+ * is what a launch with this block takes.  Return: an enumerator below, or the negative elo_status with which the entry point
+ * would refuse the block.  All forms of an entry point compute the same outputs bit for bit.
+ *   elo_fused_conv_random_k: G<lanes per centre>U<window slots per lane and step>: up to 16 slots G16U1, up to 32 G32U1, above
+ *     that G16U4 for K <= 16 and G32U2 for a larger K.
+ *   elo_fused_conv_random_k_dense: ROWS<rows of 64 centres per workgroup>: the forced elo_tuning.random_dense_rows, else 4 from
+ *     1024 four-row tiles on; 2 wherever the four-row tile does not fit 64 KB of LDS (ELO_ERR_LIMIT where 2 rows do not either).
+ *   elo_fused_conv_select_k: ELO_SELECT_FORM(store, path).  store: REG<J> -- the window in J registers per lane (flag_copy 0 and
+ *     K <= 8 with at most 512 slots, or K <= 32 with at most 192; J = 2 up to 128 slots, 3 up to 192, else 8) -- or LDS<waves per
+ *     block> (4 while 4 * (order + 4 waves' window state) fits 64 KB: up to 1820 slots; 2 up to 3276; else 1).  path (REG only; the
+ *     LDS forms answer ELO_SELECT_PATH_SWAPS): with rounds = min(K, slots), SMALL for rounds <= 7 (candidates below the largest of
+ *     eight lane-group minima, ranked), MID for J <= 3 (candidates below the (rounds+1)-th lane minimum, ranked; the whole window
+ *     ranked when that gives up), ROUNDS for J = 8 with K = 8 (the swap rounds in registers).  SMALL and MID fall back to the swap
+ *     rounds on an exact tie that touches the selected elements or the first one left out; a centre at the origin is zero-filled
+ *     by every form.
+ *   elo_fused_conv_select_k_dense: ELO_SELECT_DENSE_FORM(waves, counts): W4 / W8 / W16 waves per 64-centre tile (the forced
+ *     elo_tuning.select_dense_waves, else by the tile count), counts = 1 where valid_idx or valid_in_dis_idx is asked for. */
+enum { ELO_RANDOM_G16U1 = 0, ELO_RANDOM_G32U1 = 1, ELO_RANDOM_G16U4 = 2, ELO_RANDOM_G32U2 = 3 };
+enum { ELO_RANDOM_DENSE_ROWS2 = 0, ELO_RANDOM_DENSE_ROWS4 = 1 };
+enum { ELO_SELECT_REG2 = 0, ELO_SELECT_REG3 = 1, ELO_SELECT_REG8 = 2, ELO_SELECT_LDS4 = 3, ELO_SELECT_LDS2 = 4, ELO_SELECT_LDS1 = 5 };
+enum { ELO_SELECT_PATH_SWAPS = 0, ELO_SELECT_PATH_SMALL = 1, ELO_SELECT_PATH_MID = 2, ELO_SELECT_PATH_ROUNDS = 3 };
+#define ELO_SELECT_FORM(store, path) ((store) | (path) << 4)
+enum { ELO_SELECT_DENSE_W4 = 0, ELO_SELECT_DENSE_W8 = 1, ELO_SELECT_DENSE_W16 = 2 };
+#define ELO_SELECT_DENSE_FORM(waves, counts) ((waves) | (counts) << 4)
+int elo_fused_conv_random_k_form(const elo_group_args *a);
+int elo_fused_conv_select_k_form(const elo_group_args *a);
+int elo_fused_conv_random_k_dense_form(const elo_group_args *a);
+int elo_fused_conv_select_k_dense_form(const elo_group_args *a);
 
 /* ------------------------------------------------------------------------- *
  * Feature path: fused gather / encode / pool kernels.  These replace chains of

@@ -28,3 +28,20 @@ def test_ctypes_structs_mirror_the_header(tmp_path):
         assert ctypes.sizeof(cls) == int(want[name]), name
         for field, _ in cls._fields_:
             assert getattr(cls, field).offset == int(want["%s.%s" % (name, field)]), (name, field)
+
+
+def test_grouping_block_and_its_form_queries():
+    """elo_group_args (mirrored as GroupArgs) field by field, and the four form queries that take it: declared in the header,
+    bound in the ctypes table with that block as their only argument."""
+    import re
+    L = load_pkg("_lib")
+    header = open(os.path.join(ROOT, "include", "elo.h")).read()
+    body = re.search(r"typedef struct elo_group_args \{(.*?)\} elo_group_args;", header, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    declared = [re.sub(r"^.*[\s*]", "", name.strip()) for d in body.split(";") if d.strip() for name in d.split(",")]
+    assert [name for name, _ in L.GroupArgs._fields_] == declared
+    for query in ("elo_fused_conv_random_k_form", "elo_fused_conv_select_k_form", "elo_fused_conv_random_k_dense_form",
+                  "elo_fused_conv_select_k_dense_form"):
+        assert re.search(r"^int %s\(const elo_group_args \*a\);" % query, header, re.M)
+        assert (query, ctypes.c_int, [ctypes.POINTER(L.GroupArgs)]) in L.SYMBOLS
+    assert tuple(L.GROUPING_QUERIES) == tuple(q for q in (n for n, _r, _a in L.SYMBOLS) if q.startswith("elo_fused_conv") and q.endswith("_form"))
