@@ -163,6 +163,11 @@ MapExtractArgs = _struct("elo_map_extract_args", [
     ("voxel", _f), ("log2_capacity", _i), ("max_out", ctypes.c_long), ("keys", _vp), ("acc", _vp), ("out_key", _vp), ("out_count", _vp),
     ("out_xyz", _vp), ("cursor", _vp)])
 MAP_MAX_PROBE, MAP_MIN_LOG2, MAP_MAX_LOG2 = 128, 10, 28        # ELO_MAP_*
+MapMergeArgs = _struct("elo_map_merge_args", [
+    ("rows", ctypes.c_long), ("src_keys", _vp), ("src_acc", _vp), ("voxel", _f), ("log2_capacity", _i), ("keys", _vp), ("acc", _vp),
+    ("stats", _vp), ("centre", _vp), ("radius", _f), ("min_count", ctypes.c_longlong), ("report", _vp)])
+MAP_REPORT = ("voxels_merged", "voxels_filtered", "voxels_rejected", "voxels_dropped", "points_merged", "points_filtered",
+              "points_dropped", "claimed")                     # the words of elo_map_merge_args.report, in order
 MapFitArgs = _struct("elo_map_fit_args", [
     ("batch", _i), ("H", _i), ("W", _i), ("voxel", _f), ("log2_capacity", _i), ("keys", _vp), ("acc", _vp), ("xyz", _vp),
     ("pose_in", _vp), ("iters", _i), ("gate", _f), ("huber", _f), ("jump_rel", _f), ("min_count", _i), ("damping", _f),
@@ -297,6 +302,7 @@ SYMBOLS = [
     ("elo_model_advance", ctypes.c_int, [ctypes.POINTER(ModelAdvanceArgs), _vp]),
     ("elo_map_insert", ctypes.c_int, [ctypes.POINTER(MapInsertArgs), _vp]),
     ("elo_map_extract", ctypes.c_int, [ctypes.POINTER(MapExtractArgs), _vp]),
+    ("elo_map_merge", ctypes.c_int, [ctypes.POINTER(MapMergeArgs), _vp]),
     ("elo_map_fit", ctypes.c_int, [ctypes.POINTER(MapFitArgs), _vp]),
     ("elo_map_fit_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
     ("elo_map_fit_parts", ctypes.c_int, [ctypes.c_int] * 2),

@@ -5,6 +5,7 @@ whose backward is the matching `elo_*_backward` kernel -- there is no second (to
 nothing here looks at the global autograd mode.  Shapes are validated in C as well.  No CPU fallback: CPU tensors raise."""
 import collections
 import ctypes
+import math
 
 import numpy as np
 
@@ -971,6 +972,59 @@ def map_extract(keys, acc, spec, max_out):
                          xyz.data_ptr(), n.data_ptr())
     L.call("elo_map_extract", a, keys)
     return key[:max_out], count[:max_out], xyz[:max_out], n
+
+
+def _ranges_meet(a, b):
+    """Two tensors' memory ranges share a byte (an empty tensor shares none)."""
+    na, nb = a.numel() * a.element_size(), b.numel() * b.element_size()
+    return na > 0 and nb > 0 and a.data_ptr() < b.data_ptr() + nb and b.data_ptr() < a.data_ptr() + na
+
+
+def _check_map_merge(keys, acc, stats, src_keys, src_acc, spec, centre, radius, min_count):
+    """What the host can refuse about a merge without a GPU or the library -> (radius as a float, min_count as an int)."""
+    _check_map(keys, acc, spec, stats)
+    _check_tensors((("src_keys", src_keys, torch.int64), ("src_acc", src_acc, torch.int64)))
+    if src_keys.dim() != 1 or tuple(src_acc.shape) != (src_keys.shape[0], 4):
+        raise L.EloError("source rows are src_keys (rows,) and src_acc (rows, 4) (got %s, %s)" % (tuple(src_keys.shape), tuple(src_acc.shape)))
+    if src_keys.shape[0] >= 2 ** 31:
+        raise L.EloError("rows stays below 2^31 (got %d)" % src_keys.shape[0])
+    if src_keys.device != keys.device or src_acc.device != keys.device:
+        raise L.EloError("the map and the source rows live on one device")
+    if any(_ranges_meet(s, d) for s in (src_keys, src_acc) for d in (keys, acc)):
+        raise L.EloError("the source rows overlap the destination table: a table is not merged into itself")
+    if isinstance(min_count, bool) or not hasattr(min_count, "__index__") or not 1 <= min_count.__index__() < 2 ** 63:
+        raise L.EloError("min_count is an integer >= 1 (got %r)" % (min_count,))
+    if centre is None:
+        if radius is not None:
+            raise L.EloError("a radius needs the centre it is about")
+        return 0.0, min_count.__index__()
+    _check_tensors((("centre", centre, torch.float64),))
+    if centre.numel() != 3:
+        raise L.EloError("centre is 3 doubles x y z (got %s)" % (tuple(centre.shape),))
+    if centre.device != keys.device:
+        raise L.EloError("the map and the centre live on one device")
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not (math.isfinite(radius) and radius > 0):
+        raise L.EloError("with a centre, radius is positive and finite (got %r)" % (radius,))
+    return float(radius), min_count.__index__()
+
+
+def map_merge(keys, acc, stats, src_keys, src_acc, spec, centre=None, radius=None, min_count=1):
+    """elo_map_merge: the source rows src_keys (rows,), src_acc (rows,4) int64 -- another table's buffers, or the rows of a saved
+    state; a key of -1 is an empty slot -- filtered and added into the voxel map (keys, acc, stats, spec as map_insert's) -> report,
+    an (8,) int64 device tensor of L.MAP_REPORT.  centre: a contiguous float64 device tensor of 3 elements (a view such as
+    world64[4:] qualifies), read when the launch RUNS, with radius (m): rows whose voxel centre lies outside the box are filtered;
+    min_count: rows with fewer points are filtered.  One launch on the current stream, no host synchronisation, capturable.  Bad
+    types, shapes, layouts, devices and overlap are refused here, before the library is touched."""
+    radius, min_count = _check_map_merge(keys, acc, stats, src_keys, src_acc, spec, centre, radius, min_count)
+    L.require_gpu(keys, acc, stats, src_keys, src_acc, centre)
+    report = torch.zeros((8,), dtype=torch.int64, device=keys.device)
+    rows = src_keys.shape[0]
+    none = report.data_ptr()                                  # (an empty tensor has no address: rows = 0 reads nothing)
+    a = L.MapMergeArgs(rows, src_keys.data_ptr() if rows else none, src_acc.data_ptr() if rows else none, spec.voxel,
+                       spec.log2_capacity, keys.data_ptr(), acc.data_ptr(), stats.data_ptr(), _ptr(centre), radius, min_count,
+                       report.data_ptr())
+    L.call("elo_map_merge", a, keys)
+    return report
 
 
 class MapFitResult(PoseFitResult):

@@ -11,6 +11,8 @@
 // ballot, butterfly sum -- costs 24 shuffles per key: slower than one add per point below ~8 cells a key; tools/micro/map_atomics.hip
 // holds all three forms.)  The counters go the same way: ballots and one add per wave and counter.
 // map_extract_kernel: one thread per slot, ballot compaction, one atomic on the cursor per wave.
+// map_merge_kernel (elo_map_merge): source rows (key, four integers) filtered and added into a table through the insert's own
+// probe / claim / add (map_add, elo_map_device.h): the sliding window, growth, a loaded state and the union of two maps.
 #include "elo_map_device.h"
 
 namespace elo {
@@ -49,24 +51,6 @@ __device__ __forceinline__ int map_point(const MapInsert &a, const double (&R)[9
     if (!map_axis(x, voxel, fx, g[0]) || !map_axis(y, voxel, fy, g[1]) || !map_axis(z, voxel, fz, g[2])) return MAP_REJECTED;
     key = fx << 42 | fy << 21 | fz;
     return MAP_POINT;
-}
-
-// the slot of `key`, claimed where it has none yet; false: none within ELO_MAP_MAX_PROBE.  A slot only ever turns from empty into
-// one key, so a plain load that shows another key is final and one that shows empty is settled by the CAS.
-__device__ __forceinline__ bool map_slot(unsigned long long *keys, const unsigned long long mask, const unsigned long long key,
-                                         unsigned long long &slot, unsigned &claimed)
-{
-    const unsigned long long home = map_home(key);
-    for (int j = 0; j < ELO_MAP_MAX_PROBE; ++j) {
-        const unsigned long long s = (home + (unsigned long long)j) & mask;
-        unsigned long long cur = __atomic_load_n(keys + s, __ATOMIC_RELAXED);
-        if (cur == MAP_EMPTY) {
-            cur = atomicCAS(keys + s, MAP_EMPTY, key);
-            if (cur == MAP_EMPTY) { claimed += 1u; cur = key; }
-        }
-        if (cur == key) { slot = s; return true; }
-    }
-    return false;
 }
 
 __device__ __forceinline__ unsigned wave_sum(unsigned v)
@@ -141,17 +125,11 @@ __global__ __launch_bounds__(ELO_BLOCK) void map_insert_kernel(const MapInsert a
         }
         const bool last = lane == MAP_WAVE - 1 || (heads >> (lane + 1u) & 1ull) != 0ull;
         if (last && n != 0u) {
-            unsigned long long slot;
-            if (map_slot(a.keys, a.mask, mine, slot, claimed)) {
-                unsigned long long *row = a.acc + slot * 4ull;
-                atomicAdd(row + 0, (unsigned long long)n);
-                atomicAdd(row + 1, (unsigned long long)gx);
-                atomicAdd(row + 2, (unsigned long long)gy);
-                atomicAdd(row + 3, (unsigned long long)gz);
+            if (map_add(a.keys, a.acc, a.mask, mine, (unsigned long long)n, (unsigned long long)gx, (unsigned long long)gy,
+                        (unsigned long long)gz, claimed))
                 inserted += n;
-            } else {
+            else
                 dropped += n;
-            }
         }
     }
     inserted = wave_sum(inserted);
@@ -206,6 +184,130 @@ __global__ __launch_bounds__(ELO_BLOCK) void map_extract_kernel(const MapExtract
     a.out_xyz[row * 3 + 2] = map_centroid(key & 0x1fffffull, acc[3], count, voxel);
 }
 
+constexpr int MERGE_STRIP = 2;                          // source rows per lane and step: their keys are one 16-byte load
+constexpr int MERGE_STEPS = 8;                          // steps per wave: 1024 neighbouring rows
+constexpr int MERGE_TILE = ELO_BLOCK * MERGE_STRIP * MERGE_STEPS;      // source rows per workgroup
+
+struct MapMerge {
+    unsigned long long rows;
+    const unsigned long long *src_keys, *src_acc;
+    float voxel, radius;
+    unsigned long long mask;        // C - 1, the destination's
+    unsigned long long *keys, *acc, *stats;
+    const double *centre;           // NULL: no window
+    unsigned long long min_count;
+    unsigned long long *report;
+    int vec_keys, vec_acc;          // 1: src_keys / src_acc is 16-byte aligned
+};
+
+enum { MERGE_SKIP = 0, MERGE_REJECTED = 1, MERGE_FILTERED = 2, MERGE_ROW = 3 };
+
+// the per-row rule of include/elo.h for an occupied source row (key is not all ones) -> MERGE_REJECTED / FILTERED / ROW
+__device__ __forceinline__ int merge_row(const MapMerge &a, const double (&centre)[3], unsigned long long key,
+                                         const unsigned long long (&r)[4])
+{
+    const unsigned long long n = r[0];
+    if (key >> 63 != 0ull || n == 0ull || n >= 1ull << 40) return MERGE_REJECTED;
+    const unsigned long long most = 65535ull * n;                                       // < 2^56
+    if (r[1] > most || r[2] > most || r[3] > most) return MERGE_REJECTED;
+    if (n < a.min_count) return MERGE_FILTERED;
+    if (a.centre) {
+        const double voxel = (double)a.voxel, radius = (double)a.radius;
+        for (int axis = 0; axis < 3; ++axis) {
+            const unsigned long long field = key >> (42 - 21 * axis) & 0x1fffffull;
+            const double c = ((double)((long long)field - (1ll << 20)) + 0.5) * voxel;
+            const double d = fabs(c - centre[axis]);
+            if (!(d <= radius)) return MERGE_FILTERED;                                  // (a NaN centre keeps nothing)
+        }
+    }
+    return MERGE_ROW;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+    for (int d = MAP_WAVE / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, MAP_WAVE);
+    return v;
+}
+
+// a stream over src_keys, 8 bytes a source row.  A wave takes MERGE_STEPS * 128 neighbouring rows, 128 a step (a lane two
+// neighbours: one 16-byte load), all its key loads issued before the first is looked at; a step whose 128 slots are all empty -- most
+// steps over a table -- costs no more.  The 32 bytes of an acc row are read for occupied rows only.  Every kept row is one map_add: a
+// source has a key once (a table) or a few times (concatenated states), so there are no runs to fold.  The counters are the wave's,
+// one add per wave and counter: with one step a wave, a table of 2^22 slots made 32 768 waves add to the same few words and those
+// adds, not the probes, were the kernel's time (profiles/map_merge.txt).
+__global__ __launch_bounds__(ELO_BLOCK) void map_merge_kernel(const MapMerge a)
+{
+    const unsigned lane = threadIdx.x & (MAP_WAVE - 1);
+    const unsigned long long wave = (unsigned long long)blockIdx.x * (ELO_BLOCK / MAP_WAVE) + threadIdx.x / MAP_WAVE;
+    const unsigned long long first = (wave * MERGE_STEPS * MAP_WAVE + lane) * MERGE_STRIP;      // this lane's rows of step 0
+    unsigned long long key[MERGE_STEPS][MERGE_STRIP];
+    for (int step = 0; step < MERGE_STEPS; ++step) {
+        const unsigned long long i0 = first + (unsigned long long)step * (MAP_WAVE * MERGE_STRIP);
+        if (a.vec_keys && i0 + MERGE_STRIP <= a.rows) {
+            const ulonglong2 u = *reinterpret_cast<const ulonglong2 *>(a.src_keys + i0);
+            key[step][0] = u.x; key[step][1] = u.y;
+        } else {
+            for (int c = 0; c < MERGE_STRIP; ++c) key[step][c] = i0 + c < a.rows ? a.src_keys[i0 + c] : MAP_EMPTY;
+        }
+    }
+    double centre[3] = {0.0, 0.0, 0.0};
+    if (a.centre) { centre[0] = a.centre[0]; centre[1] = a.centre[1]; centre[2] = a.centre[2]; }
+    unsigned v_merged = 0, v_filtered = 0, v_rejected = 0, v_dropped = 0;               // wave-uniform: ballots
+    unsigned long long p_merged = 0, p_filtered = 0, p_dropped = 0;                     // this lane's
+    unsigned claimed = 0;
+    for (int step = 0; step < MERGE_STEPS; ++step) {
+        if (__ballot(key[step][0] != MAP_EMPTY || key[step][1] != MAP_EMPTY) == 0ull) continue;
+        const unsigned long long i0 = first + (unsigned long long)step * (MAP_WAVE * MERGE_STRIP);
+        for (int c = 0; c < MERGE_STRIP; ++c) {
+            int kind = MERGE_SKIP;
+            bool dropped = false;
+            if (key[step][c] != MAP_EMPTY) {
+                const unsigned long long *s = a.src_acc + (i0 + c) * 4ull;
+                unsigned long long r[4];
+                if (a.vec_acc) {
+                    const ulonglong2 u0 = reinterpret_cast<const ulonglong2 *>(s)[0], u1 = reinterpret_cast<const ulonglong2 *>(s)[1];
+                    r[0] = u0.x; r[1] = u0.y; r[2] = u1.x; r[3] = u1.y;
+                } else {
+                    for (int j = 0; j < 4; ++j) r[j] = s[j];
+                }
+                kind = merge_row(a, centre, key[step][c], r);
+                if (kind == MERGE_ROW) {
+                    if (map_add(a.keys, a.acc, a.mask, key[step][c], r[0], r[1], r[2], r[3], claimed)) p_merged += r[0];
+                    else { dropped = true; p_dropped += r[0]; }
+                } else if (kind == MERGE_FILTERED) {
+                    p_filtered += r[0];
+                }
+            }
+            v_merged += (unsigned)__popcll(__ballot(kind == MERGE_ROW && !dropped));
+            v_filtered += (unsigned)__popcll(__ballot(kind == MERGE_FILTERED));
+            v_rejected += (unsigned)__popcll(__ballot(kind == MERGE_REJECTED));
+            v_dropped += (unsigned)__popcll(__ballot(dropped));
+        }
+    }
+    if ((v_merged | v_filtered | v_rejected | v_dropped) == 0u) return;                 // (wave-uniform) only empty slots
+    p_merged = wave_sum64(p_merged);
+    p_filtered = wave_sum64(p_filtered);
+    p_dropped = wave_sum64(p_dropped);
+    claimed = wave_sum(claimed);
+    if (lane == 0u) {
+        if (v_merged) atomicAdd(a.report + 0, (unsigned long long)v_merged);
+        if (v_filtered) atomicAdd(a.report + 1, (unsigned long long)v_filtered);
+        if (v_rejected) atomicAdd(a.report + 2, (unsigned long long)v_rejected);
+        if (v_dropped) atomicAdd(a.report + 3, (unsigned long long)v_dropped);
+        if (p_merged) { atomicAdd(a.report + 4, p_merged); atomicAdd(a.stats + 0, p_merged); }
+        if (p_filtered) atomicAdd(a.report + 5, p_filtered);
+        if (p_dropped) { atomicAdd(a.report + 6, p_dropped); atomicAdd(a.stats + 3, p_dropped); }
+        if (claimed) { atomicAdd(a.report + 7, (unsigned long long)claimed); atomicAdd(a.stats + 4, (unsigned long long)claimed); }
+    }
+}
+
+// [p, p + pb) and [q, q + qb) share a byte
+inline bool map_ranges_meet(const void *p, unsigned long long pb, const void *q, unsigned long long qb)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return pb != 0ull && qb != 0ull && a < b + qb && b < a + pb;
+}
+
 #define ELO_REQUIRE(cond, who, what) \
     do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
 
@@ -250,5 +352,29 @@ extern "C" int elo_map_extract(const elo_map_extract_args *a, elo_stream_t strea
     const MapExtract e = {a->voxel, slots, (unsigned long long)a->max_out, a->keys, a->acc, a->out_key, a->out_count, a->out_xyz, a->cursor};
     hipLaunchKernelGGL(map_cursor_kernel, dim3(1), dim3(MAP_WAVE), 0, s, a->cursor);
     hipLaunchKernelGGL(map_extract_kernel, dim3((unsigned)(slots / ELO_BLOCK)), dim3(ELO_BLOCK), 0, s, e);    // <= 2^20 workgroups
+    return check_launch(who);
+}
+
+extern "C" int elo_map_merge(const elo_map_merge_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_map_merge";
+    ELO_REQUIRE(a, who, "null argument block");
+    ELO_REQUIRE(a->rows >= 0 && a->rows < (1l << 31), who, "rows is 0 .. 2^31 - 1");
+    ELO_REQUIRE(map_table_ok(a->voxel, a->log2_capacity), who, "voxel is positive and finite, log2_capacity ELO_MAP_MIN_LOG2 .. ELO_MAP_MAX_LOG2");
+    ELO_REQUIRE(a->min_count >= 1, who, "min_count is >= 1");
+    ELO_REQUIRE(!a->centre || (a->radius > 0.0f && a->radius - a->radius == 0.0f), who, "with a centre, radius is positive and finite");
+    ELO_REQUIRE(a->src_keys && a->src_acc && a->keys && a->acc && a->stats && a->report, who, "null pointer");
+    ELO_REQUIRE(aligned8(a->src_keys) && aligned8(a->src_acc) && aligned8(a->keys) && aligned8(a->acc) && aligned8(a->stats) &&
+                aligned8(a->centre) && aligned8(a->report), who, "src_keys, src_acc, keys, acc, stats, centre and report must be 8-byte aligned");
+    const unsigned long long rows = (unsigned long long)a->rows, slots = 1ull << a->log2_capacity;
+    ELO_REQUIRE(!map_ranges_meet(a->src_keys, rows * 8ull, a->keys, slots * 8ull) && !map_ranges_meet(a->src_keys, rows * 8ull, a->acc, slots * 32ull) &&
+                !map_ranges_meet(a->src_acc, rows * 32ull, a->keys, slots * 8ull) && !map_ranges_meet(a->src_acc, rows * 32ull, a->acc, slots * 32ull),
+                who, "the source rows overlap the destination table");
+    if (a->rows == 0) return ELO_OK;
+    const MapMerge m = {rows, a->src_keys, a->src_acc, a->voxel, a->radius, slots - 1ull, a->keys, a->acc, a->stats, a->centre,
+                        (unsigned long long)a->min_count, a->report, ((uintptr_t)a->src_keys & 15) == 0 ? 1 : 0,
+                        ((uintptr_t)a->src_acc & 15) == 0 ? 1 : 0};
+    const dim3 grid((unsigned)((rows + MERGE_TILE - 1) / MERGE_TILE));                  // < 2^19: rows < 2^31, 4096 rows a workgroup
+    hipLaunchKernelGGL(map_merge_kernel, grid, dim3(ELO_BLOCK), 0, (hipStream_t)stream, m);
     return check_launch(who);
 }

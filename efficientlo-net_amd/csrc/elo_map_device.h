@@ -1,5 +1,6 @@
 // elo_map_device.h -- the world map's rules that more than one file states (include/elo.h, WORLD MAP): the pose row, the voxel index
-// of a rounded coordinate, the hash, the centroid.  elo_map.hip writes the table by them and elo_mapfit.hip reads it by them.
+// of a rounded coordinate, the hash, the probe / claim / add, the centroid.  elo_map.hip writes the table by them (the insert and
+// the merge through the same map_add) and elo_mapfit.hip reads it by them.
 #pragma once
 #include "elo_common.h"
 
@@ -48,6 +49,40 @@ __device__ __forceinline__ float map_centroid(unsigned long long field, unsigned
 {
     const double i = (double)((long long)field - (1ll << 20));
     return (float)((i + ((double)s / (double)count + 0.5) / 65536.0) * voxel);
+}
+
+// the slot of `key`, claimed where it has none yet; false: none within ELO_MAP_MAX_PROBE.  A slot only ever turns from empty into
+// one key, so a plain load that shows another key is final and one that shows empty is settled by the CAS.
+__device__ __forceinline__ bool map_slot(unsigned long long *keys, const unsigned long long mask, const unsigned long long key,
+                                         unsigned long long &slot, unsigned &claimed)
+{
+    const unsigned long long home = map_home(key);
+    for (int j = 0; j < ELO_MAP_MAX_PROBE; ++j) {
+        const unsigned long long s = (home + (unsigned long long)j) & mask;
+        unsigned long long cur = __atomic_load_n(keys + s, __ATOMIC_RELAXED);
+        if (cur == MAP_EMPTY) {
+            cur = atomicCAS(keys + s, MAP_EMPTY, key);
+            if (cur == MAP_EMPTY) { claimed += 1u; cur = key; }
+        }
+        if (cur == key) { slot = s; return true; }
+    }
+    return false;
+}
+
+// probe / claim / add: {n, sx, sy, sz} into the voxel `key` of the table; false: no slot within the limit, nothing touched.  The
+// ONE writer of a table's rows: elo_map_insert sends a run's sums through it, elo_map_merge a source row's.
+__device__ __forceinline__ bool map_add(unsigned long long *keys, unsigned long long *acc, const unsigned long long mask,
+                                        const unsigned long long key, const unsigned long long n, const unsigned long long sx,
+                                        const unsigned long long sy, const unsigned long long sz, unsigned &claimed)
+{
+    unsigned long long slot;
+    if (!map_slot(keys, mask, key, slot, claimed)) return false;
+    unsigned long long *row = acc + slot * 4ull;
+    atomicAdd(row + 0, n);
+    atomicAdd(row + 1, sx);
+    atomicAdd(row + 2, sy);
+    atomicAdd(row + 3, sz);
+    return true;
 }
 
 inline bool map_table_ok(float voxel, int log2_capacity)

@@ -251,12 +251,16 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
     holds its voxels, float32 rows x y z count in the frame the first sample's pose leads to (WorldMap.save).
     `map_fit=MapFit(...)` with `world_map=VoxelMap(...)`: the map TRACKS -- every scan's composed pose is fitted against the map
     before the scan goes in (WorldMap(fit=)).  What predict_sequence returns does not change; `<out_dir>/<seq>_map_poses.txt`, beside
-    the map, holds one row per sample: the world pose q t the scan was inserted at, then count, rms and status of its fit."""
-    wmap, map_fit = kw.get("world_map"), kw.pop("map_fit", None)
+    the map, holds one row per sample: the world pose q t the scan was inserted at, then count, rms and status of its fit.
+    `map_window=MapWindow(...)` with `world_map=VoxelMap(...)`: the map follows the vehicle (WorldMap(window=)).  With a map,
+    `<out_dir>/<seq>_map_state.npz` holds its state (WorldMap.save_state): WorldMap.load_state continues from it."""
+    wmap, map_fit, map_window = kw.get("world_map"), kw.pop("map_fit", None), kw.pop("map_window", None)
     if map_fit is not None and not isinstance(wmap, VoxelMap):
         raise ValueError("map_fit= builds the tracking map itself: pass world_map=VoxelMap(...) with it")
+    if map_window is not None and not isinstance(wmap, VoxelMap):
+        raise ValueError("map_window= builds the windowed map itself: pass world_map=VoxelMap(...) with it")
     if isinstance(wmap, VoxelMap):
-        wmap = kw["world_map"] = WorldMap(wmap, device=net.device, fit=map_fit)
+        wmap = kw["world_map"] = WorldMap(wmap, device=net.device, fit=map_fit, window=map_window)
     q, t, *fit_out = predict_sequence(net, root, seq, T_diff, **kw)
     Tr = kitti.read_calib(os.path.join(root, seq, "calib.txt"))["Tr"]
     rows = pose_rows(q, t, Tr)
@@ -267,6 +271,7 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
             np.savetxt(os.path.join(out_dir, "%s_fit.txt" % seq), fit_out[0], fmt="%.9e")
         if wmap is not None:
             wmap.save(os.path.join(out_dir, "%s_map.bin" % seq))
+            wmap.save_state(os.path.join(out_dir, "%s_map_state.npz" % seq))
             if map_fit is not None:
                 log = wmap.fit_log().cpu().numpy().astype(np.float64)
                 table = np.concatenate([wmap.trajectory().cpu().numpy(), log[:, (0, 2, 3)]], 1)

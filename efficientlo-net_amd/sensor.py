@@ -17,7 +17,8 @@ one range image (elo_model_render; local_model.ModelTracker) instead of against 
 
 `VoxelMap` asks for the map the poses are for: every scan carried by its world pose into a hash table of voxels on the device
 (elo_map_insert; world_map.WorldMap).  `MapFit` asks for a scan's world pose to be fitted against that map before the scan goes
-in (elo_map_fit; WorldMap(fit=)).
+in (elo_map_fit; WorldMap(fit=)).  `MapWindow` asks for that map to follow the vehicle: what lies beyond a radius is dropped at a
+rebuild every few scans (elo_map_merge; WorldMap(window=)).
 """
 import math
 
@@ -182,8 +183,9 @@ class VoxelMap(_Frozen):
     its world pose into a hash table of voxels, each holding the count and the centroid of its points (elo_map_insert, include/elo.h;
     world_map.WorldMap).  Frozen and hashable.
     voxel (m): the edge of a voxel, finite and > 0; log2_capacity: the table has 1 << log2_capacity slots, an integer in 10 .. 28 (it
-    does not grow: points that find no slot are counted as dropped); min_range / max_range (m): a point whose range in its own scan
-    lies outside [min_range, max_range] is left out, 0 <= min_range < max_range, max_range may be inf."""
+    does not grow by itself: points that find no slot are counted as dropped; WorldMap.rebuild moves a map into a larger one);
+    min_range / max_range (m): a point whose range in its own scan lies outside [min_range, max_range] is left out, 0 <= min_range <
+    max_range, max_range may be inf."""
     __slots__ = ("voxel", "log2_capacity", "min_range", "max_range")
 
     def __init__(self, voxel=0.5, log2_capacity=22, min_range=0.0, max_range=math.inf):
@@ -236,6 +238,31 @@ class MapFit(_Frozen):
         if gate > spec.voxel:
             raise ValueError("the gate (%r) may not exceed the map's voxel (%r)" % (gate, spec.voxel))
         return gate
+
+
+class MapWindow(_Frozen):
+    """MapWindow(radius, every=10, min_count=1): the world map as a LOCAL map that follows the vehicle -- after every `every`-th scan
+    the table is rebuilt into a second one (elo_map_merge, include/elo.h; world_map.WorldMap(window=)) and only the voxels whose
+    centre lies within `radius` of that scan's position on all three axes (a box), and that hold at least `min_count` points, are
+    carried over.  Frozen and hashable.
+    radius (m): finite and > 0; every: an integer >= 1; min_count: an integer >= 1."""
+    __slots__ = ("radius", "every", "min_count")
+
+    def __init__(self, radius, every=10, min_count=1):
+        for name, value in (("every", every), ("min_count", min_count)):
+            if isinstance(value, bool) or not hasattr(value, "__index__"):
+                raise ValueError("%s is an integer (got %r)" % (name, value))
+            if value.__index__() < 1 or value.__index__() >= 2 ** 63:
+                raise ValueError("%s is >= 1 (got %d)" % (name, value.__index__()))
+        if isinstance(radius, bool):
+            raise ValueError("radius is a length in metres (got %r)" % (radius,))
+        radius = float(radius)
+        if not (math.isfinite(radius) and radius > 0):
+            raise ValueError("radius must be positive and finite (got %r)" % (radius,))
+        self._freeze(radius, every.__index__(), min_count.__index__())
+
+    def __repr__(self):
+        return "MapWindow(radius=%r, every=%r, min_count=%r)" % self._key()
 
 
 def resolve(sensor):

@@ -11,6 +11,14 @@
     wmap.add(xyz1, pose7)                      # the map as it stands (elo_map_fit), and the scan goes in at the fitted pose
     res = wmap.fit(xyz, pose64)                # the raw fit of scans against this map: localising in a map built earlier
 
+    wmap = WorldMap(VoxelMap(voxel=0.5), fit=MapFit(iters=2), window=MapWindow(radius=80.0, every=10))     # a LOCAL map: after
+    wmap.add(xyz1, pose7)                      # every 10th scan the table is rebuilt into a second one (elo_map_merge) and what
+    wmap.window_stats()                        # lies beyond 80 m of that scan, per axis, stays behind
+    wmap.rebuild(log2_capacity=24)             # GROWTH: the content moves into a larger table
+    wmap.merge(other)                          # the UNION: integer sums, so exactly the map of both drives' points
+    wmap.save_state("04_map_state.npz")        # keys and integer sums, the world pose, the totals: WorldMap.load_state(path)
+                                               # continues the drive as if the process had never ended
+
 DIRECTION.  A sample's pose carries frame 1 = scan n into frame 2 = scan n-1 (kitti.load_pair; local_model), so the running
 product W_n = T_0 o T_1 o ... o T_n carries scan n into the frame sample 0's pose leads to: what evaluate.pose_rows forms, with Tr
 the identity.  Scan n is inserted at W_n.
@@ -23,7 +31,7 @@ import torch
 
 from . import _ops
 from .local_model import _qmul
-from .sensor import MapFit, VoxelMap
+from .sensor import MapFit, MapWindow, VoxelMap
 
 
 def compose(world64, pose7):
@@ -44,31 +52,39 @@ def compose(world64, pose7):
 
 
 class WorldMap:
-    """WorldMap(spec, device="cuda:0", fit=None): one voxel map and the running world pose of the drive that fills it.
+    """WorldMap(spec, device="cuda:0", fit=None, window=None): one voxel map and the running world pose of the drive that fills it.
     spec: sensor.VoxelMap.  State, all on the device: `keys` (C,) int64 -- the table's unsigned 64-bit words; an empty slot, all ones,
     reads -1 --, `acc` (C,4) int64 {count, sx, sy, sz}, `stat_words` (8,) int64, and `world64` (7) float64 [q | t], the pose of the
     last scan added -> world (the identity after reset()).  insert() and add() enqueue launches and device-side float64 operators
     only: the host never waits for the device.
     fit: a sensor.MapFit -- add() then holds the running pose to the map: each scan's composed pose is the guess of a fit against
     the map as it stands, the scan is inserted at the fitted pose and `world64` becomes that pose.  A flagged scan (the first one,
-    against an empty map; a starved one) goes in at its guess.  `last_fit`: the _ops.MapFitResult rows of the last add()."""
+    against an empty map; a starved one) goes in at its guess.  `last_fit`: the _ops.MapFitResult rows of the last add().
+    window: a sensor.MapWindow -- after every `every`-th scan added since reset() (a HOST count: no device value is read) the map
+    is rebuilt about the translation of that scan's world pose: rebuild().  `keys`, `acc` -- and `spec`, where a rebuild changed
+    the capacity -- are REBOUND by a rebuild: take them from the map after it, do not hold on to them."""
 
     STATS = ("inserted", "filtered", "rejected", "dropped_full", "occupied")
 
-    def __init__(self, spec, device="cuda:0", fit=None):
+    def __init__(self, spec, device="cuda:0", fit=None, window=None):
         if not isinstance(spec, VoxelMap):
             raise TypeError("spec is a VoxelMap (got %r)" % (type(spec).__name__,))
         if fit is not None:
             if not isinstance(fit, MapFit):
                 raise TypeError("fit is a MapFit or None (got %r)" % (type(fit).__name__,))
             fit.gate_for(spec)                               # a gate beyond the voxel is refused here, not at the first scan
-        self.spec, self.device, self.tracking = spec, torch.device(device), fit
+        if window is not None and not isinstance(window, MapWindow):
+            raise TypeError("window is a MapWindow or None (got %r)" % (type(window).__name__,))
+        self.spec, self.device, self.tracking, self.window = spec, torch.device(device), fit, window
         self.last_fit, self._rows, self._log = None, [], []
         C = spec.capacity
         self.keys = torch.empty((C,), dtype=torch.int64, device=self.device)
         self.acc = torch.empty((C, 4), dtype=torch.int64, device=self.device)
         self.stat_words = torch.empty((8,), dtype=torch.int64, device=self.device)
         self.world64 = torch.empty((7,), dtype=torch.float64, device=self.device)
+        self.window_words = torch.empty((8,), dtype=torch.int64, device=self.device)     # the reports of every rebuild, summed
+        self._fresh_stats = torch.empty((8,), dtype=torch.int64, device=self.device)     # a rebuilt table's own stats
+        self._spare = None                                   # the other (keys, acc) of this capacity: rebuilds alternate
         self.reset()
 
     def reset(self):
@@ -78,7 +94,9 @@ class WorldMap:
         self.stat_words.zero_()
         self.world64.zero_()
         self.world64[0].fill_(1.0)
+        self.window_words.zero_()
         self.last_fit, self._rows, self._log = None, [], []
+        self._scans = self._rebuilds = 0                     # scans added / rebuilds made since reset(): the host's counts
 
     def insert(self, xyz, pose64):
         """The raw insert: range images xyz (n,H,W,3) float32 at the poses pose64 (n,7) float64 [q | t], scan -> world.  The running
@@ -120,18 +138,27 @@ class WorldMap:
         if n == 0:
             return
         rows, world = [], self.world64
+        every = self.window.every if self.window is not None else 0
         if self.tracking is None:
             for j in range(n):
                 world = compose(world, pose7[j])
                 rows.append(world)
             rows = torch.stack(rows).contiguous()
-            self.insert(xyz, rows)
+            # the one insert launch, split after every scan a rebuild is due at: the content is that of the scans taken one at a time
+            cuts = [j + 1 for j in range(n) if every and (self._scans + j + 1) % every == 0]
+            ends = cuts if cuts and cuts[-1] == n else cuts + [n]
+            for a, b in zip([0] + ends, ends):
+                self.insert(xyz[a:b], rows[a:b])
+                if b in cuts:
+                    self._rebuild_about(rows[b - 1, 4:])
         else:
             fits = []
             for j in range(n):
                 guess = compose(world, pose7[j]).reshape(1, 7).contiguous()
                 res = self.fit(xyz[j:j + 1], guess)
                 self.insert(xyz[j:j + 1], res.pose)
+                if every and (self._scans + j + 1) % every == 0:
+                    self._rebuild_about(res.pose[0, 4:])
                 world = res.pose[0]
                 fits.append(res)
                 rows.append(res.pose)
@@ -141,10 +168,116 @@ class WorldMap:
                                                                             for name in ("info", "grad", "stats")))
         self._rows.append(rows)
         self.world64.copy_(world)
+        self._scans += n
+
+    def merge(self, other, centre=None, radius=None, min_count=1):
+        """Add the voxels of `other` -- a WorldMap of the same voxel (ValueError otherwise; its capacity may differ), or a (key, acc)
+        pair of int64 tensors: (m,) keys and (m,4) {count, sx, sy, sz} rows, those of state() for one -- into this map: the UNION.
+        The sums are integers, so the result is exactly the map of both maps' points.  centre (3 float64 on the device, read when
+        the launch runs), radius, min_count: the filter of _ops.map_merge.  `inserted` grows by the points merged, `dropped_full` by
+        those that found no slot, and a WorldMap's own `filtered`, `rejected` and `dropped_full` totals are added to this map's:
+        the totals of both drives.  Returns the report, (8,) int64 on the device (_lib.MAP_REPORT); `other` is only read."""
+        if isinstance(other, WorldMap):
+            if other.spec.voxel != self.spec.voxel:
+                raise ValueError("the maps' voxels differ (%r, %r): their keys do not mean the same places" % (self.spec.voxel, other.spec.voxel))
+            key, acc = other.keys, other.acc
+        else:
+            try:
+                key, acc = other
+            except (TypeError, ValueError):
+                raise TypeError("other is a WorldMap or a (key, acc) pair of int64 tensors (got %r)" % (type(other).__name__,)) from None
+        report = _ops.map_merge(self.keys, self.acc, self.stat_words, key, acc, self.spec, centre, radius, min_count)
+        if isinstance(other, WorldMap):
+            self.stat_words[1:4] += other.stat_words[1:4].to(self.device)
+        return report
+
+    def rebuild(self, log2_capacity=None, centre=None, radius=None, min_count=1):
+        """The map moved into a FRESH table of the same or a new capacity (log2_capacity; `spec` is then replaced by the VoxelMap of
+        that capacity), filled on the device, under the filter of _ops.map_merge: GROWTH (a larger table, no filter) and EVICTION
+        (a window about `centre`, a least count) are both this.  `keys` and `acc` are rebound; the two buffer sets of one capacity are
+        kept and alternate, so a windowed drive allocates nothing after its first rebuild.  `inserted`, `filtered`, `rejected` and
+        `dropped_full` stay the drive's running totals, `occupied` becomes the new table's; what the rebuild left behind is summed
+        into window_stats().  Enqueued on the current stream; the host never waits.  Returns the report."""
+        spec = self.spec
+        if log2_capacity is not None and log2_capacity != spec.log2_capacity:
+            spec = VoxelMap(spec.voxel, log2_capacity, spec.min_range, spec.max_range)
+        if self._spare is not None and self._spare[0].shape[0] == spec.capacity:
+            keys, acc = self._spare
+        else:
+            keys = torch.empty((spec.capacity,), dtype=torch.int64, device=self.device)
+            acc = torch.empty((spec.capacity, 4), dtype=torch.int64, device=self.device)
+        keys.fill_(-1)
+        acc.zero_()
+        self._fresh_stats.zero_()
+        report = _ops.map_merge(keys, acc, self._fresh_stats, self.keys, self.acc, spec, centre, radius, min_count)
+        self.stat_words[4].copy_(self._fresh_stats[4])
+        self.window_words += report
+        self._spare = (self.keys, self.acc) if spec.capacity == self.spec.capacity else None
+        self.keys, self.acc, self.spec = keys, acc, spec
+        self._rebuilds += 1
+        return report
+
+    def _rebuild_about(self, centre):
+        return self.rebuild(centre=centre, radius=self.window.radius, min_count=self.window.min_count)
 
     def stats(self):
-        """{inserted, filtered, rejected, dropped_full, occupied} as python ints (synchronises)."""
+        """{inserted, filtered, rejected, dropped_full, occupied} as python ints (synchronises).  The first four are running totals
+        of the drive; `occupied` is the table's present occupancy (a rebuild may lower it)."""
         return dict(zip(self.STATS, (int(v) for v in self.stat_words[:5].cpu())))
+
+    def window_stats(self):
+        """{rebuilds, evicted_voxels, evicted_points, dropped_voxels, dropped_points} as python ints (synchronises): the rebuilds
+        since reset() and what they left behind -- filtered by the window or the least count (evicted), or without a slot in the
+        new table (dropped).  The counts in the table sum to inserted - evicted_points - dropped_points."""
+        w = [int(v) for v in self.window_words.cpu()]
+        return {"rebuilds": self._rebuilds, "evicted_voxels": w[1], "evicted_points": w[5], "dropped_voxels": w[3], "dropped_points": w[6]}
+
+    def state(self):
+        """Everything a later process needs to go on with this map, as numpy arrays and python numbers (synchronises): `key` (m,)
+        int64 SORTED and `acc` (m,4) int64 {count, sx, sy, sz} -- the integers themselves, not centroids --, `world64` (7,), the five
+        stats() by name, `voxel`, `min_range`, `max_range`, `log2_capacity`, and the window's counts: `scans`, `rebuilds`,
+        `window_words` (8,)."""
+        full = self.keys != -1
+        key, order = torch.sort(self.keys[full])
+        out = {"key": key.cpu().numpy(), "acc": self.acc[full][order].cpu().numpy(), "world64": self.world64.cpu().numpy()}
+        out.update(self.stats())
+        out.update(voxel=self.spec.voxel, min_range=self.spec.min_range, max_range=self.spec.max_range,
+                   log2_capacity=self.spec.log2_capacity, scans=self._scans, rebuilds=self._rebuilds,
+                   window_words=self.window_words.cpu().numpy())
+        return out
+
+    def save_state(self, path):
+        """Write state() with numpy.savez: arrays and numbers only, nothing a reader has to execute.  Returns the number of voxels.
+        (`path` as numpy.savez takes it: a name without .npz gets it appended.)"""
+        state = self.state()
+        np.savez(path, **state)
+        return len(state["key"])
+
+    @classmethod
+    def load_state(cls, path, device="cuda:0", log2_capacity=None, fit=None, window=None):
+        """The map of a save_state() file, in a table of the saved capacity or of `log2_capacity`: the rows are merged in
+        (elo_map_merge: a file is not trusted, malformed rows are refused -- ValueError), `world64`, the totals and the window's
+        counts are restored, and further add() calls continue the drive as if the process had never ended.  Synchronises."""
+        with np.load(path, allow_pickle=False) as f:
+            state = {name: f[name] for name in f.files}
+        log2 = int(state["log2_capacity"]) if log2_capacity is None else log2_capacity
+        wm = cls(VoxelMap(float(state["voxel"]), log2, float(state["min_range"]), float(state["max_range"])), device, fit=fit, window=window)
+        key = torch.from_numpy(np.ascontiguousarray(state["key"], dtype=np.int64)).to(wm.device)
+        acc = torch.from_numpy(np.ascontiguousarray(state["acc"], dtype=np.int64)).to(wm.device)
+        report = _ops.map_merge(wm.keys, wm.acc, wm._fresh_stats.zero_(), key, acc, wm.spec)
+        words = [int(state[name]) for name in cls.STATS[:4]]
+        wm.stat_words[:4].copy_(torch.tensor(words, dtype=torch.int64))
+        wm.stat_words[4].copy_(wm._fresh_stats[4])
+        wm.window_words.copy_(torch.from_numpy(np.ascontiguousarray(state["window_words"], dtype=np.int64)))
+        wm.world64.copy_(torch.from_numpy(np.ascontiguousarray(state["world64"], dtype=np.float64)))
+        wm._scans, wm._rebuilds = int(state["scans"]), int(state["rebuilds"])
+        r = [int(v) for v in report.cpu()]
+        if r[2]:
+            raise ValueError("%s holds %d malformed rows (a key with its top bit set, a count of 0 or beyond 2^40, a sum beyond "
+                             "65535 * count)" % (path, r[2]))
+        wm.window_words[3] += r[3]                           # rows a smaller table had no slot for: not in it, and counted so
+        wm.window_words[6] += r[6]
+        return wm
 
     def points(self):
         """(xyz (m,3) float32 centroids, count (m) int64, key (m) int64), one row per occupied voxel, SORTED BY KEY (torch.sort, on the

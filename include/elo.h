@@ -795,6 +795,36 @@ int elo_model_advance(const elo_model_advance_args *a, elo_stream_t stream);
  *     c = ((double)i + ((double)s / (double)count + 0.5) / 65536.0) * (double)voxel,   i = the key's field - 2^20,
  *   rounded to float32 once.  Two launches; capturable.  ELO_ERR_ARG: a NULL pointer, max_out < 0, a bad voxel or log2_capacity,
  *   keys / acc / cursor / out_key / out_count not 8-byte aligned.
+ * elo_map_merge, ONE launch: source ROWS (key, {count, sx, sy, sz}) from anywhere -- the keys / acc of another table, rows = its C,
+ *   or the m rows of a saved state -- filtered and added into the destination table.  A sliding window (rebuild into a second
+ *   table under a box about the vehicle), growth (rebuild into a larger table), loading a state and joining two maps are all this.
+ *   The source's keys are taken to mean the destination's voxel.  ONE SOURCE ROW with key k and count n, in this order:
+ *   empty      k all ones: skipped, counts nowhere;
+ *   malformed  k's top bit set, n == 0, n >= 2^40, or a sum above 65535 * n -> `voxels_rejected`: no division by zero and no
+ *              overflowing sum can enter a table from rows that are not trusted;
+ *   min_count  n < min_count -> filtered.  The SOURCE ROW's count, not the destination's total;
+ *   window     with centre (3 device doubles, read when the launch RUNS): per axis c = ((double)i + 0.5) * (double)voxel, i = the
+ *              key's field - 2^20, d = fabs(c - centre[axis]); the row is kept where d <= (double)radius on all three axes (a BOX;
+ *              a voxel whose centre lies exactly at the radius is kept), else filtered.  A NaN centre keeps nothing.  Every step is
+ *              one IEEE operation in double;
+ *   add        elo_map_insert's home slot, probing and atomicCAS claim -- the same device function --; the found slot gets count +=
+ *              n, sx += sx, sy += sy, sz += sz.  No slot within ELO_MAP_MAX_PROBE -> dropped, nothing touched.
+ *   report, eight words the launch ADDS to (the caller zeroes them): {voxels_merged, voxels_filtered, voxels_rejected,
+ *   voxels_dropped, points_merged, points_filtered, points_dropped, claimed}, points being the rows' counts; summed per wave, one add
+ *   per wave and counter.  The destination's stats get inserted += points_merged, dropped_full += points_dropped, occupied +=
+ *   claimed: the sum of all counts of a table stays equal to its `inserted`.  Filtered and rejected rows were never offered to the
+ *   table and do not touch its stats.  A key may stand in several source rows (concatenated states): the result is that of one add
+ *   per row.
+ *   DETERMINED as for the insert: with nothing dropped, the destination's content, its stats and the report are a function of the
+ *   multiset of rows merged and of what the table held before -- not of row order, split into launches, launch order or races;
+ *   an eager run and a graph replay agree bit for bit in content.  PLACEMENT is not determined.  With rows dropped, which ones
+ *   depends on the races; what is stored is still consistent.
+ *   The grid is a fixed function of rows (not of alignment: the keys are taken by 16-byte loads where src_keys is 16-byte aligned,
+ *   one word at a time otherwise; likewise the acc rows, which are read for occupied rows only).  Static trip bounds, nothing
+ *   waits on another thread, integer atomics only; no host synchronisation; capturable.
+ *   ELO_ERR_ARG (nothing is launched): a NULL pointer other than centre, rows < 0 or >= 2^31, a bad voxel or log2_capacity,
+ *   min_count < 1, with a centre a radius that is not positive and finite, a pointer that is not 8-byte aligned, a source range
+ *   ([rows] keys, [rows][4] acc) that overlaps the destination's keys or acc.  rows == 0 launches nothing and is ELO_OK.
  * LIFETIME as elo_model_render's.  Additive to ABI 26: no existing struct changes. */
 #define ELO_MAP_MAX_PROBE 128
 #define ELO_MAP_MIN_LOG2 10
@@ -822,6 +852,21 @@ typedef struct elo_map_extract_args {
     unsigned long long *cursor;   /* one word OUT: the number of occupied slots */
 } elo_map_extract_args;
 int elo_map_extract(const elo_map_extract_args *a, elo_stream_t stream);
+typedef struct elo_map_merge_args {
+    long rows;                    /* source rows, >= 0: ANY number (a table's C, or a saved state's m) */
+    const unsigned long long *src_keys;  /* [rows]; all ones = an empty slot: skipped, counts nowhere */
+    const unsigned long long *src_acc;   /* [rows][4] {count, sx, sy, sz} */
+    float voxel;                  /* the DESTINATION table's; the source's keys are taken to mean the same voxel */
+    int log2_capacity;
+    unsigned long long *keys;     /* [C] IN/OUT: the destination, as elo_map_insert_args */
+    unsigned long long *acc;      /* [C][4] IN/OUT */
+    unsigned long long *stats;    /* [8] IN/OUT */
+    const double *centre;         /* NULL: no window.  Else 3 device doubles, read when the launch RUNS */
+    float radius;                 /* with centre: finite, > 0 (m) */
+    long long min_count;          /* >= 1 */
+    unsigned long long *report;   /* [8] device words, ADDED to (the caller zeroes them) */
+} elo_map_merge_args;
+int elo_map_merge(const elo_map_merge_args *a, elo_stream_t stream);
 
 /* SCAN-TO-MAP REGISTRATION (csrc/elo_mapfit.hip): the point-to-plane fit of a scan's WORLD pose against the voxel map above -- every
  * cell of a range image carried by the scan -> world pose, matched to the nearest voxel centroid of the map, and -- on request -- a
