@@ -172,6 +172,13 @@ MapFitArgs = _struct("elo_map_fit_args", [
     ("batch", _i), ("H", _i), ("W", _i), ("voxel", _f), ("log2_capacity", _i), ("keys", _vp), ("acc", _vp), ("xyz", _vp),
     ("pose_in", _vp), ("iters", _i), ("gate", _f), ("huber", _f), ("jump_rel", _f), ("min_count", _i), ("damping", _f),
     ("min_points", _i), ("pose_out", _vp), ("info", _vp), ("grad", _vp), ("stats", _vp), ("match", _vp), ("scratch", _vp)])
+PLACE_MAX_RINGS, PLACE_MAX_SECTORS, PLACE_LEVELS, PLACE_MAX_K = 32, 128, 4095, 8      # ELO_PLACE_*
+ScanDescriptorArgs = _struct("elo_scan_descriptor_args", [
+    ("batch", _i), ("H", _i), ("W", _i), ("rings", _i), ("sectors", _i), ("z_min", ctypes.c_double), ("z_step", ctypes.c_double),
+    ("min_range2", ctypes.c_double), ("edge2", ctypes.c_double * (PLACE_MAX_RINGS + 1)), ("xyz", _vp), ("desc", _vp)])
+DescriptorSearchArgs = _struct("elo_descriptor_search_args", [
+    ("n", _i), ("m", _i), ("rings", _i), ("sectors", _i), ("k", _i), ("query", _vp), ("db", _vp), ("entry", _vp), ("shift", _vp),
+    ("dist", _vp), ("best_shift", _vp), ("best_dist", _vp)])
 
 # backward passes (csrc/elo_backward.hip)
 GroupConcatBwdArgs = _struct("elo_group_concat_bwd_args", [
@@ -306,6 +313,8 @@ SYMBOLS = [
     ("elo_map_fit", ctypes.c_int, [ctypes.POINTER(MapFitArgs), _vp]),
     ("elo_map_fit_scratch_words", ctypes.c_long, [ctypes.c_int] * 3),
     ("elo_map_fit_parts", ctypes.c_int, [ctypes.c_int] * 2),
+    ("elo_scan_descriptor", ctypes.c_int, [ctypes.POINTER(ScanDescriptorArgs), _vp]),
+    ("elo_descriptor_search", ctypes.c_int, [ctypes.POINTER(DescriptorSearchArgs), _vp]),
     ("elo_group_concat_backward", ctypes.c_int, [ctypes.POINTER(GroupConcatBwdArgs), _vp]),
     ("elo_masked_maxpool_backward", ctypes.c_int, [ctypes.POINTER(MaskedMaxpoolBwdArgs), _vp]),
     ("elo_cv_encode1_backward", ctypes.c_int, [ctypes.POINTER(CvEncode1BwdArgs), _vp]),

@@ -1076,6 +1076,90 @@ def map_fit(keys, acc, xyz, pose64, spec, fit, match=False):
     return res
 
 
+def _check_context(spec):
+    if not isinstance(spec, _sensor.ScanContext):
+        raise TypeError("spec is a ScanContext (got %r)" % (type(spec).__name__,))
+
+
+def _check_descriptors(name, t, spec):
+    _check_tensors(((name, t, torch.uint16),))
+    if t.dim() != 3 or tuple(t.shape[1:]) != (spec.sectors, spec.rings):
+        raise L.EloError("%s is (rows, %d, %d): sectors by rings, sector-major (got %s)" % (name, spec.sectors, spec.rings, tuple(t.shape)))
+
+
+def scan_descriptor(xyz, spec, out=None):
+    """elo_scan_descriptor: the range images xyz (n,H,W,3) float32, W >= spec.sectors -> their descriptors (n, sectors, rings)
+    uint16 (spec: sensor.ScanContext), written into `out` where one is given.  One launch on the current stream, no host
+    synchronisation, capturable; inputs are contiguous and used in place.  Bad types, shapes, layouts or devices are refused here,
+    before the library is touched."""
+    _check_context(spec)
+    _check_tensors((("xyz", xyz, torch.float32),))
+    if xyz.dim() != 4 or xyz.shape[-1] != 3:
+        raise L.EloError("xyz is (n,H,W,3): one range image per scan (got %s)" % (tuple(xyz.shape),))
+    n, H, W, _ = xyz.shape
+    if H < 1 or W < spec.sectors:
+        raise L.EloError("a sector needs a column: H >= 1, W >= sectors = %d (got %d x %d)" % (spec.sectors, H, W))
+    if n * H * W >= 2 ** 31 or n > 65535:
+        raise L.EloError("n*H*W stays below 2^31 and n below 65536 (got n, H, W = %d, %d, %d)" % (n, H, W))
+    if out is not None:
+        _check_descriptors("out", out, spec)
+        if out.shape[0] != n:
+            raise L.EloError("out holds one descriptor per image: (%d, %d, %d) (got %s)" % (n, spec.sectors, spec.rings, tuple(out.shape)))
+        if out.device != xyz.device:
+            raise L.EloError("the images and the descriptors live on one device")
+    L.require_gpu(xyz, out)
+    if out is None:
+        out = torch.empty((n, spec.sectors, spec.rings), dtype=torch.uint16, device=xyz.device)
+    if n == 0:
+        return out
+    edge2 = (ctypes.c_double * (L.PLACE_MAX_RINGS + 1))(*spec.edge2())
+    a = L.ScanDescriptorArgs(n, H, W, spec.rings, spec.sectors, spec.z_min, spec.z_step, spec.min_range * spec.min_range, edge2,
+                             xyz.data_ptr(), out.data_ptr())
+    L.call("elo_scan_descriptor", a, xyz)
+    return out
+
+
+class PlaceSearchResult:
+    """What elo_descriptor_search wrote for n queries: `entry` (n,k) int32, `shift` (n,k) int32, `dist` (n,k) float64 -- the k
+    nearest entries by (dist, entry), padded with -1, -1, +inf beyond the entries searched -- and the profile they are taken
+    from, `best_shift` (n,m) int32 and `best_dist` (n,m) float64: every entry's best shift and its distance."""
+    __slots__ = ("entry", "shift", "dist", "best_shift", "best_dist")
+
+    def __init__(self, entry, shift, dist, best_shift, best_dist):
+        self.entry, self.shift, self.dist, self.best_shift, self.best_dist = entry, shift, dist, best_shift, best_dist
+
+
+def descriptor_search(query, db, m, spec, k=1):
+    """elo_descriptor_search: the descriptors query (n, sectors, rings) against the entries [0, m) of db (cap, sectors, rings), both
+    uint16 (spec: sensor.ScanContext), over every entry and every column shift -> PlaceSearchResult.  m: a python integer in 0 ..
+    cap (the caller counts its entries on the host); k: 1 .. 8.  Two launches on the current stream (one where m == 0), no host
+    synchronisation, capturable.  Bad types, shapes, layouts, devices, m or k are refused here, before the library is touched."""
+    _check_context(spec)
+    _check_descriptors("query", query, spec)
+    _check_descriptors("db", db, spec)
+    if query.device != db.device:
+        raise L.EloError("the queries and the database live on one device")
+    if isinstance(m, bool) or not hasattr(m, "__index__") or not 0 <= m.__index__() <= db.shape[0] or m.__index__() >= 2 ** 31:
+        raise L.EloError("m is an integer in 0 .. %d, the rows db holds (got %r)" % (db.shape[0], m))
+    if isinstance(k, bool) or not hasattr(k, "__index__") or not 1 <= k.__index__() <= L.PLACE_MAX_K:
+        raise L.EloError("k is an integer in 1 .. %d (got %r)" % (L.PLACE_MAX_K, k))
+    m, k, n = m.__index__(), k.__index__(), query.shape[0]
+    if n > 65535:
+        raise L.EloError("n stays below 65536 (got %d)" % n)
+    L.require_gpu(query, db)
+    dev = query.device
+    res = PlaceSearchResult(torch.empty((n, k), dtype=torch.int32, device=dev), torch.empty((n, k), dtype=torch.int32, device=dev),
+                            torch.empty((n, k), dtype=torch.float64, device=dev), torch.empty((n, m), dtype=torch.int32, device=dev),
+                            torch.empty((n, m), dtype=torch.float64, device=dev))
+    if n == 0:
+        return res
+    a = L.DescriptorSearchArgs(n, m, spec.rings, spec.sectors, k, query.data_ptr(), db.data_ptr() if m else query.data_ptr(),
+                               res.entry.data_ptr(), res.shift.data_ptr(), res.dist.data_ptr(), res.best_shift.data_ptr() if m else None,
+                               res.best_dist.data_ptr() if m else None)
+    L.call("elo_descriptor_search", a, query)
+    return res
+
+
 class _WarpProject(torch.autograd.Function):
     """elo_warp_project / elo_warp_project_backward.  The forward's scratch (who won each cell) is kept for the backward."""
 

@@ -39,13 +39,13 @@ enum { MAP_NONE = 0, MAP_FILTERED = 1, MAP_REJECTED = 2, MAP_POINT = 3 };
 __device__ __forceinline__ int map_point(const MapInsert &a, const double (&R)[9], const double (&t)[3], float ax, float ay, float az,
                                          unsigned long long &key, unsigned (&g)[3])
 {
-    if (ax == 0.0f && ay == 0.0f && az == 0.0f) return MAP_NONE;
+    if (map_cell_empty(ax, ay, az)) return MAP_NONE;
     const float rf = sqrtf(ax * ax + ay * ay + az * az);
     if (rf < a.min_range || rf > a.max_range) return MAP_FILTERED;
     const float x = (float)(R[0] * ax + R[1] * ay + R[2] * az + t[0]);
     const float y = (float)(R[3] * ax + R[4] * ay + R[5] * az + t[1]);
     const float z = (float)(R[6] * ax + R[7] * ay + R[8] * az + t[2]);
-    if (x - x != 0.0f || y - y != 0.0f || z - z != 0.0f) return MAP_REJECTED;
+    if (!map_point_finite(x, y, z)) return MAP_REJECTED;
     const double voxel = (double)a.voxel;
     unsigned long long fx, fy, fz;
     if (!map_axis(x, voxel, fx, g[0]) || !map_axis(y, voxel, fy, g[1]) || !map_axis(z, voxel, fz, g[2])) return MAP_REJECTED;

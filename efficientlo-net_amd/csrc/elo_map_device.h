@@ -24,6 +24,11 @@ __device__ __forceinline__ bool map_pose(const double *row, double (&R)[9], doub
     return true;
 }
 
+// the validity rule of a cell, in its two halves: a cell that is exactly (0,0,0) holds no point, and a point with a non-finite
+// component (the insert looks at the carried, rounded p') is rejected.  elo_place.hip applies both to the cell as it stands.
+__device__ __forceinline__ bool map_cell_empty(float x, float y, float z) { return x == 0.0f && y == 0.0f && z == 0.0f; }
+__device__ __forceinline__ bool map_point_finite(float x, float y, float z) { return !(x - x != 0.0f || y - y != 0.0f || z - z != 0.0f); }
+
 // one axis of the rounded p': its 21-bit field of the key and its offset inside the voxel; false: the index is out of range
 __device__ __forceinline__ bool map_axis(float c, double voxel, unsigned long long &field, unsigned &g)
 {

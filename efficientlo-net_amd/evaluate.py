@@ -253,14 +253,19 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
     before the scan goes in (WorldMap(fit=)).  What predict_sequence returns does not change; `<out_dir>/<seq>_map_poses.txt`, beside
     the map, holds one row per sample: the world pose q t the scan was inserted at, then count, rms and status of its fit.
     `map_window=MapWindow(...)` with `world_map=VoxelMap(...)`: the map follows the vehicle (WorldMap(window=)).  With a map,
-    `<out_dir>/<seq>_map_state.npz` holds its state (WorldMap.save_state): WorldMap.load_state continues from it."""
+    `<out_dir>/<seq>_map_state.npz` holds its state (WorldMap.save_state): WorldMap.load_state continues from it.
+    `places=Places(...)` with `world_map=VoxelMap(...)`: the map keeps an index of scan descriptors and looks every few scans up in
+    it (WorldMap(places=)); `<out_dir>/<seq>_revisits.txt` holds one row per lookup: scan, entry, entry_scan, shift, dist."""
     wmap, map_fit, map_window = kw.get("world_map"), kw.pop("map_fit", None), kw.pop("map_window", None)
+    places = kw.pop("places", None)
+    if places is not None and not isinstance(wmap, VoxelMap):
+        raise ValueError("places= builds the map with its index itself: pass world_map=VoxelMap(...) with it")
     if map_fit is not None and not isinstance(wmap, VoxelMap):
         raise ValueError("map_fit= builds the tracking map itself: pass world_map=VoxelMap(...) with it")
     if map_window is not None and not isinstance(wmap, VoxelMap):
         raise ValueError("map_window= builds the windowed map itself: pass world_map=VoxelMap(...) with it")
     if isinstance(wmap, VoxelMap):
-        wmap = kw["world_map"] = WorldMap(wmap, device=net.device, fit=map_fit, window=map_window)
+        wmap = kw["world_map"] = WorldMap(wmap, device=net.device, fit=map_fit, window=map_window, places=places)
     q, t, *fit_out = predict_sequence(net, root, seq, T_diff, **kw)
     Tr = kitti.read_calib(os.path.join(root, seq, "calib.txt"))["Tr"]
     rows = pose_rows(q, t, Tr)
@@ -276,6 +281,8 @@ def run_sequence(net, root, seq, T_diff, poses_gt=None, out_dir=None, **kw):
                 log = wmap.fit_log().cpu().numpy().astype(np.float64)
                 table = np.concatenate([wmap.trajectory().cpu().numpy(), log[:, (0, 2, 3)]], 1)
                 np.savetxt(os.path.join(out_dir, "%s_map_poses.txt" % seq), table, fmt="%.17g")
+            if places is not None:
+                np.savetxt(os.path.join(out_dir, "%s_revisits.txt" % seq), wmap.revisits().cpu().numpy(), fmt="%.17g")
     score = None
     if poses_gt is not None:
         score = kitti.overall(kitti.sequence_errors(np.asarray(poses_gt)[:len(rows)], rows))

@@ -18,7 +18,9 @@ one range image (elo_model_render; local_model.ModelTracker) instead of against 
 `VoxelMap` asks for the map the poses are for: every scan carried by its world pose into a hash table of voxels on the device
 (elo_map_insert; world_map.WorldMap).  `MapFit` asks for a scan's world pose to be fitted against that map before the scan goes
 in (elo_map_fit; WorldMap(fit=)).  `MapWindow` asks for that map to follow the vehicle: what lies beyond a radius is dropped at a
-rebuild every few scans (elo_map_merge; WorldMap(window=)).
+rebuild every few scans (elo_map_merge; WorldMap(window=)).  `ScanContext` is the descriptor of a scan for place recognition and
+`Places` asks the map to keep an index of them and to look every few scans up in it (elo_scan_descriptor / elo_descriptor_search;
+places.PlaceIndex; WorldMap(places=)).
 """
 import math
 
@@ -263,6 +265,81 @@ class MapWindow(_Frozen):
 
     def __repr__(self):
         return "MapWindow(radius=%r, every=%r, min_count=%r)" % self._key()
+
+
+class ScanContext(_Frozen):
+    """ScanContext(rings=20, sectors=60, max_range=KITTI_HDL64.crop_xy, min_range=0.0, z_min=-3.0, z_step=0.005): the descriptor of
+    a scan for place recognition -- `sectors` azimuth sectors by `rings` range rings, each bin holding the height of its highest
+    point as an integer level 1 .. 4095 (0: no point) (elo_scan_descriptor, include/elo.h; places.PlaceIndex).  Frozen and hashable.
+    rings: an integer in 1 .. 32; sectors: an integer in 1 .. 128; 0 <= min_range < max_range (m, in the xy plane), both finite;
+    z_min (m): the height of level 1, finite; z_step (m): the height of a level, finite and > 0."""
+    __slots__ = ("rings", "sectors", "max_range", "min_range", "z_min", "z_step")
+    LEVELS = 4095
+
+    def __init__(self, rings=20, sectors=60, max_range=KITTI_HDL64.crop_xy, min_range=0.0, z_min=-3.0, z_step=0.005):
+        for name, value, most in (("rings", rings, 32), ("sectors", sectors, 128)):
+            if isinstance(value, bool) or not hasattr(value, "__index__"):
+                raise ValueError("%s is an integer (got %r)" % (name, value))
+            if value.__index__() < 1 or value.__index__() > most:
+                raise ValueError("%s is 1 .. %d (got %d)" % (name, most, value.__index__()))
+        for name, value in (("max_range", max_range), ("min_range", min_range), ("z_min", z_min), ("z_step", z_step)):
+            if isinstance(value, bool):
+                raise ValueError("%s is a length in metres (got %r)" % (name, value))
+        max_range, min_range, z_min, z_step = float(max_range), float(min_range), float(z_min), float(z_step)
+        if not (math.isfinite(min_range) and min_range >= 0):
+            raise ValueError("min_range must be finite and >= 0 (got %r)" % (min_range,))
+        if not (math.isfinite(max_range) and max_range > min_range):
+            raise ValueError("max_range must be finite and lie above min_range (got %r, %r)" % (max_range, min_range))
+        if not math.isfinite(z_min):
+            raise ValueError("z_min must be finite (got %r)" % (z_min,))
+        if not (math.isfinite(z_step) and z_step > 0):
+            raise ValueError("z_step must be positive and finite (got %r)" % (z_step,))
+        self._freeze(rings.__index__(), sectors.__index__(), max_range, min_range, z_min, z_step)
+
+    def __repr__(self):
+        return "ScanContext(rings=%r, sectors=%r, max_range=%r, min_range=%r, z_min=%r, z_step=%r)" % self._key()
+
+    def edge2(self):
+        """The squared ring edges the kernel compares against, python doubles: edge2[j] = e_j * e_j, e_j = max_range * j / rings, for
+        j = 0 .. rings (include/elo.h: formed on the host, in double)."""
+        out = []
+        for j in range(self.rings + 1):
+            e = self.max_range * j / self.rings
+            out.append(e * e)
+        return tuple(out)
+
+    def yaw_of(self, shift):
+        """The rotation about the scan's z axis a column shift stands for, in radians in [-pi, pi): the query's heading relative to
+        the entry's.  A shift is shift * 2 pi / sectors of a turn, and its SIGN is negative: the columns of a range image run
+        against the azimuth (column w looks along pi - (w + 0.5) 2 pi / W), so a vehicle turned by +yaw sees the place in columns
+        moved UP by yaw, and the search pairs its column j with the entry's column j + shift = j - yaw sectors / 2 pi."""
+        shift = shift % self.sectors
+        if 2 * shift > self.sectors:
+            shift -= self.sectors
+        return -shift * (2.0 * math.pi / self.sectors) if shift else 0.0
+
+
+class Places(_Frozen):
+    """Places(context=ScanContext(), every=5, skip_recent=50, capacity=4096): the world map keeps an index of scan descriptors next
+    to their world poses and looks every `every`-th scan up in it before adding it (world_map.WorldMap(places=);
+    places.PlaceIndex).  Frozen and hashable.
+    context: a ScanContext; every: an integer >= 1; skip_recent: the newest entries a lookup leaves out (the scans just driven
+    through are no revisit), an integer >= 0; capacity: the entries the index holds, an integer >= 1."""
+    __slots__ = ("context", "every", "skip_recent", "capacity")
+
+    def __init__(self, context=None, every=5, skip_recent=50, capacity=4096):
+        context = ScanContext() if context is None else context
+        if not isinstance(context, ScanContext):
+            raise ValueError("context is a ScanContext (got %r)" % (type(context).__name__,))
+        for name, value, least in (("every", every, 1), ("skip_recent", skip_recent, 0), ("capacity", capacity, 1)):
+            if isinstance(value, bool) or not hasattr(value, "__index__"):
+                raise ValueError("%s is an integer (got %r)" % (name, value))
+            if value.__index__() < least or value.__index__() >= 2 ** 31:
+                raise ValueError("%s is %d .. 2^31 - 1 (got %d)" % (name, least, value.__index__()))
+        self._freeze(context, every.__index__(), skip_recent.__index__(), capacity.__index__())
+
+    def __repr__(self):
+        return "Places(context=%r, every=%r, skip_recent=%r, capacity=%r)" % self._key()
 
 
 def resolve(sensor):

@@ -19,6 +19,11 @@
     wmap.save_state("04_map_state.npz")        # keys and integer sums, the world pose, the totals: WorldMap.load_state(path)
                                                # continues the drive as if the process had never ended
 
+    wmap = WorldMap(VoxelMap(voxel=0.5), fit=MapFit(iters=2), places=Places())      # PLACES: every 5th scan's descriptor is looked
+    wmap.add(xyz1, pose7)                      # up among the earlier ones (elo_descriptor_search), then kept with its world pose
+    wmap.revisits()                            # (r,5) [scan, entry, entry_scan, shift, dist]: the caller reads dist
+    out = wmap.relocalise(xyz, k=4)            # a scan with NO pose guess: the k nearest places, each fitted against the map
+
 DIRECTION.  A sample's pose carries frame 1 = scan n into frame 2 = scan n-1 (kitti.load_pair; local_model), so the running
 product W_n = T_0 o T_1 o ... o T_n carries scan n into the frame sample 0's pose leads to: what evaluate.pose_rows forms, with Tr
 the identity.  Scan n is inserted at W_n.
@@ -31,7 +36,8 @@ import torch
 
 from . import _ops
 from .local_model import _qmul
-from .sensor import MapFit, MapWindow, VoxelMap
+from .places import PlaceIndex
+from .sensor import MapFit, MapWindow, Places, VoxelMap
 
 
 def compose(world64, pose7):
@@ -52,7 +58,7 @@ def compose(world64, pose7):
 
 
 class WorldMap:
-    """WorldMap(spec, device="cuda:0", fit=None, window=None): one voxel map and the running world pose of the drive that fills it.
+    """WorldMap(spec, device="cuda:0", fit=None, window=None, places=None): one voxel map and the running world pose of the drive that fills it.
     spec: sensor.VoxelMap.  State, all on the device: `keys` (C,) int64 -- the table's unsigned 64-bit words; an empty slot, all ones,
     reads -1 --, `acc` (C,4) int64 {count, sx, sy, sz}, `stat_words` (8,) int64, and `world64` (7) float64 [q | t], the pose of the
     last scan added -> world (the identity after reset()).  insert() and add() enqueue launches and device-side float64 operators
@@ -62,11 +68,15 @@ class WorldMap:
     against an empty map; a starved one) goes in at its guess.  `last_fit`: the _ops.MapFitResult rows of the last add().
     window: a sensor.MapWindow -- after every `every`-th scan added since reset() (a HOST count: no device value is read) the map
     is rebuilt about the translation of that scan's world pose: rebuild().  `keys`, `acc` -- and `spec`, where a rebuild changed
-    the capacity -- are REBOUND by a rebuild: take them from the map after it, do not hold on to them."""
+    the capacity -- are REBOUND by a rebuild: take them from the map after it, do not hold on to them.
+    places: a sensor.Places -- the map keeps a places.PlaceIndex (`places`): every `every`-th scan added since reset() (a HOST
+    count) is FIRST looked up in it, k = 1, the newest `skip_recent` entries left out, and THEN appended at the world pose it was
+    inserted at.  The lookups are revisits(); nothing is thresholded.  The index only reads the scans: the map's content and the
+    trajectory are those of the same drive without it."""
 
     STATS = ("inserted", "filtered", "rejected", "dropped_full", "occupied")
 
-    def __init__(self, spec, device="cuda:0", fit=None, window=None):
+    def __init__(self, spec, device="cuda:0", fit=None, window=None, places=None):
         if not isinstance(spec, VoxelMap):
             raise TypeError("spec is a VoxelMap (got %r)" % (type(spec).__name__,))
         if fit is not None:
@@ -75,7 +85,12 @@ class WorldMap:
             fit.gate_for(spec)                               # a gate beyond the voxel is refused here, not at the first scan
         if window is not None and not isinstance(window, MapWindow):
             raise TypeError("window is a MapWindow or None (got %r)" % (type(window).__name__,))
+        if places is not None and not isinstance(places, Places):
+            raise TypeError("places is a Places or None (got %r)" % (type(places).__name__,))
         self.spec, self.device, self.tracking, self.window = spec, torch.device(device), fit, window
+        self.place_spec = places
+        self.places = PlaceIndex(places.context, places.capacity, self.device) if places is not None else None
+        self._revisits = []
         self.last_fit, self._rows, self._log = None, [], []
         C = spec.capacity
         self.keys = torch.empty((C,), dtype=torch.int64, device=self.device)
@@ -95,7 +110,9 @@ class WorldMap:
         self.world64.zero_()
         self.world64[0].fill_(1.0)
         self.window_words.zero_()
-        self.last_fit, self._rows, self._log = None, [], []
+        self.last_fit, self._rows, self._log, self._revisits = None, [], [], []
+        if self.places is not None:
+            self.places.reset()
         self._scans = self._rebuilds = 0                     # scans added / rebuilds made since reset(): the host's counts
 
     def insert(self, xyz, pose64):
@@ -128,7 +145,9 @@ class WorldMap:
         """n consecutive samples: xyz (n,H,W,3) float32 range images (each sample's frame 1) and pose7 (n,7) their relative poses
         [q | t], frame 1 -> frame 2, any float dtype.  The poses are composed in order onto `world64` and scan j is inserted at the
         world pose AFTER its own pose; one insert launch for all n.  With a MapFit the scans are taken one at a time: compose, fit
-        against the map as it stands, insert at the fitted pose.  Everything is enqueued; the host never waits."""
+        against the map as it stands, insert at the fitted pose.  Everything is enqueued; the host never waits.  With Places the
+        scans due for a lookup are looked up and appended after that, by launches and device-side operators alone; where the index
+        has no room for all of them IndexError is raised BEFORE anything is enqueued and the map is as it was."""
         if not isinstance(xyz, torch.Tensor) or xyz.dim() != 4:
             raise ValueError("xyz is an (n,H,W,3) tensor of range images")
         pose7 = torch.as_tensor(pose7).to(device=self.device, dtype=torch.float64)
@@ -137,6 +156,10 @@ class WorldMap:
             raise ValueError("pose7 is one [q | t] row per image: (%d, 7) (got %s)" % (n, tuple(pose7.shape)))
         if n == 0:
             return
+        visits = [j for j in range(n) if (self._scans + j + 1) % self.place_spec.every == 0] if self.places is not None else []
+        if visits and len(self.places) + len(visits) > self.places.capacity:
+            raise IndexError("the place index is full: %d entries held, %d of these scans are due, capacity %d; nothing was added"
+                             % (len(self.places), len(visits), self.places.capacity))
         rows, world = [], self.world64
         every = self.window.every if self.window is not None else 0
         if self.tracking is None:
@@ -168,7 +191,56 @@ class WorldMap:
                                                                             for name in ("info", "grad", "stats")))
         self._rows.append(rows)
         self.world64.copy_(world)
+        for j in visits:
+            self._visit(xyz[j:j + 1], rows[j:j + 1], self._scans + j)
         self._scans += n
+
+    def _visit(self, xyz, pose64, scan):
+        """Look scan number `scan` (xyz (1,H,W,3), inserted at pose64 (1,7)) up in the index, log the row, append the scan.  Every
+        value stays a (1,) device tensor and the entry's scan number comes by a device-side gather (index_select): a 0-dim tensor
+        used as an index would be read on the host."""
+        match = self.places.query(xyz, k=1, skip_recent=self.place_spec.skip_recent)
+        entry, shift, dist = match.entry[0], match.shift[0], match.dist[0]                  # (1,) each
+        held = self.places.scan.index_select(0, entry.clamp(min=0).to(torch.int64))
+        entry_scan = torch.where(entry >= 0, held, torch.full_like(held, -1))
+        row = torch.cat([torch.full_like(dist, float(scan)), entry.to(torch.float64), entry_scan.to(torch.float64),
+                         shift.to(torch.float64), dist])
+        self._revisits.append(row.reshape(1, 5))
+        self.places.add(xyz, pose64, scan=[scan])
+
+    def revisits(self):
+        """(r,5) float64 on the device: [scan, entry, entry_scan, shift, dist] of every lookup since reset() -- the number of the
+        scan looked up (0-based, counted since reset()), the nearest entry of the index, the number of THAT entry's scan, its best
+        column shift and its distance; -1, -1, -1, +inf where the index had nothing to search yet.  Nothing is thresholded: whether
+        a row is a revisit is the caller's reading of `dist`."""
+        if not self._revisits:
+            return torch.empty((0, 5), dtype=torch.float64, device=self.device)
+        return torch.cat(self._revisits)
+
+    def relocalise(self, xyz, k=4, fit=None):
+        """One scan xyz (1,H,W,3) float32 with NO pose guess: the k nearest places of the index (PlaceIndex.query), a fit against
+        the map at each of their guesses -- the keyframe's world pose turned by the matched heading -- and the choice among them
+        -> {"match": the places.PlaceMatch, "fits": the _ops.MapFitResult of the k guesses (rows in rank order; padding rows are
+        fitted at the identity and count as flagged), "best": a python int}.  best: the candidate that is not flagged (status 0)
+        with the most terms, ties going to the better rank; -1 where every candidate is flagged.  SYNCHRONISES to choose (the k
+        status words and counts are read).  `fit`: a sensor.MapFit (None: the one this map was built with).
+        THE LIMIT.  A descriptor gives a place and a heading, not a translation: the guess stands at the keyframe's own position,
+        and the fit's basin is its gate, at most one voxel.  A scan taken further from its keyframe than about a voxel comes back
+        flagged or unmoved; it needs a coarser map first, which is not built here."""
+        if self.places is None:
+            raise ValueError("this map was built without Places: pass places=Places(...)")
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 4 or xyz.shape[0] != 1:
+            raise ValueError("xyz is one (1,H,W,3) range image")
+        match = self.places.query(xyz, k=k)
+        kk = match.entry.shape[1]
+        fits = self.fit(xyz.expand(kk, -1, -1, -1).contiguous(), match.pose[0].contiguous(), fit=fit)
+        # the one read: per candidate [found, status, count]
+        rows = torch.stack([(match.entry[0] >= 0).to(torch.float32), fits.stats[:, 3], fits.stats[:, 0]], 1).cpu().tolist()
+        best, most = -1, -1.0
+        for r, (found, status, count) in enumerate(rows):
+            if found and status == 0.0 and count > most:
+                best, most = r, count
+        return {"match": match, "fits": fits, "best": best}
 
     def merge(self, other, centre=None, radius=None, min_count=1):
         """Add the voxels of `other` -- a WorldMap of the same voxel (ValueError otherwise; its capacity may differ), or a (key, acc)
@@ -244,6 +316,9 @@ class WorldMap:
         out.update(voxel=self.spec.voxel, min_range=self.spec.min_range, max_range=self.spec.max_range,
                    log2_capacity=self.spec.log2_capacity, scans=self._scans, rebuilds=self._rebuilds,
                    window_words=self.window_words.cpu().numpy())
+        if self.places is not None:                          # (without Places the keys are exactly the ones above)
+            out.update(self.places.state())
+            out["place_revisits"] = self.revisits().cpu().numpy()
         return out
 
     def save_state(self, path):
@@ -254,14 +329,27 @@ class WorldMap:
         return len(state["key"])
 
     @classmethod
-    def load_state(cls, path, device="cuda:0", log2_capacity=None, fit=None, window=None):
+    def load_state(cls, path, device="cuda:0", log2_capacity=None, fit=None, window=None, places=None):
         """The map of a save_state() file, in a table of the saved capacity or of `log2_capacity`: the rows are merged in
         (elo_map_merge: a file is not trusted, malformed rows are refused -- ValueError), `world64`, the totals and the window's
-        counts are restored, and further add() calls continue the drive as if the process had never ended.  Synchronises."""
+        counts are restored, and further add() calls continue the drive as if the process had never ended.  Synchronises.
+        places: a sensor.Places -- the index and the revisit log the file carries are restored too (ValueError where it carries
+        none, where its descriptors are of another ScanContext, or where they are malformed: PlaceIndex.from_state)."""
         with np.load(path, allow_pickle=False) as f:
             state = {name: f[name] for name in f.files}
         log2 = int(state["log2_capacity"]) if log2_capacity is None else log2_capacity
         wm = cls(VoxelMap(float(state["voxel"]), log2, float(state["min_range"]), float(state["max_range"])), device, fit=fit, window=window)
+        if places is not None:
+            if not isinstance(places, Places):
+                raise TypeError("places is a Places or None (got %r)" % (type(places).__name__,))
+            index = PlaceIndex.from_state(state, places.capacity, wm.device)     # (the one index this map gets: none was built above)
+            if index.spec != places.context:
+                raise ValueError("%s holds descriptors of %r, not of %r" % (path, index.spec, places.context))
+            wm.place_spec, wm.places = places, index
+            log = np.asarray(state.get("place_revisits", np.zeros((0, 5))))
+            if log.dtype != np.float64 or log.ndim != 2 or log.shape[1] != 5:
+                raise ValueError("place_revisits is (r, 5) float64 (got %s %s)" % (log.shape, log.dtype))
+            wm._revisits = [torch.from_numpy(np.ascontiguousarray(log)).to(wm.device)] if len(log) else []
         key = torch.from_numpy(np.ascontiguousarray(state["key"], dtype=np.int64)).to(wm.device)
         acc = torch.from_numpy(np.ascontiguousarray(state["acc"], dtype=np.int64)).to(wm.device)
         report = _ops.map_merge(wm.keys, wm.acc, wm._fresh_stats.zero_(), key, acc, wm.spec)

@@ -952,6 +952,81 @@ long elo_map_fit_scratch_words(int batch, int H, int W);    /* < 0: sizes the en
 int elo_map_fit_parts(int H, int W);                        /* partial rows (workgroups) per image of an evaluation */
 int elo_map_fit(const elo_map_fit_args *a, elo_stream_t stream);
 
+/* PLACE RECOGNITION (csrc/elo_place.hip): a descriptor of a scan that does not depend on the vehicle's heading -- a grid of
+ * `sectors` azimuth sectors by `rings` range rings that holds, per bin, the height of its highest point as an INTEGER level -- and
+ * the search of a database of such descriptors over every entry and every column shift.  Integers throughout: the descriptor and
+ * every inner product of the search are exact, the distance is a fixed sequence of IEEE double operations.
+ * elo_scan_descriptor, ONE launch.  xyz: (batch,H,W,3) range images, W >= sectors.  desc: (batch,sectors,rings) unsigned 16-bit,
+ *   sector-major (one sector's rings are contiguous), written in full.  A stored level is 1 .. ELO_PLACE_LEVELS; 0 = no point.
+ * ONE CELL (h, w) with p = (x, y, z), in this order:
+ *   validity   elo_map_insert's rule for a cell at the identity pose, without its range gate: a cell that is exactly (0,0,0) is
+ *              empty, a cell with a non-finite component is left out (the same device functions, csrc/elo_map_device.h);
+ *   sector     (w * sectors) / W in integers: the columns of a sector are a contiguous run, of two lengths where sectors does not
+ *              divide W;
+ *   r2         (double)x * (double)x + (double)y * (double)y: both products are exact in double, the sum is ONE rounding;
+ *   ring       the number of j in 1 .. rings with edge2[j] <= r2 (a point exactly on an edge lies in the ring above it).  edge2[j]
+ *              = e_j * e_j with e_j = (double)max_range * j / rings is formed by the CALLER in double and passed in, so that the
+ *              kernel and a restatement compare against the same numbers; edge2[0] is not read;
+ *   range      r2 < min_range2 or r2 >= edge2[rings]: left out (min_range2 = min_range * min_range, the caller's, in double);
+ *   level      q = ((double)z - z_min) / z_step (a division), f = floor(q), clamped IN DOUBLE to [0, ELO_PLACE_LEVELS - 1];
+ *              level = (int)f + 1.  Both ends clamp; nothing is counted;
+ *   bin        desc[sector][ring] = the largest level of its points (an integer max: no order of arrival).
+ *   An image without points gives all zeros.  A workgroup owns one sector of one image: `rings` words of LDS, integer atomicMax on
+ *   them, `rings` plain stores; no global atomics, no scratch buffer.
+ * elo_descriptor_search, TWO launches (one where m == 0).  query: (n,sectors,rings), db: (cap,sectors,rings), both as desc above;
+ *   the entries [0, m) are searched, m BY VALUE (the caller counts its entries on the host).
+ * THE DISTANCE of a query Q, an entry D and a shift s in 0 .. sectors - 1:
+ *   pairing    column j of Q goes with column c = (j + s) mod sectors of D;
+ *   integers   a = sum_r Q[j][r]^2, b = sum_r D[c][r]^2, d = sum_r Q[j][r] * D[c][r]  (each below 2^31: 4095^2 * 32);
+ *   skipped    a pair with a == 0 or b == 0 (an empty column) gives no term and does not count in `pairs`;
+ *   term       1.0 - (double)d / sqrt((double)((unsigned long long)a * b)): product in 64-bit integers, ONE conversion, IEEE sqrt
+ *              and division;
+ *   dist       (sum of the terms) / (double)pairs, the terms added in ASCENDING j, one after the other, in double, from 0.0;
+ *              no pair at all: +inf.
+ *   A function of (Q, D, s) alone: not of where the entry sits or which lane computed it -- equal entries give equal bits.
+ *   best_shift[q][e], best_dist[q][e]: the shift with the smallest dist, the SMALLER shift winning a tie, and that dist.
+ *   ranking    the entries by (best_dist, entry) ascending; for r < k: entry[q][r], shift[q][r] = its best shift, dist[q][r].  Rows
+ *              r >= m are padded with -1, -1, +inf; m == 0 is legal and gives padding only.
+ *   THE YAW a shift stands for: the query's heading relative to the entry's, about the scan's z axis, is MINUS s * 2 pi / sectors
+ *   (mod 2 pi).  The columns of a range image run AGAINST the azimuth (column w looks along pi - (w + 0.5) 2 pi / W): a vehicle
+ *   turned by +yaw sees the place in columns moved up by yaw W / 2 pi, so its column j pairs with the entry's column j - yaw
+ *   sectors / 2 pi = j + s.  The guess of a fit is the entry's world pose composed with R_z(-s 2 pi / sectors)
+ *   (sensor.ScanContext.yaw_of is this rule on the host, wrapped to [-pi, pi)).
+ * Static trip bounds, nothing waits on another thread, no atomics in the search; no host synchronisation; capturable.  Two runs,
+ *   and an eager run and a graph replay, agree bit for bit.
+ * ELO_ERR_ARG (nothing is launched): a NULL pointer (best_shift / best_dist may be NULL only where m == 0), batch or n < 0, H < 1,
+ *   W < sectors, batch * H * W at or beyond 2^31, rings outside 1 .. ELO_PLACE_MAX_RINGS, sectors outside 1 ..
+ *   ELO_PLACE_MAX_SECTORS, z_step not positive and finite, z_min not finite, min_range2 negative or NaN, edge2[1 .. rings] not
+ *   positive, finite and ascending, m < 0, k outside 1 .. ELO_PLACE_MAX_K, dist / best_dist not 8-byte aligned.  An empty batch
+ *   (n == 0) launches nothing and is ELO_OK.
+ * LIFETIME as elo_model_render's.  Additive to ABI 26: no existing struct changes. */
+#define ELO_PLACE_MAX_RINGS 32
+#define ELO_PLACE_MAX_SECTORS 128
+#define ELO_PLACE_LEVELS 4095
+#define ELO_PLACE_MAX_K 8
+typedef struct elo_scan_descriptor_args {
+    int batch, H, W;
+    int rings, sectors;
+    double z_min, z_step;         /* m */
+    double min_range2;            /* m^2 */
+    double edge2[ELO_PLACE_MAX_RINGS + 1];  /* m^2: [1 .. rings] are read */
+    const float *xyz;             /* (batch,H,W,3); an all-zero cell is empty */
+    unsigned short *desc;         /* (batch,sectors,rings) OUT */
+} elo_scan_descriptor_args;
+int elo_scan_descriptor(const elo_scan_descriptor_args *a, elo_stream_t stream);
+typedef struct elo_descriptor_search_args {
+    int n, m;                     /* queries; entries searched, 0 .. the rows db holds */
+    int rings, sectors, k;
+    const unsigned short *query;  /* (n,sectors,rings) */
+    const unsigned short *db;     /* (>= m,sectors,rings) */
+    int *entry;                   /* (n,k) OUT */
+    int *shift;                   /* (n,k) OUT */
+    double *dist;                 /* (n,k) OUT */
+    int *best_shift;              /* (n,m) OUT */
+    double *best_dist;            /* (n,m) OUT */
+} elo_descriptor_search_args;
+int elo_descriptor_search(const elo_descriptor_search_args *a, elo_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * Backward passes of the feature kernels above, for TRAINING (csrc/elo_backward.hip).
  * The reference trains through TensorFlow's autodiff of its stock ops (main.py:171-176): gather_nd -> scatter-add of
