@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import kitti, pwclo_model
+from ._check import is_a
 from .local_model import DeviceTracker, ModelTracker
 from .distributed import quat2mat
 from .sensor import LocalModel, VoxelMap
@@ -73,11 +74,8 @@ def predict_sequence(net, root, seq, T_diff, H_input=64, W_input=1800, batch_siz
     them; the forward itself is untouched, so the return values are those of a run without the argument, bit for bit.  On the
     sequential path and with `lanes` (inside the in-order collection; the lane is not written again before the insert has read its
     clouds)."""
-    if world_map is not None and not isinstance(world_map, WorldMap):
-        raise TypeError("world_map is a WorldMap or None (got %r)" % (type(world_map).__name__,))
-    if model is not None:
-        if not isinstance(model, LocalModel):
-            raise TypeError("model is a LocalModel or None (got %r)" % (type(model).__name__,))
+    is_a("world_map", world_map, WorldMap, or_none=True)
+    if is_a("model", model, LocalModel, or_none=True) is not None:
         if fit is None:
             raise ValueError("a local model is what a pose fit runs against: pass fit=PoseFit(...) with model=")
         if lanes > 0 and not model.resident:

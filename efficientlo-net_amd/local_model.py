@@ -6,7 +6,7 @@ Several scans carried into one frame fill each other's holes: the model has the 
 
     tracker = ModelTracker(H, W, LocalModel(scans=4), PoseFit(iters=2))
     for xyz1, xyz2, pose7 in pairs:            # consecutive pairs of one drive
-        res = tracker.step(xyz1, xyz2, pose7)  # an _ops.PoseFitResult; res.pose: frame 1 -> frame 2, fitted against the model
+        res = tracker.step(xyz1, xyz2, pose7)  # an _scan_ops.PoseFitResult; res.pose: frame 1 -> frame 2, fitted against the model
 
 DIRECTION.  A pair is (frame 1, frame 2) = (scan n, scan n-1) -- kitti.load_pair hands over the current scan first, and the net's
 pose carries frame 1 into frame 2, the running product of evaluate.pose_rows.  So pair n's frame 2 is the scan that was pair
@@ -22,36 +22,10 @@ sequence without a host decision, recorded once into a hipGraph and replayed per
 """
 import torch
 
-from . import _ops
+from . import _ops, _scan_ops
 from . import sensor as _sensor
-
-
-def _qmul(a, b):
-    """Hamilton product of quaternions a (4) and b (n,4) -> (n,4)."""
-    a0, a1, a2, a3 = a.unbind(-1)
-    b0, b1, b2, b3 = b.unbind(-1)
-    return torch.stack([a0 * b0 - a1 * b1 - a2 * b2 - a3 * b3, a0 * b1 + a1 * b0 + a2 * b3 - a3 * b2,
-                        a0 * b2 - a1 * b3 + a2 * b0 + a3 * b1, a0 * b3 + a1 * b2 - a2 * b1 + a3 * b0], -1)
-
-
-def rebase(poses64, T):
-    """The held poses after the model's frame moved by T: every row P_j of poses64 (n,7) [q | t] (scan j -> the OLD model frame)
-    becomes T^-1 o P_j (scan j -> the NEW frame), where T (7) [q | t] carries the new frame into the old one, p_old = R(q) p_new
-    + t -- the pose a fit of (new scan, model) returns.  q_new = conj(q_T) (x) q_j, renormalised; t_new = R(q_T)^T (t_j - t_T).
-    A pure function in float64, on whatever device poses64 lives (array-likes are taken to the CPU): no host synchronisation."""
-    P = torch.as_tensor(poses64)
-    P = P.to(torch.float64).reshape(-1, 7)
-    T = torch.as_tensor(T).to(device=P.device, dtype=torch.float64).reshape(7)
-    q = T[:4] / T[:4].norm()
-    qc = torch.cat([q[:1], -q[1:]])
-    qn = _qmul(qc, P[:, :4] / P[:, :4].norm(dim=1, keepdim=True))
-    qn = qn / qn.norm(dim=1, keepdim=True)
-    # R(conj q) v = v + 2 w (u x v) + 2 u x (u x v), conj q = (w, u)
-    v = P[:, 4:] - T[4:]
-    u = qc[1:].expand_as(v)
-    c = torch.linalg.cross(u, v)
-    tn = v + 2.0 * qc[0] * c + 2.0 * torch.linalg.cross(u, c)
-    return torch.cat([qn, tn], 1)
+from ._check import is_a
+from .pose7 import rebase
 
 
 class _Tracker:
@@ -59,11 +33,8 @@ class _Tracker:
     beam table on the tracker's device (_ops.bind_sensor: uploaded once, owned here for every launch and graph that reads it)."""
 
     def __init__(self, H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"):
-        if not isinstance(model, _sensor.LocalModel):
-            raise TypeError("model is a LocalModel (got %r)" % (type(model).__name__,))
-        if not isinstance(fit, _sensor.PoseFit):
-            raise TypeError("fit is a PoseFit (got %r)" % (type(fit).__name__,))
-        self.H, self.W, self.model, self.fit = int(H), int(W), model, fit
+        self.model, self.fit = is_a("model", model, _sensor.LocalModel), is_a("fit", fit, _sensor.PoseFit)
+        self.H, self.W = int(H), int(W)
         if self.H < 3 or self.W < 1:
             raise ValueError("a pose fit needs H >= 3 and W >= 1 (got %d x %d)" % (self.H, self.W))
         self.device = torch.device(device)
@@ -77,7 +48,7 @@ class _Tracker:
 
 class ModelTracker(_Tracker):
     """ModelTracker(H, W, model, fit, sensor=None, beam_elev=None, device="cuda:0"): the local model of ONE drive.
-    model: sensor.LocalModel; fit: sensor.PoseFit; sensor / beam_elev: the cell rule, as _ops.pose_fit takes them (a sensor with a
+    model: sensor.LocalModel; fit: sensor.PoseFit; sensor / beam_elev: the cell rule, as _scan_ops.pose_fit takes them (a sensor with a
     beam table is uploaded once, here).
     State, all on the device: `ring` (scans,H,W,3) float32, zeroed -- slot i % scans holds the i-th scan that entered since
     reset(), an unused slot is all empty cells and gives the render nothing --; `poses64` (scans,7) float64 [q | t], scan of the
@@ -108,19 +79,19 @@ class ModelTracker(_Tracker):
         self.entered += 1
 
     def render(self):
-        """The model as it stands -> (xyz (1,H,W,3), src_idx (1,H,W)) of _ops.model_render."""
+        """The model as it stands -> (xyz (1,H,W,3), src_idx (1,H,W)) of _scan_ops.model_render."""
         self.poses32.copy_(self.poses64.reshape(1, -1, 7))
-        return _ops.model_render(self.ring.unsqueeze(0), self.poses32, sensor=self.sensor, beam_elev=self.beam_elev)
+        return _scan_ops.model_render(self.ring.unsqueeze(0), self.poses32, sensor=self.sensor, beam_elev=self.beam_elev)
 
     def step(self, xyz1, xyz2, pose7):
         """One pair: xyz1 / xyz2 (1,H,W,3) float32 range images on the tracker's device, pose7 (1,7) [q | t] from frame 1 to frame 2
-        -> the _ops.PoseFitResult of xyz1 against the MODEL at pose7.  Then the model moves into frame 1 by the pose the fit
+        -> the _scan_ops.PoseFitResult of xyz1 against the MODEL at pose7.  Then the model moves into frame 1 by the pose the fit
         returned (a flagged image's is pose7, by the kernel's own guarantee) and xyz1 enters it."""
         self._pair(xyz1, xyz2)
         if self.entered == 0:
             self._enter(xyz2)
         model, _src = self.render()
-        res = _ops.pose_fit(xyz1, model, pose7, self.fit, sensor=self.sensor, beam_elev=self.beam_elev)
+        res = _scan_ops.pose_fit(xyz1, model, pose7, self.fit, sensor=self.sensor, beam_elev=self.beam_elev)
         self.poses64.copy_(rebase(self.poses64, res.pose[0]))
         self._enter(xyz1)
         return res
@@ -161,12 +132,12 @@ class DeviceTracker(_Tracker):
         """One pair, as ModelTracker.step takes it -- xyz1 / xyz2 (1,H,W,3) float32 on the tracker's device, pose7 (1,7) -- enqueued on
         the current stream: begin (frame 2 enters an empty model), render, the fit of xyz1 against the rendered image at pose7, advance
         (the model moves into frame 1 by the pose the fit returned, xyz1 enters).  6 + 2 (iters + 1) launches, no host branch on
-        device state, no synchronisation -> the _ops.PoseFitResult."""
+        device state, no synchronisation -> the _scan_ops.PoseFitResult."""
         self._pair(xyz1, xyz2)
-        _ops.model_begin(self.ring, self.state, xyz2[0])
-        model, _src = _ops.model_render(self.ring.unsqueeze(0), self.poses32.unsqueeze(0), sensor=self.sensor, beam_elev=self.beam_elev)
-        res = _ops.pose_fit(xyz1, model, pose7, self.fit, sensor=self.sensor, beam_elev=self.beam_elev)
-        _ops.model_advance(self.ring, self.poses64, self.poses32, self.state, xyz1[0], res.pose)
+        _scan_ops.model_begin(self.ring, self.state, xyz2[0])
+        model, _src = _scan_ops.model_render(self.ring.unsqueeze(0), self.poses32.unsqueeze(0), sensor=self.sensor, beam_elev=self.beam_elev)
+        res = _scan_ops.pose_fit(xyz1, model, pose7, self.fit, sensor=self.sensor, beam_elev=self.beam_elev)
+        _scan_ops.model_advance(self.ring, self.poses64, self.poses32, self.state, xyz1[0], res.pose)
         return res
 
     def capture(self, warmup=2):

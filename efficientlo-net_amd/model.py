@@ -14,7 +14,8 @@ import numpy as np
 
 import torch
 
-from . import _lib, _ops, fused, model_util, perm, pwclo_model, tf_util, tuning
+from . import _lib, _ops, _scan_ops, fused, model_util, perm, pwclo_model, tf_util, tuning
+from ._check import is_a
 from . import sensor as sensor_mod
 
 
@@ -138,7 +139,7 @@ class PWCLONet:
     # -- eager ---------------------------------------------------------------
     def forward(self, xyz_f1_proj, xyz_f2_proj, is_training=False, bn_decay=None, pose_out=None, fit=None):
         """get_model_from_projection under this net's variables and permutations.
-        `fit` (sensor.PoseFit): the tuple gains one more entry, the _ops.PoseFitResult of the l0 pose on the pair's own range images
+        `fit` (sensor.PoseFit): the tuple gains one more entry, the _scan_ops.PoseFitResult of the l0 pose on the pair's own range images
         (elo_pose_fit, by this net's sensor / beam table); the other outputs are what they are without it."""
         if fit is not None:
             out = self.forward(xyz_f1_proj, xyz_f2_proj, is_training, bn_decay, pose_out)
@@ -159,7 +160,7 @@ class PWCLONet:
         with torch.no_grad():
             if pose7 is None:
                 pose7 = torch.cat([out[0].detach().reshape(-1, 4), out[1].detach().reshape(-1, 3)], -1).contiguous()
-            return _ops.pose_fit(xyz_f1_proj.detach().contiguous(), xyz_f2_proj.detach().contiguous(), pose7, fit, sensor=self.sensor,
+            return _scan_ops.pose_fit(xyz_f1_proj.detach().contiguous(), xyz_f2_proj.detach().contiguous(), pose7, fit, sensor=self.sensor,
                                  beam_elev=self.beam_elev)
 
     def forward_points(self, point_cloud, H_input, W_input, T_gt, T_trans, T_trans_inv, is_training=False,
@@ -285,9 +286,7 @@ class PWCLONet:
 
     @staticmethod
     def _check_capture_args(num_points, pose_ring, sweep, motion_is_pose, fit):
-        if fit is not None and not isinstance(fit, sensor_mod.PoseFit):
-            raise TypeError("fit is a PoseFit or None (got %r)" % (type(fit).__name__,))
-        if fit is not None and pose_ring:
+        if is_a("fit", fit, sensor_mod.PoseFit, or_none=True) is not None and pose_ring:
             raise ValueError("capture(pose_ring=..., fit=...): a pose fit reads the lane's ONE (B,7) pose block, a ring spreads "
                              "the rows over slots -- record one or the other")
         if sweep is not None and num_points is None:
@@ -535,7 +534,7 @@ class PWCLONet:
         return self._lanes[lane_index].motion
 
     def lane_fit(self, lane_index, fit=None):
-        """The _ops.PoseFitResult of the lane's last replay (capture(..., fit=PoseFit(...))): buffers the lane owns, written by
+        """The _scan_ops.PoseFitResult of the lane's last replay (capture(..., fit=PoseFit(...))): buffers the lane owns, written by
         the fit launches behind the l0 pose head; valid once the lane's stream has been synchronised or waited on.  `fit`: the
         PoseFit the caller expects the graphs to hold -- another one than capture() recorded is an error, not a silent mismatch."""
         lane = self._lanes[lane_index]

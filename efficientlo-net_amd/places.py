@@ -16,16 +16,18 @@ import math
 import numpy as np
 import torch
 
-from . import _ops
-from .local_model import _qmul
+from . import _scan_ops
+from ._check import integer, is_a
+from ._check_torch import image_batch, pose_rows
+from .pose7 import qmul
 from .sensor import ScanContext
 
 
 class PlaceMatch:
     """What PlaceIndex.query found for n scans: `entry` (n,k) int32, `shift` (n,k) int32, `dist` (n,k) float64 as
-    _ops.PlaceSearchResult's (padding: -1, -1, +inf), `yaw` (n,k) float64 -- the query's heading relative to the entry's about the
+    _scan_ops.PlaceSearchResult's (padding: -1, -1, +inf), `yaw` (n,k) float64 -- the query's heading relative to the entry's about the
     scan's z axis, ScanContext.yaw_of(shift), 0 for padding -- and `pose` (n,k,7) float64 [q | t]: the entry's world pose composed
-    with that rotation, the identity for padding.  `search`: the _ops.PlaceSearchResult itself (the per-entry profile)."""
+    with that rotation, the identity for padding.  `search`: the _scan_ops.PlaceSearchResult itself (the per-entry profile)."""
     __slots__ = ("entry", "shift", "dist", "yaw", "pose", "search")
 
     def __init__(self, entry, shift, dist, yaw, pose, search):
@@ -38,11 +40,9 @@ class PlaceIndex:
     is the host's (len())."""
 
     def __init__(self, spec, capacity=4096, device="cuda:0"):
-        if not isinstance(spec, ScanContext):
-            raise TypeError("spec is a ScanContext (got %r)" % (type(spec).__name__,))
-        if isinstance(capacity, bool) or not hasattr(capacity, "__index__") or not 1 <= capacity.__index__() < 2 ** 31:
-            raise ValueError("capacity is an integer >= 1 (got %r)" % (capacity,))
-        self.spec, self.capacity, self.device = spec, capacity.__index__(), torch.device(device)
+        self.spec = is_a("spec", spec, ScanContext)
+        self.capacity = integer("capacity", capacity, ValueError, 1, 2 ** 31 - 1)
+        self.device = torch.device(device)
         self.desc = torch.zeros((self.capacity, spec.sectors, spec.rings), dtype=torch.uint16, device=self.device)
         self.pose64 = torch.zeros((self.capacity, 7), dtype=torch.float64, device=self.device)
         self.scan = torch.zeros((self.capacity,), dtype=torch.int64, device=self.device)
@@ -62,12 +62,9 @@ class PlaceIndex:
         With pose64 -- and scan, where it is a tensor -- ON THE DEVICE the host never waits; a HOST pose64 or scan tensor costs a
         host-to-device copy, which waits for the stream (python integers do not: they are written by fills).  Raises IndexError
         where the index has no room for all n; nothing is added then.  Returns the index of the first entry added."""
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 4:
-            raise ValueError("xyz is an (n,H,W,3) tensor of range images")
-        n, first = xyz.shape[0], self._count
+        n, first = image_batch("xyz", xyz), self._count
         pose64 = torch.as_tensor(pose64)
-        if tuple(pose64.shape) != (n, 7):
-            raise ValueError("pose64 is one [q | t] row per image: (%d, 7) (got %s)" % (n, tuple(pose64.shape)))
+        pose_rows("pose64", pose64, (n, 7), "image", ValueError)
         if scan is None:
             scan = range(first, first + n)
         if isinstance(scan, torch.Tensor):
@@ -75,16 +72,14 @@ class PlaceIndex:
                 raise ValueError("a scan tensor is int64 (got %s)" % (scan.dtype,))
             scan = scan.reshape(-1)
         else:
-            scan = list(scan)
-            if any(isinstance(v, bool) or not hasattr(v, "__index__") for v in scan):
-                raise ValueError("scan is one integer per image (got %r)" % (scan,))
+            scan = [integer("scan", v, ValueError) for v in scan]       # (one integer per image)
         if len(scan) != n:
             raise ValueError("scan is one number per image (got %d for %d images)" % (len(scan), n))
         if first + n > self.capacity:
             raise IndexError("the index is full: %d entries held, %d more asked for, capacity %d" % (first, n, self.capacity))
         if n == 0:
             return first
-        _ops.scan_descriptor(xyz, self.spec, out=self.desc[first:first + n])
+        _scan_ops.scan_descriptor(xyz, self.spec, out=self.desc[first:first + n])
         self.pose64[first:first + n].copy_(pose64.to(device=self.device, dtype=torch.float64))
         if isinstance(scan, torch.Tensor):
             self.scan[first:first + n].copy_(scan.to(self.device))
@@ -92,17 +87,15 @@ class PlaceIndex:
             torch.arange(scan[0], scan[0] + n, dtype=torch.int64, device=self.device, out=self.scan[first:first + n])
         else:
             for j, v in enumerate(scan):
-                self.scan[first + j].fill_(v.__index__())
+                self.scan[first + j].fill_(v)
         self._count = first + n
         return first
 
     def query(self, xyz, k=1, skip_recent=0):
         """The k nearest entries of every image xyz (n,H,W,3) float32 among the entries [0, max(0, len - skip_recent)) ->
         PlaceMatch.  A descriptor launch, the search's two, and device-side float64 operators for the poses; the host never waits."""
-        if isinstance(skip_recent, bool) or not hasattr(skip_recent, "__index__") or skip_recent.__index__() < 0:
-            raise ValueError("skip_recent is an integer >= 0 (got %r)" % (skip_recent,))
-        m = max(0, self._count - skip_recent.__index__())
-        res = _ops.descriptor_search(_ops.scan_descriptor(xyz, self.spec), self.desc, m, self.spec, k)
+        m = max(0, self._count - integer("skip_recent", skip_recent, ValueError, 0))
+        res = _scan_ops.descriptor_search(_scan_ops.scan_descriptor(xyz, self.spec), self.desc, m, self.spec, k)
         return self._match(res)
 
     def _match(self, res):
@@ -114,8 +107,7 @@ class PlaceIndex:
         q = rows[..., :4] / rows[..., :4].norm(dim=-1, keepdim=True)
         half = 0.5 * yaw
         turn = torch.stack([torch.cos(half), torch.zeros_like(half), torch.zeros_like(half), torch.sin(half)], -1)
-        # q_entry (x) q_z(yaw), elementwise over (n,k): _qmul's formula with both operands batched
-        q = _qmul(q, turn)
+        q = qmul(q, turn)                                                                # q_entry (x) q_z(yaw), elementwise over (n,k)
         q = q / q.norm(dim=-1, keepdim=True)
         pose = torch.cat([q, rows[..., 4:]], -1)
         # (formed by device operators: assigning a python scalar into a device tensor copies it from the host)

@@ -24,6 +24,8 @@ places.PlaceIndex; WorldMap(places=)).
 """
 import math
 
+from ._check import integer, is_a, real
+
 
 class _Frozen:
     """A value: its fields (the subclass's __slots__) are set once by _freeze and never again; equal where the class and every
@@ -66,13 +68,11 @@ class Sensor(_Frozen):
                 raise ValueError("beam elevations must be finite")
             if not all(a > b for a, b in zip(table, table[1:])):
                 raise ValueError("beam elevations must be strictly descending (row 0 is the highest beam)")
-        up = float(fov_up_deg) if fov_up_deg is not None else (table[0] if table else 2.0)
-        down = float(fov_down_deg) if fov_down_deg is not None else (table[-1] if table else -24.8)
-        crop = float(crop_xy)
-        if not (math.isfinite(up) and math.isfinite(down) and up > down):
+        up = real("fov_up_deg", fov_up_deg, ValueError) if fov_up_deg is not None else (table[0] if table else 2.0)
+        down = real("fov_down_deg", fov_down_deg, ValueError) if fov_down_deg is not None else (table[-1] if table else -24.8)
+        if not up > down:
             raise ValueError("fov_up_deg must lie above fov_down_deg (got %r, %r)" % (up, down))
-        if not (crop > 0):
-            raise ValueError("crop_xy must be positive (got %r)" % (crop,))
+        crop = real("crop_xy", crop_xy, ValueError, finite=False, positive=True)
         self._freeze(up, down, crop, table)
 
     def __repr__(self):
@@ -111,14 +111,8 @@ class Sweep(_Frozen):
             if phase != "azimuth":
                 raise ValueError("phase is \"azimuth\" or the channel of the cloud that holds it (got %r)" % (phase,))
         else:
-            if isinstance(phase, bool) or not hasattr(phase, "__index__"):
-                raise ValueError("a phase channel is an integer (got %r)" % (phase,))
-            phase = phase.__index__()
-            if phase < 3:
-                raise ValueError("channels 0 .. 2 of a cloud are x, y, z: a phase channel is >= 3 (got %d)" % phase)
-        ref = float(phase_ref)
-        if not math.isfinite(ref):
-            raise ValueError("phase_ref must be finite (got %r)" % (ref,))
+            phase = integer("phase", phase, ValueError, 3)    # (channels 0 .. 2 of a cloud are x, y, z)
+        ref = real("phase_ref", phase_ref, ValueError)
         self._freeze(phase, ref)
 
     def __repr__(self):
@@ -135,21 +129,12 @@ class PoseFit(_Frozen):
     __slots__ = ("iters", "gate", "huber", "jump_rel", "min_count", "damping")
 
     def __init__(self, iters=0, gate=1.0, huber=0.1, jump_rel=0.1, min_count=50, damping=0.0):
-        for name, value in (("iters", iters), ("min_count", min_count)):
-            if isinstance(value, bool) or not hasattr(value, "__index__"):
-                raise ValueError("%s is an integer (got %r)" % (name, value))
-        iters, min_count = iters.__index__(), min_count.__index__()
-        if iters < 0 or iters > 64:
-            raise ValueError("iters is 0 .. 64 (got %d)" % iters)
-        if min_count < 0 or min_count >= 2 ** 31:
-            raise ValueError("min_count is a non-negative 32-bit count (got %d)" % min_count)
-        gate, huber, jump_rel, damping = float(gate), float(huber), float(jump_rel), float(damping)
-        for name, value in (("gate", gate), ("huber", huber)):
-            if not (math.isfinite(value) and value > 0):
-                raise ValueError("%s must be positive and finite (got %r)" % (name, value))
-        for name, value in (("jump_rel", jump_rel), ("damping", damping)):
-            if not (math.isfinite(value) and value >= 0):
-                raise ValueError("%s must be finite and >= 0 (got %r)" % (name, value))
+        iters = integer("iters", iters, ValueError, 0, 64)
+        min_count = integer("min_count", min_count, ValueError, 0, 2 ** 31 - 1)
+        gate = real("gate", gate, ValueError, positive=True)
+        huber = real("huber", huber, ValueError, positive=True)
+        jump_rel = real("jump_rel", jump_rel, ValueError, non_negative=True)
+        damping = real("damping", damping, ValueError, non_negative=True)
         self._freeze(iters, gate, huber, jump_rel, min_count, damping)
 
     def __repr__(self):
@@ -165,11 +150,7 @@ class LocalModel(_Frozen):
     __slots__ = ("scans", "resident")
 
     def __init__(self, scans=4, resident=False):
-        if isinstance(scans, bool) or not hasattr(scans, "__index__"):
-            raise ValueError("scans is an integer (got %r)" % (scans,))
-        scans = scans.__index__()
-        if scans < 1 or scans > 16:
-            raise ValueError("scans is 1 .. 16 (got %d)" % scans)
+        scans = integer("scans", scans, ValueError, 1, 16)
         if not isinstance(resident, bool):
             raise ValueError("resident is True or False (got %r)" % (resident,))
         self._freeze(scans, resident)
@@ -191,16 +172,10 @@ class VoxelMap(_Frozen):
     __slots__ = ("voxel", "log2_capacity", "min_range", "max_range")
 
     def __init__(self, voxel=0.5, log2_capacity=22, min_range=0.0, max_range=math.inf):
-        if isinstance(log2_capacity, bool) or not hasattr(log2_capacity, "__index__"):
-            raise ValueError("log2_capacity is an integer (got %r)" % (log2_capacity,))
-        log2_capacity = log2_capacity.__index__()
-        if log2_capacity < 10 or log2_capacity > 28:
-            raise ValueError("log2_capacity is 10 .. 28 (got %d)" % log2_capacity)
-        voxel, min_range, max_range = float(voxel), float(min_range), float(max_range)
-        if not (math.isfinite(voxel) and voxel > 0):
-            raise ValueError("voxel must be positive and finite (got %r)" % (voxel,))
-        if not (math.isfinite(min_range) and min_range >= 0):
-            raise ValueError("min_range must be finite and >= 0 (got %r)" % (min_range,))
+        log2_capacity = integer("log2_capacity", log2_capacity, ValueError, 10, 28)
+        voxel = real("voxel", voxel, ValueError, positive=True)
+        min_range = real("min_range", min_range, ValueError, non_negative=True)
+        max_range = real("max_range", max_range, ValueError, finite=False)
         if not (max_range > min_range):
             raise ValueError("max_range must lie above min_range (got %r, %r)" % (max_range, min_range))
         self._freeze(voxel, log2_capacity, min_range, max_range)
@@ -224,11 +199,7 @@ class MapFit(_Frozen):
 
     def __init__(self, iters=0, gate=None, huber=0.1, jump_rel=0.1, min_count=50, damping=0.0, min_points=1):
         base = PoseFit(iters, 1.0 if gate is None else gate, huber, jump_rel, min_count, damping)
-        if isinstance(min_points, bool) or not hasattr(min_points, "__index__"):
-            raise ValueError("min_points is an integer (got %r)" % (min_points,))
-        min_points = min_points.__index__()
-        if min_points < 1 or min_points >= 2 ** 31:
-            raise ValueError("min_points is a positive 32-bit count (got %d)" % min_points)
+        min_points = integer("min_points", min_points, ValueError, 1, 2 ** 31 - 1)
         self._freeze(base.iters, None if gate is None else base.gate, base.huber, base.jump_rel, base.min_count, base.damping, min_points)
 
     def __repr__(self):
@@ -251,17 +222,10 @@ class MapWindow(_Frozen):
     __slots__ = ("radius", "every", "min_count")
 
     def __init__(self, radius, every=10, min_count=1):
-        for name, value in (("every", every), ("min_count", min_count)):
-            if isinstance(value, bool) or not hasattr(value, "__index__"):
-                raise ValueError("%s is an integer (got %r)" % (name, value))
-            if value.__index__() < 1 or value.__index__() >= 2 ** 63:
-                raise ValueError("%s is >= 1 (got %d)" % (name, value.__index__()))
-        if isinstance(radius, bool):
-            raise ValueError("radius is a length in metres (got %r)" % (radius,))
-        radius = float(radius)
-        if not (math.isfinite(radius) and radius > 0):
-            raise ValueError("radius must be positive and finite (got %r)" % (radius,))
-        self._freeze(radius, every.__index__(), min_count.__index__())
+        every = integer("every", every, ValueError, 1, 2 ** 63 - 1)
+        min_count = integer("min_count", min_count, ValueError, 1, 2 ** 63 - 1)
+        radius = real("radius", radius, ValueError, positive=True, takes="no_bool")
+        self._freeze(radius, every, min_count)
 
     def __repr__(self):
         return "MapWindow(radius=%r, every=%r, min_count=%r)" % self._key()
@@ -277,24 +241,15 @@ class ScanContext(_Frozen):
     LEVELS = 4095
 
     def __init__(self, rings=20, sectors=60, max_range=KITTI_HDL64.crop_xy, min_range=0.0, z_min=-3.0, z_step=0.005):
-        for name, value, most in (("rings", rings, 32), ("sectors", sectors, 128)):
-            if isinstance(value, bool) or not hasattr(value, "__index__"):
-                raise ValueError("%s is an integer (got %r)" % (name, value))
-            if value.__index__() < 1 or value.__index__() > most:
-                raise ValueError("%s is 1 .. %d (got %d)" % (name, most, value.__index__()))
-        for name, value in (("max_range", max_range), ("min_range", min_range), ("z_min", z_min), ("z_step", z_step)):
-            if isinstance(value, bool):
-                raise ValueError("%s is a length in metres (got %r)" % (name, value))
-        max_range, min_range, z_min, z_step = float(max_range), float(min_range), float(z_min), float(z_step)
-        if not (math.isfinite(min_range) and min_range >= 0):
-            raise ValueError("min_range must be finite and >= 0 (got %r)" % (min_range,))
-        if not (math.isfinite(max_range) and max_range > min_range):
-            raise ValueError("max_range must be finite and lie above min_range (got %r, %r)" % (max_range, min_range))
-        if not math.isfinite(z_min):
-            raise ValueError("z_min must be finite (got %r)" % (z_min,))
-        if not (math.isfinite(z_step) and z_step > 0):
-            raise ValueError("z_step must be positive and finite (got %r)" % (z_step,))
-        self._freeze(rings.__index__(), sectors.__index__(), max_range, min_range, z_min, z_step)
+        rings = integer("rings", rings, ValueError, 1, 32)
+        sectors = integer("sectors", sectors, ValueError, 1, 128)
+        max_range = real("max_range", max_range, ValueError, takes="no_bool")
+        min_range = real("min_range", min_range, ValueError, non_negative=True, takes="no_bool")
+        if not max_range > min_range:
+            raise ValueError("max_range must lie above min_range (got %r, %r)" % (max_range, min_range))
+        z_min = real("z_min", z_min, ValueError, takes="no_bool")
+        z_step = real("z_step", z_step, ValueError, positive=True, takes="no_bool")
+        self._freeze(rings, sectors, max_range, min_range, z_min, z_step)
 
     def __repr__(self):
         return "ScanContext(rings=%r, sectors=%r, max_range=%r, min_range=%r, z_min=%r, z_step=%r)" % self._key()
@@ -328,15 +283,11 @@ class Places(_Frozen):
     __slots__ = ("context", "every", "skip_recent", "capacity")
 
     def __init__(self, context=None, every=5, skip_recent=50, capacity=4096):
-        context = ScanContext() if context is None else context
-        if not isinstance(context, ScanContext):
-            raise ValueError("context is a ScanContext (got %r)" % (type(context).__name__,))
-        for name, value, least in (("every", every, 1), ("skip_recent", skip_recent, 0), ("capacity", capacity, 1)):
-            if isinstance(value, bool) or not hasattr(value, "__index__"):
-                raise ValueError("%s is an integer (got %r)" % (name, value))
-            if value.__index__() < least or value.__index__() >= 2 ** 31:
-                raise ValueError("%s is %d .. 2^31 - 1 (got %d)" % (name, least, value.__index__()))
-        self._freeze(context, every.__index__(), skip_recent.__index__(), capacity.__index__())
+        context = ScanContext() if context is None else is_a("context", context, ScanContext, ValueError)
+        every = integer("every", every, ValueError, 1, 2 ** 31 - 1)
+        skip_recent = integer("skip_recent", skip_recent, ValueError, 0, 2 ** 31 - 1)
+        capacity = integer("capacity", capacity, ValueError, 1, 2 ** 31 - 1)
+        self._freeze(context, every, skip_recent, capacity)
 
     def __repr__(self):
         return "Places(context=%r, every=%r, skip_recent=%r, capacity=%r)" % self._key()
@@ -344,11 +295,7 @@ class Places(_Frozen):
 
 def resolve(sensor):
     """sensor=None is the reference's sensor."""
-    if sensor is None:
-        return KITTI_HDL64
-    if not isinstance(sensor, Sensor):
-        raise TypeError("sensor is a Sensor or None (got %r)" % (type(sensor).__name__,))
-    return sensor
+    return KITTI_HDL64 if sensor is None else is_a("sensor", sensor, Sensor)
 
 
 def projection_constants(H_input, W_input, sensor=None):

@@ -34,27 +34,12 @@ Where keys sit in the table is NOT determined; points() sorts by key, and that i
 import numpy as np
 import torch
 
-from . import _ops
-from .local_model import _qmul
+from . import _scan_ops
+from ._check import is_a
+from ._check_torch import image_batch, pose_rows
 from .places import PlaceIndex
+from .pose7 import compose
 from .sensor import MapFit, MapWindow, Places, VoxelMap
-
-
-def compose(world64, pose7):
-    """W o T: world64 (7) [q | t] (scan n-1 -> world) and pose7 (7) [q | t] (scan n -> scan n-1) -> (7) float64 (scan n -> world):
-    q = q_W (x) q_T, renormalised (both are normalised where they are used); t = R(q_W) t_T + t_W.  A pure function in float64, on
-    whatever device world64 lives (array-likes are taken to the CPU): no host synchronisation."""
-    Wp = torch.as_tensor(world64)
-    Wp = Wp.to(torch.float64).reshape(7)
-    T = torch.as_tensor(pose7).to(device=Wp.device, dtype=torch.float64).reshape(7)
-    qw = Wp[:4] / Wp[:4].norm()
-    q = _qmul(qw, (T[:4] / T[:4].norm()).reshape(1, 4))[0]
-    q = q / q.norm()
-    # R(q) v = v + 2 w (u x v) + 2 u x (u x v), q = (w, u)
-    v, u = T[4:], qw[1:]
-    c = torch.linalg.cross(u, v)
-    t = v + 2.0 * qw[0] * c + 2.0 * torch.linalg.cross(u, c) + Wp[4:]
-    return torch.cat([q, t])
 
 
 class WorldMap:
@@ -65,7 +50,7 @@ class WorldMap:
     only: the host never waits for the device.
     fit: a sensor.MapFit -- add() then holds the running pose to the map: each scan's composed pose is the guess of a fit against
     the map as it stands, the scan is inserted at the fitted pose and `world64` becomes that pose.  A flagged scan (the first one,
-    against an empty map; a starved one) goes in at its guess.  `last_fit`: the _ops.MapFitResult rows of the last add().
+    against an empty map; a starved one) goes in at its guess.  `last_fit`: the _scan_ops.MapFitResult rows of the last add().
     window: a sensor.MapWindow -- after every `every`-th scan added since reset() (a HOST count: no device value is read) the map
     is rebuilt about the translation of that scan's world pose: rebuild().  `keys`, `acc` -- and `spec`, where a rebuild changed
     the capacity -- are REBOUND by a rebuild: take them from the map after it, do not hold on to them.
@@ -77,18 +62,11 @@ class WorldMap:
     STATS = ("inserted", "filtered", "rejected", "dropped_full", "occupied")
 
     def __init__(self, spec, device="cuda:0", fit=None, window=None, places=None):
-        if not isinstance(spec, VoxelMap):
-            raise TypeError("spec is a VoxelMap (got %r)" % (type(spec).__name__,))
-        if fit is not None:
-            if not isinstance(fit, MapFit):
-                raise TypeError("fit is a MapFit or None (got %r)" % (type(fit).__name__,))
+        self.spec, self.device = is_a("spec", spec, VoxelMap), torch.device(device)
+        if is_a("fit", fit, MapFit, or_none=True) is not None:
             fit.gate_for(spec)                               # a gate beyond the voxel is refused here, not at the first scan
-        if window is not None and not isinstance(window, MapWindow):
-            raise TypeError("window is a MapWindow or None (got %r)" % (type(window).__name__,))
-        if places is not None and not isinstance(places, Places):
-            raise TypeError("places is a Places or None (got %r)" % (type(places).__name__,))
-        self.spec, self.device, self.tracking, self.window = spec, torch.device(device), fit, window
-        self.place_spec = places
+        self.tracking, self.window = fit, is_a("window", window, MapWindow, or_none=True)
+        self.place_spec = is_a("places", places, Places, or_none=True)
         self.places = PlaceIndex(places.context, places.capacity, self.device) if places is not None else None
         self._revisits = []
         self.last_fit, self._rows, self._log = None, [], []
@@ -118,16 +96,16 @@ class WorldMap:
     def insert(self, xyz, pose64):
         """The raw insert: range images xyz (n,H,W,3) float32 at the poses pose64 (n,7) float64 [q | t], scan -> world.  The running
         world pose is neither read nor moved."""
-        _ops.map_insert(self.keys, self.acc, self.stat_words, xyz, pose64, self.spec)
+        _scan_ops.map_insert(self.keys, self.acc, self.stat_words, xyz, pose64, self.spec)
 
     def fit(self, xyz, pose64, match=False, fit=None):
         """The raw fit against this map: range images xyz (n,H,W,3) float32 at the guesses pose64 (n,7) float64 [q | t], scan ->
-        world -> the _ops.MapFitResult (pose: the fitted world poses, float64).  `fit`: a sensor.MapFit (None: the one this map
+        world -> the _scan_ops.MapFitResult (pose: the fitted world poses, float64).  `fit`: a sensor.MapFit (None: the one this map
         was built with).  The map and the running world pose are only read."""
         fit = self.tracking if fit is None else fit
         if fit is None:
             raise ValueError("this map was built without a MapFit: pass fit=MapFit(...)")
-        return _ops.map_fit(self.keys, self.acc, xyz, pose64, self.spec, fit, match=match)
+        return _scan_ops.map_fit(self.keys, self.acc, xyz, pose64, self.spec, fit, match=match)
 
     def trajectory(self):
         """(n,7) float64 on the device: the world pose every scan added since reset() was inserted at, in order."""
@@ -148,12 +126,9 @@ class WorldMap:
         against the map as it stands, insert at the fitted pose.  Everything is enqueued; the host never waits.  With Places the
         scans due for a lookup are looked up and appended after that, by launches and device-side operators alone; where the index
         has no room for all of them IndexError is raised BEFORE anything is enqueued and the map is as it was."""
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 4:
-            raise ValueError("xyz is an (n,H,W,3) tensor of range images")
+        n = image_batch("xyz", xyz)
         pose7 = torch.as_tensor(pose7).to(device=self.device, dtype=torch.float64)
-        n = xyz.shape[0]
-        if tuple(pose7.shape) != (n, 7):
-            raise ValueError("pose7 is one [q | t] row per image: (%d, 7) (got %s)" % (n, tuple(pose7.shape)))
+        pose_rows("pose7", pose7, (n, 7), "image", ValueError)
         if n == 0:
             return
         visits = [j for j in range(n) if (self._scans + j + 1) % self.place_spec.every == 0] if self.places is not None else []
@@ -187,7 +162,7 @@ class WorldMap:
                 rows.append(res.pose)
                 self._log.append(res.stats)
             rows = torch.cat(rows)
-            self.last_fit = fits[0] if n == 1 else _ops.MapFitResult(rows, *(torch.cat([getattr(f, name) for f in fits])
+            self.last_fit = fits[0] if n == 1 else _scan_ops.MapFitResult(rows, *(torch.cat([getattr(f, name) for f in fits])
                                                                             for name in ("info", "grad", "stats")))
         self._rows.append(rows)
         self.world64.copy_(world)
@@ -220,7 +195,7 @@ class WorldMap:
     def relocalise(self, xyz, k=4, fit=None):
         """One scan xyz (1,H,W,3) float32 with NO pose guess: the k nearest places of the index (PlaceIndex.query), a fit against
         the map at each of their guesses -- the keyframe's world pose turned by the matched heading -- and the choice among them
-        -> {"match": the places.PlaceMatch, "fits": the _ops.MapFitResult of the k guesses (rows in rank order; padding rows are
+        -> {"match": the places.PlaceMatch, "fits": the _scan_ops.MapFitResult of the k guesses (rows in rank order; padding rows are
         fitted at the identity and count as flagged), "best": a python int}.  best: the candidate that is not flagged (status 0)
         with the most terms, ties going to the better rank; -1 where every candidate is flagged.  SYNCHRONISES to choose (the k
         status words and counts are read).  `fit`: a sensor.MapFit (None: the one this map was built with).
@@ -229,8 +204,8 @@ class WorldMap:
         flagged or unmoved; it needs a coarser map first, which is not built here."""
         if self.places is None:
             raise ValueError("this map was built without Places: pass places=Places(...)")
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 4 or xyz.shape[0] != 1:
-            raise ValueError("xyz is one (1,H,W,3) range image")
+        if image_batch("xyz", xyz) != 1:
+            raise ValueError("xyz is one (1,H,W,3) range image (got %s)" % (tuple(xyz.shape),))
         match = self.places.query(xyz, k=k)
         kk = match.entry.shape[1]
         fits = self.fit(xyz.expand(kk, -1, -1, -1).contiguous(), match.pose[0].contiguous(), fit=fit)
@@ -246,7 +221,7 @@ class WorldMap:
         """Add the voxels of `other` -- a WorldMap of the same voxel (ValueError otherwise; its capacity may differ), or a (key, acc)
         pair of int64 tensors: (m,) keys and (m,4) {count, sx, sy, sz} rows, those of state() for one -- into this map: the UNION.
         The sums are integers, so the result is exactly the map of both maps' points.  centre (3 float64 on the device, read when
-        the launch runs), radius, min_count: the filter of _ops.map_merge.  `inserted` grows by the points merged, `dropped_full` by
+        the launch runs), radius, min_count: the filter of _scan_ops.map_merge.  `inserted` grows by the points merged, `dropped_full` by
         those that found no slot, and a WorldMap's own `filtered`, `rejected` and `dropped_full` totals are added to this map's:
         the totals of both drives.  Returns the report, (8,) int64 on the device (_lib.MAP_REPORT); `other` is only read."""
         if isinstance(other, WorldMap):
@@ -258,14 +233,14 @@ class WorldMap:
                 key, acc = other
             except (TypeError, ValueError):
                 raise TypeError("other is a WorldMap or a (key, acc) pair of int64 tensors (got %r)" % (type(other).__name__,)) from None
-        report = _ops.map_merge(self.keys, self.acc, self.stat_words, key, acc, self.spec, centre, radius, min_count)
+        report = _scan_ops.map_merge(self.keys, self.acc, self.stat_words, key, acc, self.spec, centre, radius, min_count)
         if isinstance(other, WorldMap):
             self.stat_words[1:4] += other.stat_words[1:4].to(self.device)
         return report
 
     def rebuild(self, log2_capacity=None, centre=None, radius=None, min_count=1):
         """The map moved into a FRESH table of the same or a new capacity (log2_capacity; `spec` is then replaced by the VoxelMap of
-        that capacity), filled on the device, under the filter of _ops.map_merge: GROWTH (a larger table, no filter) and EVICTION
+        that capacity), filled on the device, under the filter of _scan_ops.map_merge: GROWTH (a larger table, no filter) and EVICTION
         (a window about `centre`, a least count) are both this.  `keys` and `acc` are rebound; the two buffer sets of one capacity are
         kept and alternate, so a windowed drive allocates nothing after its first rebuild.  `inserted`, `filtered`, `rejected` and
         `dropped_full` stay the drive's running totals, `occupied` becomes the new table's; what the rebuild left behind is summed
@@ -281,7 +256,7 @@ class WorldMap:
         keys.fill_(-1)
         acc.zero_()
         self._fresh_stats.zero_()
-        report = _ops.map_merge(keys, acc, self._fresh_stats, self.keys, self.acc, spec, centre, radius, min_count)
+        report = _scan_ops.map_merge(keys, acc, self._fresh_stats, self.keys, self.acc, spec, centre, radius, min_count)
         self.stat_words[4].copy_(self._fresh_stats[4])
         self.window_words += report
         self._spare = (self.keys, self.acc) if spec.capacity == self.spec.capacity else None
@@ -339,9 +314,7 @@ class WorldMap:
             state = {name: f[name] for name in f.files}
         log2 = int(state["log2_capacity"]) if log2_capacity is None else log2_capacity
         wm = cls(VoxelMap(float(state["voxel"]), log2, float(state["min_range"]), float(state["max_range"])), device, fit=fit, window=window)
-        if places is not None:
-            if not isinstance(places, Places):
-                raise TypeError("places is a Places or None (got %r)" % (type(places).__name__,))
+        if is_a("places", places, Places, or_none=True) is not None:
             index = PlaceIndex.from_state(state, places.capacity, wm.device)     # (the one index this map gets: none was built above)
             if index.spec != places.context:
                 raise ValueError("%s holds descriptors of %r, not of %r" % (path, index.spec, places.context))
@@ -352,7 +325,7 @@ class WorldMap:
             wm._revisits = [torch.from_numpy(np.ascontiguousarray(log)).to(wm.device)] if len(log) else []
         key = torch.from_numpy(np.ascontiguousarray(state["key"], dtype=np.int64)).to(wm.device)
         acc = torch.from_numpy(np.ascontiguousarray(state["acc"], dtype=np.int64)).to(wm.device)
-        report = _ops.map_merge(wm.keys, wm.acc, wm._fresh_stats.zero_(), key, acc, wm.spec)
+        report = _scan_ops.map_merge(wm.keys, wm.acc, wm._fresh_stats.zero_(), key, acc, wm.spec)
         words = [int(state[name]) for name in cls.STATS[:4]]
         wm.stat_words[:4].copy_(torch.tensor(words, dtype=torch.int64))
         wm.stat_words[4].copy_(wm._fresh_stats[4])
@@ -371,7 +344,7 @@ class WorldMap:
         """(xyz (m,3) float32 centroids, count (m) int64, key (m) int64), one row per occupied voxel, SORTED BY KEY (torch.sort, on the
         device): the table's own order is arbitrary, this one is canonical.  Synchronises (m is read)."""
         m = int(self.stat_words[4].item())                   # `occupied`: the rows to make room for
-        key, count, xyz, n = _ops.map_extract(self.keys, self.acc, self.spec, m)
+        key, count, xyz, n = _scan_ops.map_extract(self.keys, self.acc, self.spec, m)
         if int(n.item()) != m:
             raise RuntimeError("the map holds %d voxels, its counter says %d: buffers nobody reset?" % (int(n.item()), m))
         key, order = torch.sort(key)

@@ -22,7 +22,7 @@ OPS = ("input_stage", "input_stage+sweep", "pose_fit/0", "pose_fit/2", "model_re
 
 def build_calls():
     """{name: f(**how) -> tuple of output tensors} on fixed device inputs; `how` is sensor= / beam_elev=."""
-    ops, S, synth = load_pkg("_ops"), load_pkg("sensor"), load_pkg("synth")
+    ops, scan_ops, S, synth = load_pkg("_ops"), load_pkg("_scan_ops"), load_pkg("sensor"), load_pkg("synth")
     sensor = S.Sensor(beam_elevations_deg=D.TABLE8)
     rng = np.random.default_rng(8)
     cloud = np.zeros((B, 2 * N, 4), np.float32)
@@ -39,13 +39,13 @@ def build_calls():
     fit = lambda iters: S.PoseFit(iters=iters, jump_rel=0.5, min_count=20)
 
     def fitted(iters, **how):
-        res = ops.pose_fit(x1, x2, pose7, fit(iters), **how)
+        res = scan_ops.pose_fit(x1, x2, pose7, fit(iters), **how)
         return res.pose, res.info, res.grad, res.stats
 
     return {"input_stage": lambda **how: ops.input_stage(cloud, None, None, H, W, **how),
             "input_stage+sweep": lambda **how: ops.input_stage(cloud, None, None, H, W, sweep=S.Sweep(phase=3), motion=motion, **how),
             "pose_fit/0": lambda **how: fitted(0, **how), "pose_fit/2": lambda **how: fitted(2, **how),
-            "model_render": lambda **how: ops.model_render(src, carry, **how)}
+            "model_render": lambda **how: scan_ops.model_render(src, carry, **how)}
 
 
 def same(a, b):

@@ -1,4 +1,4 @@
-"""The net half of tests/test_pose_fit_gpu.py, run as a program of its own: forward(fit=) against _ops.pose_fit on the same pair and
+"""The net half of tests/test_pose_fit_gpu.py, run as a program of its own: forward(fit=) against _scan_ops.pose_fit on the same pair and
 pose, a lane captured with a fit against the eager result (and its other outputs against a capture without one), a graph replay of
 the bare entry against its eager call, the refusals, and the sequence evaluation's fit file on both of its paths.
 It is a program because capture() draws its streams from the process-wide pool and binds them to hardware queues: in the suite's
@@ -26,7 +26,7 @@ def same(a, b):
 
 
 def main():
-    model, S, perm, ops, ev = load_pkg("model"), load_pkg("sensor"), load_pkg("perm"), load_pkg("_ops"), load_pkg("evaluate")
+    model, S, perm, ops, ev = load_pkg("model"), load_pkg("sensor"), load_pkg("perm"), load_pkg("_scan_ops"), load_pkg("evaluate")
     H, W = 64, 900
     f1, f2 = R.scene(1, H, W, seed=21)
     a, b = t(f1), t(f2)

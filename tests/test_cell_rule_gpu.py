@@ -1,5 +1,5 @@
 """GPU: the three ways of giving a beam table -- through `sensor=`, as a host list, as the device tensor of beam_table() -- are ONE
-call for _ops.input_stage (without and with a Sweep), _ops.pose_fit (iters 0 and 2) and _ops.model_render: bit-equal outputs.  A
+call for _ops.input_stage (without and with a Sweep), _scan_ops.pose_fit (iters 0 and 2) and _scan_ops.model_render: bit-equal outputs.  A
 device tensor is the memory the launch reads (no hidden copy), a malformed one is refused before anything is launched, and a host
 table is refused inside an open capture, which then closes cleanly (tests/cell_rule_capture.py).  B = 2, N = 256 points, 8 x 32 images, K = 2 scans, a
 non-uniform 8-beam table: every branch of _ops.cell_rule, in a few seconds."""

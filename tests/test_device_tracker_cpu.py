@@ -1,6 +1,6 @@
 """CPU: the tracker state on the device as far as it can be checked without one -- the LocalModel(resident=) value, the ctypes
-mirror of elo_model_begin_args / elo_model_advance_args against include/elo.h, the host's refusals of _ops.model_begin /
-_ops.model_advance (before the library is touched), DeviceTracker's and predict_sequence's argument errors, and the numpy state
+mirror of elo_model_begin_args / elo_model_advance_args against include/elo.h, the host's refusals of _scan_ops.model_begin /
+_scan_ops.model_advance (before the library is touched), DeviceTracker's and predict_sequence's argument errors, and the numpy state
 machine tests/test_device_tracker_gpu.py compares the kernels with (tests/device_tracker_reference.py) against a plain list of "the
 last K scans"."""
 import ctypes
@@ -75,7 +75,7 @@ def test_the_argument_blocks_are_declared_and_mirrored(tmp_path):
 
 
 def test_host_refusals_come_before_the_library(monkeypatch):
-    ops, L, S, lm = load_pkg("_ops"), load_pkg("_lib"), load_pkg("sensor"), load_pkg("local_model")
+    ops, L, S, lm = load_pkg("_scan_ops"), load_pkg("_lib"), load_pkg("sensor"), load_pkg("local_model")
 
     def no_library():
         raise AssertionError("the library was touched")

@@ -25,7 +25,7 @@ H, W = M.BOX_H, M.BOX_W
 
 
 def _pkgs():
-    return load_pkg("_ops"), load_pkg("sensor"), load_pkg("_lib"), load_pkg("local_model")
+    return load_pkg("_scan_ops"), load_pkg("sensor"), load_pkg("_lib"), load_pkg("local_model")
 
 
 def _fit(S, iters=2):
@@ -42,7 +42,7 @@ def _same_result(a, b):
 
 def _keep(res):
     """A copy of a result (a captured tracker's is overwritten by its next step)."""
-    return load_pkg("_ops").PoseFitResult(res.pose.clone(), res.info.clone(), res.grad.clone(), res.stats.clone())
+    return load_pkg("_scan_ops").PoseFitResult(res.pose.clone(), res.info.clone(), res.grad.clone(), res.stats.clone())
 
 
 def _snapshot(tr):
@@ -65,7 +65,7 @@ def _is_reset(tr):
 def _check_step(tr, before, x1, x2, pose7, res, fit, sensor=None):
     """One step against the statement made by hand from `before`, the state read back ahead of it: (a) - (e) of the module's
     docstring order -- result, ring and state, re-based poses, the entered row, the float32 copy.  -> the by-hand fit."""
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     K = tr.model.scans
     torch.cuda.synchronize()
     nxt, held = before["state"]
@@ -231,7 +231,7 @@ def test_reset_mid_drive():
     assert torch.equal(bits(tr.ring[0]), bits(pairs[3][1][0])) and torch.equal(bits(tr.ring[1]), bits(pairs[3][0][0]))
     assert not bits(tr.ring[2:]).any() and tr.state.tolist() == [2, 2]
     tr.reset()                                                # (slots 1 .. K-1 are zero once the first frame 2 is in)
-    load_pkg("_ops").model_begin(tr.ring, tr.state, pairs[0][1][0])
+    load_pkg("_scan_ops").model_begin(tr.ring, tr.state, pairs[0][1][0])
     torch.cuda.synchronize()
     assert torch.equal(bits(tr.ring[0]), bits(pairs[0][1][0])) and not bits(tr.ring[1:]).any() and tr.state.tolist() == [0, 0]
 

@@ -1,4 +1,4 @@
-"""CPU: the LocalModel value, the host's refusals of _ops.model_render (before the library is touched), predict_sequence's argument
+"""CPU: the LocalModel value, the host's refusals of _scan_ops.model_render (before the library is touched), predict_sequence's argument
 errors, local_model.rebase, and the scenes tests/test_local_model_gpu.py runs the kernel on -- the share of cells the float64
 statement (tests/local_model_reference.py) calls ambiguous, and the box-scene term counts the tracker test relies on."""
 import numpy as np
@@ -26,7 +26,7 @@ def test_local_model_value():
 
 
 def test_host_refusals_come_before_the_library(monkeypatch):
-    ops, L, S = load_pkg("_ops"), load_pkg("_lib"), load_pkg("sensor")
+    ops, L, S = load_pkg("_scan_ops"), load_pkg("_lib"), load_pkg("sensor")
 
     def no_library():
         raise AssertionError("the library was touched")

@@ -28,7 +28,7 @@ def _sensor(beam):
 
 
 def _render(src, pose, beam=None):
-    xyz, idx = load_pkg("_ops").model_render(t(src), t(pose), sensor=_sensor(beam))
+    xyz, idx = load_pkg("_scan_ops").model_render(t(src), t(pose), sensor=_sensor(beam))
     torch.cuda.synchronize()
     return xyz.cpu().numpy(), idx.cpu().numpy()
 
@@ -66,7 +66,7 @@ def _cloud_images(H, W, n=4000, seed=11):
 
 def test_identity_returns_the_image_bit_for_bit():
     H, W = 16, 128
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     own = torch.arange(H * W, dtype=torch.int32, device=DEV).reshape(1, H, W)
     f1, _f2 = R.scene(1, H, W, seed=21)
     for name, images in (("input stage", _cloud_images(H, W)), ("scene", t(f1))):
@@ -114,7 +114,7 @@ def test_decisions_by_hand(bad_q):
 
 
 def test_two_calls_and_a_graph_replay_agree_bit_for_bit():
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     src, pose, _c, _beam, _want = M.rendered_case(0)
     src_d, pose_d = t(src), t(pose)
     a, b = ops.model_render(src_d, pose_d), ops.model_render(src_d, pose_d)
@@ -186,7 +186,7 @@ def _same_result(a, b):
 def test_tracker_on_the_box_scene():
     """Six half-empty scans of the box, PoseFit(iters=2), from the true poses rounded to float32.  scans=1 is the pair fit, bit for
     bit; scans=4 is a by-hand render + fit over the same ring, and from the third step on it has the terms the pair fit lacks."""
-    ops, S, L, lm = load_pkg("_ops"), load_pkg("sensor"), load_pkg("_lib"), load_pkg("local_model")
+    ops, S, L, lm = load_pkg("_scan_ops"), load_pkg("sensor"), load_pkg("_lib"), load_pkg("local_model")
     fit = S.PoseFit(iters=2, **R.FIT)
     H, W = M.BOX_H, M.BOX_W
     pairs = [(t(x1[None]), t(x2[None]), t(p[None])) for x1, x2, p in M.box_pairs()]

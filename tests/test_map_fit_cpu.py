@@ -1,5 +1,5 @@
 """CPU: the float64 statement of the scan-to-map fit (tests/map_fit_reference.py) against cases made by hand and against finite
-differences of its own residual, the MapFit value, the host's refusals of _ops.map_fit (before the library is touched) and the cases
+differences of its own residual, the MapFit value, the host's refusals of _scan_ops.map_fit (before the library is touched) and the cases
 tests/test_map_fit_gpu.py runs the kernel on: the share of points the vetting removes, the terms every case gives, the convergence
 the polish test relies on and the small synthetic drive."""
 import math
@@ -38,7 +38,7 @@ def test_map_fit_is_a_validated_frozen_value():
 
 
 def test_the_host_refuses_before_the_library_is_touched():
-    ops, S, L = load_pkg("_ops"), load_pkg("sensor"), load_pkg("_lib")
+    ops, S, L = load_pkg("_scan_ops"), load_pkg("sensor"), load_pkg("_lib")
     spec = S.VoxelMap(voxel=0.5, log2_capacity=10)
     keys, acc = torch.full((1024,), -1, dtype=torch.int64), torch.zeros((1024, 4), dtype=torch.int64)
     x, pose = torch.zeros((2, 4, 8, 3)), torch.zeros((2, 7), dtype=torch.float64)

@@ -1,5 +1,5 @@
 """CPU: the numpy restatement of elo_map_merge (tests/map_merge_reference.py) against hand-worked rows, and everything about the
-merge that needs no GPU: sensor.MapWindow, the refusals of _ops.map_merge, the state file, the ABI and the argument block."""
+merge that needs no GPU: sensor.MapWindow, the refusals of _scan_ops.map_merge, the state file, the ABI and the argument block."""
 import ctypes
 import math
 import os
@@ -114,7 +114,7 @@ def test_map_window_is_a_validated_frozen_value():
 
 
 def test_host_refusals_come_before_the_library(monkeypatch):
-    ops, L, S = load_pkg("_ops"), load_pkg("_lib"), load_pkg("sensor")
+    ops, L, S = load_pkg("_scan_ops"), load_pkg("_lib"), load_pkg("sensor")
 
     def no_library():
         raise AssertionError("the library was touched")

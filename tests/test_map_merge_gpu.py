@@ -471,7 +471,7 @@ def test_run_sequence_with_a_window_writes_a_state_that_loads(tmp_path):
 
 
 def test_refusals_launch_nothing():
-    L, ops = load_pkg("_lib"), load_pkg("_ops")
+    L, ops = load_pkg("_lib"), load_pkg("_scan_ops")
     xyz, pose, _share = M.exact_case(1)
     wm = new_map(0.5, 10)
     wm.insert(dev(xyz), dev(pose))

@@ -1,5 +1,5 @@
 """CPU: the numpy restatement of the place-recognition rule (tests/place_reference.py) against hand-worked cases, and everything
-about it that needs no GPU: sensor.ScanContext and sensor.Places, the refusals of _ops.scan_descriptor and _ops.descriptor_search,
+about it that needs no GPU: sensor.ScanContext and sensor.Places, the refusals of _scan_ops.scan_descriptor and _scan_ops.descriptor_search,
 the argument blocks against a C compiler, the index's state file, and the gap condition of the case table the GPU file compares
 exactly (tests/place_cases.py)."""
 import ctypes
@@ -175,7 +175,7 @@ def test_scan_context_and_places_are_validated_frozen_values():
 
 
 def test_host_refusals_come_before_the_library(monkeypatch):
-    ops, L, S = load_pkg("_ops"), load_pkg("_lib"), load_pkg("sensor")
+    ops, L, S = load_pkg("_scan_ops"), load_pkg("_lib"), load_pkg("sensor")
 
     def no_library():
         raise AssertionError("the library was touched")

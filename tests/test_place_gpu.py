@@ -28,7 +28,7 @@ def ctx_of(kw):
 
 
 def describe(xyz, kw):
-    return load_pkg("_ops").scan_descriptor(dev(xyz), ctx_of(kw)).cpu().numpy()
+    return load_pkg("_scan_ops").scan_descriptor(dev(xyz), ctx_of(kw)).cpu().numpy()
 
 
 def close(got, want):
@@ -87,7 +87,7 @@ def test_descriptor_matches_the_reference_exactly(i):
 
 
 def test_descriptor_placed_cases():
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     x, kw, want = C.placed()
     assert np.array_equal(describe(x, kw), want) and np.array_equal(R.descriptor(x, **kw), want)
     assert not describe(np.zeros((2, 3, 64, 3), np.float32), C.context(60, 20)).any()      # an image without points
@@ -114,7 +114,7 @@ def test_descriptor_placed_cases():
 
 
 def test_descriptor_two_runs_and_a_graph_replay_agree():
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     xyz, kw = C.cloud(3)
     X, spec = dev(xyz), ctx_of(kw)
     first, again = ops.scan_descriptor(X, spec), ops.scan_descriptor(X, spec)
@@ -125,7 +125,7 @@ def test_descriptor_two_runs_and_a_graph_replay_agree():
 
 @pytest.mark.parametrize("name", sorted(C.SEARCH))
 def test_search_matches_the_reference(name):
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     query, db, m, k, _tie, kw, ref = C.search_case(name)
     res = ops.descriptor_search(dev(query), dev(db), m, ctx_of(kw), k)
     assert tuple(res.entry.shape) == (len(query), k) and tuple(res.best_dist.shape) == (len(query), m)
@@ -133,7 +133,7 @@ def test_search_matches_the_reference(name):
 
 
 def test_search_planted_cases():
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     rng = np.random.default_rng(21)
     kw = C.context(60, 20)
     spec = ctx_of(kw)
@@ -188,7 +188,7 @@ def test_search_planted_cases():
 
 
 def test_search_two_runs_and_a_graph_replay_agree():
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     for name in ("m65_s64_r32", "m257_s60", "m0_n3_k8"):
         query, db, m, k, _tie, kw, ref = C.search_case(name)
         Q, D, spec = dev(query), dev(db), ctx_of(kw)
@@ -206,7 +206,7 @@ def test_search_two_runs_and_a_graph_replay_agree():
 
 
 def test_refusals_launch_nothing():
-    ops, L, S = load_pkg("_ops"), load_pkg("_lib"), load_pkg("sensor")
+    ops, L, S = load_pkg("_scan_ops"), load_pkg("_lib"), load_pkg("sensor")
     spec = S.ScanContext(4, 8)
     out = torch.full((1, 8, 4), 7, dtype=torch.uint16, device=DEV)
     with pytest.raises(L.EloError):
@@ -239,7 +239,7 @@ def _e2e_index(capacity=8):
 
 
 def test_index_add_and_query_are_the_two_ops():
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     index, e = _e2e_index()
     spec = index.spec
     assert len(index) == 6 and np.array_equal(index.desc[:6].cpu().numpy(), e["db"]) and index.scan[:6].tolist() == [0, 10, 20, 30, 40, 50]
@@ -296,7 +296,7 @@ def _drive(places, fit=None):
 
 
 def test_world_map_logs_its_lookups_and_the_index_only_reads():
-    ops, S = load_pkg("_ops"), load_pkg("sensor")
+    ops, S = load_pkg("_scan_ops"), load_pkg("sensor")
     spec = ctx_of(C.E2E_CONTEXT)
     places = S.Places(spec, every=2, skip_recent=1, capacity=8)
     wm, scans = _drive(places)

@@ -1,5 +1,5 @@
 """CPU: the float64 statement of the pose fit (tests/pose_fit_reference.py) against closed forms, the PoseFit value, the host's
-refusals of _ops.pose_fit (before the library is touched) and the scenes tests/test_pose_fit_gpu.py runs the kernel on: the share
+refusals of _scan_ops.pose_fit (before the library is touched) and the scenes tests/test_pose_fit_gpu.py runs the kernel on: the share
 of points the decision-margin filter removes, and the convergence the polish test relies on."""
 import math
 
@@ -103,7 +103,7 @@ def test_pose_fit_value():
 
 
 def test_host_refusals_come_before_the_library(monkeypatch):
-    ops, L, S = load_pkg("_ops"), load_pkg("_lib"), load_pkg("sensor")
+    ops, L, S = load_pkg("_scan_ops"), load_pkg("_lib"), load_pkg("sensor")
 
     def no_library():
         raise AssertionError("the library was touched")

@@ -54,7 +54,7 @@ def _case(i):
 
 
 def _run(x1, x2, poses, beam=None, **kw):
-    ops, S = load_pkg("_ops"), load_pkg("sensor")
+    ops, S = load_pkg("_scan_ops"), load_pkg("sensor")
     sensor = None if beam is None else S.Sensor(beam_elevations_deg=R.BEAMS_DEG)
     res = ops.pose_fit(t(x1), t(x2), t(poses), _fit(**kw), sensor=sensor)
     torch.cuda.synchronize()
@@ -201,7 +201,7 @@ def test_abi_refusals_launch_nothing():
 
 def test_through_the_net_eager_and_replayed():
     """tests/pose_fit_net_replay.py in a child process (its captures take streams from the process-wide pool and bind hardware
-    queues, which in this process would move the lanes of every later test of the suite): forward(fit=) against _ops.pose_fit,
+    queues, which in this process would move the lanes of every later test of the suite): forward(fit=) against _scan_ops.pose_fit,
     capture(fit=) + submit + lane_fit against the eager result, a plain graph replay of the entry against its eager call,
     capture(fit=None) against today's outputs, the sequence evaluation's fit file."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "pose_fit_net_replay.py")], cwd=ROOT, capture_output=True, text=True,

@@ -260,7 +260,7 @@ def test_extract_reports_all_and_writes_no_more_than_asked():
         where = np.searchsorted(want["key"], key[:rows])
         assert np.array_equal(want["key"][where], key[:rows]) and np.array_equal(want["acc"][where, 0], count[:rows])
         assert same_bits(cen[:rows], want["xyz"][where])
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     key, count, cen, n = ops.map_extract(wm.keys, wm.acc, wm.spec, 10)
     assert int(n.item()) == m and key.shape == (10,) and count.shape == (10,) and cen.shape == (10, 3)
 
@@ -294,7 +294,7 @@ def test_refusals_launch_nothing():
     for was, now in zip(before, (wm.keys, wm.acc, wm.stat_words)):
         assert torch.equal(was, now)
     # the host's own refusals: types, shapes, devices
-    ops = load_pkg("_ops")
+    ops = load_pkg("_scan_ops")
     for call in (lambda: ops.map_insert(wm.keys, wm.acc, wm.stat_words, X, P.float(), wm.spec),
                  lambda: ops.map_insert(wm.keys, wm.acc, wm.stat_words, X.double(), P, wm.spec),
                  lambda: ops.map_insert(wm.keys, wm.acc, wm.stat_words, X, P, "spec")):

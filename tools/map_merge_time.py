@@ -32,7 +32,7 @@ args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("this measurement needs the GPU")
 dev = torch.device("cuda:0")
-ops, synth, sensor, world_map = pkg("_ops"), pkg("synth"), pkg("sensor"), pkg("world_map")
+ops, synth, sensor, world_map = pkg("_scan_ops"), pkg("synth"), pkg("sensor"), pkg("world_map")
 H, W = 64, 1800
 lines = []
 

@@ -30,7 +30,7 @@ args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("this measurement needs the GPU")
 dev = torch.device("cuda:0")
-ops, synth = pkg("_ops"), pkg("synth")
+ops, synth = pkg("_scan_ops"), pkg("synth")
 H, W = 64, 1800
 FLOOR_US, CEILING = 4.7, 0.81 * 8e12
 lines = []

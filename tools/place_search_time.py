@@ -28,7 +28,7 @@ args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("this measurement needs the GPU")
 dev = torch.device("cuda:0")
-ops, synth, sensor, world_map, model = pkg("_ops"), pkg("synth"), pkg("sensor"), pkg("world_map"), pkg("model")
+ops, synth, sensor, world_map, model = pkg("_scan_ops"), pkg("synth"), pkg("sensor"), pkg("world_map"), pkg("model")
 H, W = 64, 1800
 lines = []
 

@@ -30,7 +30,7 @@ args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("this measurement needs the GPU")
 dev = torch.device("cuda:0")
-ops, S, synth, model = pkg("_ops"), pkg("sensor"), pkg("synth"), pkg("model")
+ops, S, synth, model = pkg("_scan_ops"), pkg("sensor"), pkg("synth"), pkg("model")
 H, W = 64, 1800
 FLOOR_US = 4.7
 lines = []
@@ -119,7 +119,7 @@ def torch_evaluation(x1, x2, pose, fit, consts):
 
 say("elo_pose_fit on %dx%d range images, %d alternating blocks, median block (min .. max), us per call; a dependent launch costs "
     "~%.1f us on this machine (DESIGN.md)" % (H, W, args.rounds, FLOOR_US))
-consts = ops.projection_constants(H, W)
+consts = S.projection_constants(H, W)
 guess = np.array([math.cos(0.005), 0, 0, -math.sin(0.005), -0.8, 0, 0], np.float32)
 for B in args.batch:
     f1, f2 = synth.frame_pair(B, H, W, seed=4)
