@@ -78,9 +78,18 @@ def zero_cell(H, W, az_res):
     return (H - 1) * W + min(int(np.float32(np.pi) / np.float32(az_res)), W - 1)
 
 
+def zero_cells(pts, H, W, az_res):
+    """The cells the zero points among pts (M,3) fall in: row H-1 (by the formula's NaN -> 0 conversion, and by the beam table's
+    clamp), the column by atan2 of their signed zeros -- +-0: zero_cell's; pi (x = -0, y = +0): column 0; -pi: column W-1."""
+    dead = pts[(pts == 0).all(-1)]
+    at = np.arctan2(dead[:, 1], dead[:, 0])
+    col = np.where(at > 1.0, 0, np.where(at < -1.0, W - 1, zero_cell(H, W, az_res) - (H - 1) * W))
+    return np.unique((H - 1) * W + col)
+
+
 def project(pts, H, W, az_res, row_of):
     """float64 (M,3) points of ONE image -> (image (H,W,3) = the sum of the points of minimum range per cell, how many were summed
-    (H,W)).  Zero points (+0, +0, +0 here) win their cell and blank it."""
+    (H,W)).  Zero points win their cell (zero_cells: by their signs) and blank it."""
     x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
     r = np.sqrt(x * x + y * y + z * z)
     live = r > 0
@@ -95,7 +104,8 @@ def project(pts, H, W, az_res, row_of):
     np.add.at(img, cell[win], pts[win])
     np.add.at(count, cell[win], 1)
     if not live.all():
-        img[zero_cell(H, W, az_res)], count[zero_cell(H, W, az_res)] = 0.0, 0
+        blank = zero_cells(pts, H, W, az_res)
+        img[blank], count[blank] = 0.0, 0
     return img.reshape(H, W, 3), count.reshape(H, W)
 
 

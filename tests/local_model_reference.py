@@ -118,14 +118,21 @@ def yaw_pose(angle, t):
 
 
 def render_case(i):
-    """(src (B,K,H,W,3) float32, pose (B,K,7) float32, consts, beam table (radians, float32) or None) of case i: every source an
-    R.scene image (a beam-table sensor's frame with the table) of its own seed, carried by a small motion (<= 1 m, <= 3 degrees,
-    about a tilted axis); the LAST source of every batch element is turned by about 180 degrees, so its points cross the seam.
+    """(src (B,K,H,W,3) float32, pose (B,K,7) float32, consts, beam table (radians, float32) or None) of case i: render_inputs at
+    CASES[i], with pose_fit_reference.BEAMS_DEG where the case has a beam table."""
+    B, K, H, W, beams = CASES[i]
+    return render_inputs(B, K, H, W, R.BEAMS_DEG if beams else None, i)
+
+
+def render_inputs(B, K, H, W, beam_deg, i):
+    """(src (B,K,H,W,3) float32, pose (B,K,7) float32, consts, beam table (radians, float32) or None); i numbers the draw: every
+    source an R.scene image (with beam_deg, a table in degrees: a frame of that beam-table sensor) of its own seed, carried by a
+    small motion (<= 1 m, <= 3 degrees, about a tilted axis); the LAST source of every batch element is turned by about 180
+    degrees, so its points cross the seam.
     The sources are SPARSE, about 1.5 / K of their cells filled (the scans a local model is for): every contributing point within
     MARGIN of a border marks two cells, 4 MARGIN of the points are that near, so the ambiguous share is about 0.8 % per point that
     reaches a cell -- 1.5 points per cell keep it under DROP_CAP, and still most filled cells are contested by two sources."""
     from conftest import load_pkg
-    B, K, H, W, beams = CASES[i]
     holes = max(0.05, 1.0 - 1.5 / K)
     rng = np.random.default_rng(100 + i)
     src = np.zeros((B, K, H, W, 3), np.float32)
@@ -133,9 +140,9 @@ def render_case(i):
     for b in range(B):
         for k in range(K):
             seed = 7 + 10 * i + 2 * (b * K + k)
-            if beams:
+            if beam_deg is not None:
                 f1, _f2 = load_pkg("synth").frame_pair(1, H, W, seed=seed, hole_rate=holes,
-                                                       sensor=load_pkg("sensor").Sensor(beam_elevations_deg=R.BEAMS_DEG))
+                                                       sensor=load_pkg("sensor").Sensor(beam_elevations_deg=beam_deg))
             else:
                 f1, _f2 = R.scene(1, H, W, seed=seed, hole_rate=holes)
             src[b, k] = f1[0]
@@ -147,9 +154,9 @@ def render_case(i):
             if k == K - 1 and K > 1:
                 q = R.qmul(yaw_pose(math.pi - 0.01 * (b + 1), (0, 0, 0))[:4], q)
             pose[b, k] = np.concatenate([q * rng.uniform(0.5, 2.0), t])         # (the kernel normalises q)
-    consts = R.constants(H, W, R.BEAMS_DEG[0], R.BEAMS_DEG[-1]) if beams else R.constants(H, W)
-    beam = (np.asarray(R.BEAMS_DEG, np.float64) * (math.pi / 180)).astype(np.float32) if beams else None
-    return src, pose, consts, beam
+    if beam_deg is None:
+        return src, pose, R.constants(H, W), None
+    return src, pose, R.constants(H, W, beam_deg[0], beam_deg[-1]), (np.asarray(beam_deg, np.float64) * (math.pi / 180)).astype(np.float32)
 
 
 @functools.lru_cache(maxsize=None)
