@@ -484,9 +484,6 @@ __global__ __launch_bounds__(ELO_BLOCK) void warp_project_bwd_kernel(const elo_w
     }
 }
 
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
 unsigned grid_for(long items, unsigned cap = 8192)
 {
     const long g = (items + ELO_BLOCK - 1) / ELO_BLOCK;

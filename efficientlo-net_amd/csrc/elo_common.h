@@ -20,6 +20,25 @@ int check_launch(const char *what);
 elo_tuning &tuning();           // the process-wide tuning (elo_set_tuning); the library reads no environment variable
 elo_tuning &tuning_base();      // ... without the elo_debug_* overrides
 
+// ---- host: the entry points' refusals ------------------------------------
+#define ELO_REQUIRE(cond, who, what) \
+    do { if (!(cond)) return ::elo::fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
+
+// a batch of (H,W) images whose cells, one image's and all of them, fit 32-bit indexing
+inline bool image_sizes_ok(int batch, int H, int W, int min_H, int max_batch = 0x7fffffff)
+{
+    return batch >= 0 && H >= min_H && W >= 1 && (long)H * W <= (1l << 31) - 1 && (long)batch * H * W <= (1l << 31) - 1 && batch <= max_batch;
+}
+template <class T>
+inline bool positive_finite(T v) { return v > T(0) && v - v == T(0); }
+inline bool aligned(const void *p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }      // bytes: a power of two; NULL is
+// [p, p + pb) and [q, q + qb) meet; an EMPTY range meets whatever its address lies strictly inside (callers that want otherwise guard)
+inline bool ranges_meet(const void *p, size_t pb, const void *q, size_t qb)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qb && b < a + pb;
+}
+
 // ---- device: arithmetic contract -----------------------------------------
 // Squared norms are ((x*x + y*y) + z*z) in fp32 with no fused multiply-add, so
 // that the GPU result equals the CPU oracle bit for bit (DESIGN.md "numerics").
@@ -182,6 +201,24 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v)
     v = dpp_add_step<0x142>(v);    // row_bcast:15
     v = dpp_add_step<0x143>(v);    // row_bcast:31
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// wave-wide fp32 sum in the fixed order of the same steps; every lane returns lane 63's total
+template <int CTRL>
+__device__ __forceinline__ float dpp_fadd_step(float v)
+{
+    return __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)));
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v)
+{
+    v = dpp_fadd_step<0xb1>(v);     // quad_perm:[1,0,3,2]
+    v = dpp_fadd_step<0x4e>(v);     // quad_perm:[2,3,0,1]
+    v = dpp_fadd_step<0x114>(v);    // row_shr:4
+    v = dpp_fadd_step<0x118>(v);    // row_shr:8
+    v = dpp_fadd_step<0x142>(v);    // row_bcast:15
+    v = dpp_fadd_step<0x143>(v);    // row_bcast:31
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
 // lexicographic (hi, lo) minimum over the wave, as one u64 key

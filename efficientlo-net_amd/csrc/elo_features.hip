@@ -1332,9 +1332,6 @@ __global__ __launch_bounds__(ELO_BLOCK) void scatter_min_kernel(const elo_warp_p
     }
 }
 
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
 }  // namespace
 }  // namespace elo
 

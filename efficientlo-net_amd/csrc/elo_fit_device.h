@@ -1,10 +1,11 @@
 // elo_fit_device.h -- what the point-to-plane fits share (elo_pose_fit, elo_posefit.hip; elo_map_fit, elo_mapfit.hip): the normal of a
 // range-image cell, the float32 sums of a term in their fixed order (thread, wave by DPP, workgroup through LDS, one partial row per
-// workgroup), and the solve launch -- the partial rows added in double, the 6x6 Cholesky, the update of the pose or the report.  The two
-// fits differ in how a term's point finds its target (an evaluation kernel each) and in the pose they move: a float32 row about the
-// origin of frame 2 (FitPoseRel), or a double row about the sensor's own position (FitPoseWorld).
+// workgroup), the solve launch -- the partial rows added in double, the 6x6 Cholesky, the update of the pose or the report -- and the
+// host's loop over the two (fit_run) with the size of its scratch.  The two fits differ in how a term's point finds its target (an
+// evaluation kernel each) and in the pose they move: a float32 row about the origin of frame 2 (FitPoseRel), or a double row about the
+// sensor's own position (FitPoseWorld).  Pose rows, R(q) and the carried point: elo_pose_device.h.
 #pragma once
-#include "elo_common.h"
+#include "elo_pose_device.h"
 
 namespace elo {
 namespace {
@@ -15,52 +16,21 @@ constexpr int FIT_ROW = 32;                         // words of a partial row: F
 constexpr int FIT_SOLVE_BLOCK = 256;                // FIT_ROW columns x FIT_SOLVE_LANES partial rows in flight
 constexpr int FIT_SOLVE_LANES = FIT_SOLVE_BLOCK / FIT_ROW;
 
-// wave-wide fp32 sum in the fixed order of the DPP reduction (wave_sum_u32's steps); every lane returns lane 63's total
-template <int CTRL>
-__device__ __forceinline__ float dpp_fadd_step(float v)
+// The normal of cell (h,w) of the (H,W,3) image x, whose point is P2, between its neighbours l / r (columns, wrapped at the seam)
+// and u / d (rows): false in the edge rows, where the cell or a neighbour is empty, a neighbour's range jumps or the cross product
+// has no length.  n: unit, towards the sensor.
+__device__ __forceinline__ bool fit_normal(const float *x, const int h, const int w, const int H, const int W, const double jump_rel,
+                                           double (&P2)[3], double (&n)[3])
 {
-    return __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)));
-}
-
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-    v = dpp_fadd_step<0xb1>(v);     // quad_perm:[1,0,3,2]
-    v = dpp_fadd_step<0x4e>(v);     // quad_perm:[2,3,0,1]
-    v = dpp_fadd_step<0x114>(v);    // row_shr:4
-    v = dpp_fadd_step<0x118>(v);    // row_shr:8
-    v = dpp_fadd_step<0x142>(v);    // row_bcast:15
-    v = dpp_fadd_step<0x143>(v);    // row_bcast:31
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-// R(q) of a normalised quaternion, as every kernel that carries points writes it
-__device__ __forceinline__ void fit_rotation(double q0, double q1, double q2, double q3, double (&R)[9])
-{
-    R[0] = 1.0 - 2.0 * (q2 * q2 + q3 * q3); R[1] = 2.0 * (q1 * q2 - q0 * q3);       R[2] = 2.0 * (q1 * q3 + q0 * q2);
-    R[3] = 2.0 * (q1 * q2 + q0 * q3);       R[4] = 1.0 - 2.0 * (q1 * q1 + q3 * q3); R[5] = 2.0 * (q2 * q3 - q0 * q1);
-    R[6] = 2.0 * (q1 * q3 - q0 * q2);       R[7] = 2.0 * (q2 * q3 + q0 * q1);       R[8] = 1.0 - 2.0 * (q1 * q1 + q2 * q2);
-}
-
-// R(q), q normalised here, in double from the row's floats (a zero quaternion: the identity)
-__device__ __forceinline__ void pose_double(const float *row, double (&R)[9], double (&t)[3], double (&q)[4])
-{
-    double q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
-    const double n = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    if (n > 0.0 && n - n == 0.0) { q0 /= n; q1 /= n; q2 /= n; q3 /= n; } else { q0 = 1.0; q1 = q2 = q3 = 0.0; }
-    q[0] = q0; q[1] = q1; q[2] = q2; q[3] = q3;
-    fit_rotation(q0, q1, q2, q3, R);
-    t[0] = row[4]; t[1] = row[5]; t[2] = row[6];
-}
-
-// The normal of the cell whose point is c, between its neighbours l / r (columns, wrapped by the caller) and u / d (rows): false
-// where the cell or a neighbour is empty, a neighbour's range jumps or the cross product has no length.  n: unit, towards the sensor.
-__device__ __forceinline__ bool fit_normal(const float *c, const float *l, const float *r, const float *u, const float *d,
-                                           const double jump_rel, double (&P2)[3], double (&n)[3])
-{
+    if (h == 0 || h == H - 1) return false;
+    const int wl = w == 0 ? W - 1 : w - 1, wr = w == W - 1 ? 0 : w + 1;
+    const int m = h * W + w;                                            // (H * W fits an int: fit_sizes_ok)
+    const float *c = x + (long)m * 3, *l = x + ((long)h * W + wl) * 3, *r = x + ((long)h * W + wr) * 3;
+    const float *u = x + (long)(m - W) * 3, *d = x + (long)(m + W) * 3;
     P2[0] = c[0]; P2[1] = c[1]; P2[2] = c[2];
     const double L[3] = {l[0], l[1], l[2]}, Rt[3] = {r[0], r[1], r[2]};
     const double U[3] = {u[0], u[1], u[2]}, D[3] = {d[0], d[1], d[2]};
-    auto empty = [](const double (&v)[3]) { return v[0] == 0.0 && v[1] == 0.0 && v[2] == 0.0; };
+    auto empty = [](const double (&v)[3]) { return cell_empty(v[0], v[1], v[2]); };
     if (empty(P2) || empty(L) || empty(Rt) || empty(U) || empty(D)) return false;
     auto range = [](const double (&v)[3]) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
     const double r2 = range(P2), jump = jump_rel * r2;
@@ -151,12 +121,7 @@ __device__ inline bool solve6(double (&M)[6][6], const double (&g)[6], double (&
 struct FitPoseRel {
     typedef float scalar;
     static constexpr bool about_sensor = false;
-    static __device__ __forceinline__ bool load(const float *row, double (&t)[3], double (&q)[4])
-    {
-        double R[9];
-        pose_double(row, R, t, q);
-        return true;
-    }
+    static __device__ __forceinline__ bool load(const float *row, double (&t)[3], double (&q)[4]) { return pose_row_or_identity(row, q, t), true; }
     static __device__ __forceinline__ bool finite(double v) { return (float)v - (float)v == 0.0f; }
 };
 
@@ -165,9 +130,7 @@ struct FitPoseWorld {
     static constexpr bool about_sensor = true;
     static __device__ __forceinline__ bool load(const double *row, double (&t)[3], double (&q)[4])
     {
-        const double n = sqrt(row[0] * row[0] + row[1] * row[1] + row[2] * row[2] + row[3] * row[3]);
-        if (!(n > 0.0) || n - n != 0.0) return false;
-        for (int i = 0; i < 4; ++i) q[i] = row[i] / n;
+        if (!pose_quaternion(row, q)) return false;
         for (int i = 0; i < 3; ++i) t[i] = row[4 + i];
         return true;
     }
@@ -288,9 +251,34 @@ __global__ __launch_bounds__(FIT_SOLVE_BLOCK) void fit_solve_kernel(const FitSol
     a.status[b] = status;
 }
 
-inline bool fit_sizes_ok(int batch, int H, int W)
+// ---- host: what elo_pose_fit and elo_map_fit share around their evaluation launch
+inline bool fit_sizes_ok(int batch, int H, int W) { return image_sizes_ok(batch, H, W, 3, 65535); }
+
+// partial rows per image, one per workgroup of `tile` cells; -1: sizes no fit takes
+inline int fit_parts(int H, int W, int tile) { return fit_sizes_ok(1, H, W) ? (int)(((long)H * W + tile - 1) / tile) : -1; }
+
+// words of [partial rows (batch, parts, FIT_ROW) | status (batch)]
+inline long fit_scratch_words(int batch, int H, int W, int tile)
 {
-    return batch >= 0 && H >= 3 && W >= 1 && (long)H * W <= (1l << 31) - 1 && (long)batch * H * W <= (1l << 31) - 1 && batch <= 65535;
+    return fit_sizes_ok(batch, H, W) ? (long)batch * fit_parts(H, W, tile) * FIT_ROW + batch : -1;
+}
+
+// The launches of a fit on a checked, non-empty argument block (elo_pose_fit_args or elo_map_fit_args: the fields named here are
+// in both): evaluate at pose_in, solve into pose_out, evaluate there, ... -- iters steps, then one evaluation more that only reports.
+// eval(pose): launches the evaluation of all images at the (batch,7) rows `pose`, partial rows to a->scratch.
+template <class Pose, class Args, class Eval>
+int fit_run(const Args *a, const int parts, hipStream_t s, const char *who, Eval eval)
+{
+    FitSolve<Pose> so = {parts, a->scratch, a->scratch + (long)a->batch * parts * FIT_ROW, a->pose_in, a->pose_in, a->pose_out,
+                         a->info, a->grad, a->stats, a->min_count, (double)a->damping, 1, 0};
+    for (int it = 0; it <= a->iters; ++it) {
+        so.pose = it == 0 ? a->pose_in : a->pose_out;
+        eval(so.pose);
+        so.first = it == 0;
+        so.report = it == a->iters;
+        hipLaunchKernelGGL(fit_solve_kernel<Pose>, dim3((unsigned)a->batch), dim3(FIT_SOLVE_BLOCK), 0, s, so);
+    }
+    return check_launch(who);
 }
 
 }  // namespace

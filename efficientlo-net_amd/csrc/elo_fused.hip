@@ -2824,9 +2824,6 @@ int check_group(const elo_group_spec &g, int H2, int W2, size_t lds_bytes, const
     return ELO_OK;
 }
 
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
 }  // namespace
 }  // namespace elo
 

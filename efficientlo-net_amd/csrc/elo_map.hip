@@ -39,13 +39,12 @@ enum { MAP_NONE = 0, MAP_FILTERED = 1, MAP_REJECTED = 2, MAP_POINT = 3 };
 __device__ __forceinline__ int map_point(const MapInsert &a, const double (&R)[9], const double (&t)[3], float ax, float ay, float az,
                                          unsigned long long &key, unsigned (&g)[3])
 {
-    if (map_cell_empty(ax, ay, az)) return MAP_NONE;
+    if (cell_empty(ax, ay, az)) return MAP_NONE;
     const float rf = sqrtf(ax * ax + ay * ay + az * az);
     if (rf < a.min_range || rf > a.max_range) return MAP_FILTERED;
-    const float x = (float)(R[0] * ax + R[1] * ay + R[2] * az + t[0]);
-    const float y = (float)(R[3] * ax + R[4] * ay + R[5] * az + t[1]);
-    const float z = (float)(R[6] * ax + R[7] * ay + R[8] * az + t[2]);
-    if (!map_point_finite(x, y, z)) return MAP_REJECTED;
+    float x, y, z;
+    pose_carry_f32(R, t, ax, ay, az, x, y, z);
+    if (!point_finite(x, y, z)) return MAP_REJECTED;
     const double voxel = (double)a.voxel;
     unsigned long long fx, fy, fz;
     if (!map_axis(x, voxel, fx, g[0]) || !map_axis(y, voxel, fy, g[1]) || !map_axis(z, voxel, fz, g[2])) return MAP_REJECTED;
@@ -63,7 +62,7 @@ __global__ __launch_bounds__(ELO_BLOCK) void map_insert_kernel(const MapInsert a
 {
     const unsigned b = blockIdx.x / a.tiles, tile = blockIdx.x - b * a.tiles;
     double R[9], t[3];
-    if (!map_pose(a.pose + (long)b * 7, R, t)) return;                                  // the whole scan, by the whole workgroup
+    if (!pose_load(a.pose + (long)b * 7, R, t)) return;                                 // the whole scan, by the whole workgroup
     const long cells = (long)a.H * a.W;
     const long i0 = ((long)tile * ELO_BLOCK + threadIdx.x) * MAP_STRIP;
     float v[3 * MAP_STRIP];
@@ -301,16 +300,6 @@ __global__ __launch_bounds__(ELO_BLOCK) void map_merge_kernel(const MapMerge a)
     }
 }
 
-// [p, p + pb) and [q, q + qb) share a byte
-inline bool map_ranges_meet(const void *p, unsigned long long pb, const void *q, unsigned long long qb)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return pb != 0ull && qb != 0ull && a < b + qb && b < a + pb;
-}
-
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
 }  // namespace
 }  // namespace elo
 
@@ -321,18 +310,18 @@ extern "C" int elo_map_insert(const elo_map_insert_args *a, elo_stream_t stream)
     const char *who = "elo_map_insert";
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->batch >= 0 && a->H >= 1 && a->W >= 1, who, "bad sizes");
-    ELO_REQUIRE((long)a->H * a->W <= (1l << 31) - 1 && (long)a->batch * a->H * a->W <= (1l << 31) - 1, who, "batch * H * W beyond 2^31");
+    ELO_REQUIRE(image_sizes_ok(a->batch, a->H, a->W, 1), who, "batch * H * W beyond 2^31");
     ELO_REQUIRE(map_table_ok(a->voxel, a->log2_capacity), who, "voxel is positive and finite, log2_capacity ELO_MAP_MIN_LOG2 .. ELO_MAP_MAX_LOG2");
     ELO_REQUIRE(a->min_range >= 0.0f, who, "min_range is >= 0");
     ELO_REQUIRE(a->max_range > a->min_range, who, "max_range lies above min_range");
     ELO_REQUIRE(a->xyz && a->pose && a->keys && a->acc && a->stats, who, "null pointer");
-    ELO_REQUIRE(aligned8(a->pose) && aligned8(a->keys) && aligned8(a->acc) && aligned8(a->stats), who,
+    ELO_REQUIRE(aligned(a->pose, 8) && aligned(a->keys, 8) && aligned(a->acc, 8) && aligned(a->stats, 8), who,
                 "pose, keys, acc and stats must be 8-byte aligned");
     if (a->batch == 0) return ELO_OK;
     const long cells = (long)a->H * a->W;
     const unsigned tiles = (unsigned)((cells + MAP_TILE - 1) / MAP_TILE);
     const MapInsert m = {a->H, a->W, a->voxel, a->min_range, a->max_range, (1ull << a->log2_capacity) - 1ull, a->xyz, a->pose, a->keys,
-                         a->acc, a->stats, tiles, (cells % MAP_STRIP == 0 && ((uintptr_t)a->xyz & 15) == 0) ? 1 : 0};
+                         a->acc, a->stats, tiles, (cells % MAP_STRIP == 0 && aligned(a->xyz, 16)) ? 1 : 0};
     const dim3 grid(tiles * (unsigned)a->batch);                        // < 2^21: batch * H * W < 2^31, 1024 cells a tile
     hipLaunchKernelGGL(map_insert_kernel, grid, dim3(ELO_BLOCK), 0, (hipStream_t)stream, m);
     return check_launch(who);
@@ -345,7 +334,7 @@ extern "C" int elo_map_extract(const elo_map_extract_args *a, elo_stream_t strea
     ELO_REQUIRE(map_table_ok(a->voxel, a->log2_capacity), who, "voxel is positive and finite, log2_capacity ELO_MAP_MIN_LOG2 .. ELO_MAP_MAX_LOG2");
     ELO_REQUIRE(a->max_out >= 0, who, "max_out is >= 0");
     ELO_REQUIRE(a->keys && a->acc && a->out_key && a->out_count && a->out_xyz && a->cursor, who, "null pointer");
-    ELO_REQUIRE(aligned8(a->keys) && aligned8(a->acc) && aligned8(a->out_key) && aligned8(a->out_count) && aligned8(a->cursor), who,
+    ELO_REQUIRE(aligned(a->keys, 8) && aligned(a->acc, 8) && aligned(a->out_key, 8) && aligned(a->out_count, 8) && aligned(a->cursor, 8), who,
                 "keys, acc, out_key, out_count and cursor must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const unsigned long long slots = 1ull << a->log2_capacity;
@@ -362,18 +351,19 @@ extern "C" int elo_map_merge(const elo_map_merge_args *a, elo_stream_t stream)
     ELO_REQUIRE(a->rows >= 0 && a->rows < (1l << 31), who, "rows is 0 .. 2^31 - 1");
     ELO_REQUIRE(map_table_ok(a->voxel, a->log2_capacity), who, "voxel is positive and finite, log2_capacity ELO_MAP_MIN_LOG2 .. ELO_MAP_MAX_LOG2");
     ELO_REQUIRE(a->min_count >= 1, who, "min_count is >= 1");
-    ELO_REQUIRE(!a->centre || (a->radius > 0.0f && a->radius - a->radius == 0.0f), who, "with a centre, radius is positive and finite");
+    ELO_REQUIRE(!a->centre || positive_finite(a->radius), who, "with a centre, radius is positive and finite");
     ELO_REQUIRE(a->src_keys && a->src_acc && a->keys && a->acc && a->stats && a->report, who, "null pointer");
-    ELO_REQUIRE(aligned8(a->src_keys) && aligned8(a->src_acc) && aligned8(a->keys) && aligned8(a->acc) && aligned8(a->stats) &&
-                aligned8(a->centre) && aligned8(a->report), who, "src_keys, src_acc, keys, acc, stats, centre and report must be 8-byte aligned");
+    ELO_REQUIRE(aligned(a->src_keys, 8) && aligned(a->src_acc, 8) && aligned(a->keys, 8) && aligned(a->acc, 8) && aligned(a->stats, 8) &&
+                aligned(a->centre, 8) && aligned(a->report, 8), who, "src_keys, src_acc, keys, acc, stats, centre and report must be 8-byte aligned");
     const unsigned long long rows = (unsigned long long)a->rows, slots = 1ull << a->log2_capacity;
-    ELO_REQUIRE(!map_ranges_meet(a->src_keys, rows * 8ull, a->keys, slots * 8ull) && !map_ranges_meet(a->src_keys, rows * 8ull, a->acc, slots * 32ull) &&
-                !map_ranges_meet(a->src_acc, rows * 32ull, a->keys, slots * 8ull) && !map_ranges_meet(a->src_acc, rows * 32ull, a->acc, slots * 32ull),
+    ELO_REQUIRE(rows == 0ull ||                                                         // (no row: nothing overlaps, whatever the pointers)
+                (!ranges_meet(a->src_keys, rows * 8ull, a->keys, slots * 8ull) && !ranges_meet(a->src_keys, rows * 8ull, a->acc, slots * 32ull) &&
+                 !ranges_meet(a->src_acc, rows * 32ull, a->keys, slots * 8ull) && !ranges_meet(a->src_acc, rows * 32ull, a->acc, slots * 32ull)),
                 who, "the source rows overlap the destination table");
     if (a->rows == 0) return ELO_OK;
     const MapMerge m = {rows, a->src_keys, a->src_acc, a->voxel, a->radius, slots - 1ull, a->keys, a->acc, a->stats, a->centre,
-                        (unsigned long long)a->min_count, a->report, ((uintptr_t)a->src_keys & 15) == 0 ? 1 : 0,
-                        ((uintptr_t)a->src_acc & 15) == 0 ? 1 : 0};
+                        (unsigned long long)a->min_count, a->report, aligned(a->src_keys, 16) ? 1 : 0,
+                        aligned(a->src_acc, 16) ? 1 : 0};
     const dim3 grid((unsigned)((rows + MERGE_TILE - 1) / MERGE_TILE));                  // < 2^19: rows < 2^31, 4096 rows a workgroup
     hipLaunchKernelGGL(map_merge_kernel, grid, dim3(ELO_BLOCK), 0, (hipStream_t)stream, m);
     return check_launch(who);

@@ -1,33 +1,15 @@
-// elo_map_device.h -- the world map's rules that more than one file states (include/elo.h, WORLD MAP): the pose row, the voxel index
-// of a rounded coordinate, the hash, the probe / claim / add, the centroid.  elo_map.hip writes the table by them (the insert and
-// the merge through the same map_add) and elo_mapfit.hip reads it by them.
+// elo_map_device.h -- the world map's rules that more than one file states (include/elo.h, WORLD MAP): the voxel index of a rounded
+// coordinate, the hash, the probe / claim / add, the centroid.  elo_map.hip writes the table by them (the insert and the merge
+// through the same map_add) and elo_mapfit.hip reads it by them.  The pose row and a cell's validity rule (cell_empty, point_finite)
+// come with elo_pose_device.h, included here.
 #pragma once
-#include "elo_common.h"
+#include "elo_pose_device.h"
 
 namespace elo {
 namespace {
 
 constexpr unsigned long long MAP_EMPTY = ~0ull;
 constexpr double MAP_HALF = 1048576.0;                  // 2^20: indices lie in [-2^20, 2^20)
-
-// model_pose (elo_model.hip) from a double row
-__device__ __forceinline__ bool map_pose(const double *row, double (&R)[9], double (&t)[3])
-{
-    double q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
-    const double n = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    if (!(n > 0.0) || n - n != 0.0) return false;
-    q0 /= n; q1 /= n; q2 /= n; q3 /= n;
-    R[0] = 1.0 - 2.0 * (q2 * q2 + q3 * q3); R[1] = 2.0 * (q1 * q2 - q0 * q3);       R[2] = 2.0 * (q1 * q3 + q0 * q2);
-    R[3] = 2.0 * (q1 * q2 + q0 * q3);       R[4] = 1.0 - 2.0 * (q1 * q1 + q3 * q3); R[5] = 2.0 * (q2 * q3 - q0 * q1);
-    R[6] = 2.0 * (q1 * q3 - q0 * q2);       R[7] = 2.0 * (q2 * q3 + q0 * q1);       R[8] = 1.0 - 2.0 * (q1 * q1 + q2 * q2);
-    t[0] = row[4]; t[1] = row[5]; t[2] = row[6];
-    return true;
-}
-
-// the validity rule of a cell, in its two halves: a cell that is exactly (0,0,0) holds no point, and a point with a non-finite
-// component (the insert looks at the carried, rounded p') is rejected.  elo_place.hip applies both to the cell as it stands.
-__device__ __forceinline__ bool map_cell_empty(float x, float y, float z) { return x == 0.0f && y == 0.0f && z == 0.0f; }
-__device__ __forceinline__ bool map_point_finite(float x, float y, float z) { return !(x - x != 0.0f || y - y != 0.0f || z - z != 0.0f); }
 
 // one axis of the rounded p': its 21-bit field of the key and its offset inside the voxel; false: the index is out of range
 __device__ __forceinline__ bool map_axis(float c, double voxel, unsigned long long &field, unsigned &g)
@@ -92,10 +74,8 @@ __device__ __forceinline__ bool map_add(unsigned long long *keys, unsigned long 
 
 inline bool map_table_ok(float voxel, int log2_capacity)
 {
-    return voxel > 0.0f && voxel - voxel == 0.0f && log2_capacity >= ELO_MAP_MIN_LOG2 && log2_capacity <= ELO_MAP_MAX_LOG2;
+    return positive_finite(voxel) && log2_capacity >= ELO_MAP_MIN_LOG2 && log2_capacity <= ELO_MAP_MAX_LOG2;
 }
-
-inline bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
 
 }  // namespace
 }  // namespace elo

@@ -53,20 +53,15 @@ __device__ __forceinline__ double mapfit_axis_gap(double p, unsigned long long f
 __device__ __forceinline__ long long mapfit_term(const MapFitEval &a, const float *x, const int h, const int w, const double (&R)[9],
                                                  const double (&t)[3], float (&acc)[FIT_SUMS], unsigned &count)
 {
-    if (h == 0 || h == a.H - 1) return -1;                              // no normal in the edge rows
-    const int wl = w == 0 ? a.W - 1 : w - 1, wr = w == a.W - 1 ? 0 : w + 1;     // the seam
-    const long m = (long)h * a.W + w;
-    const float *c = x + m * 3, *l = x + ((long)h * a.W + wl) * 3, *r = x + ((long)h * a.W + wr) * 3;
-    const float *u = x + (m - a.W) * 3, *d = x + (m + a.W) * 3;
     double P[3], ns[3];
-    if (!fit_normal(c, l, r, u, d, a.jump_rel, P, ns)) return -1;
+    if (!fit_normal(x, h, w, a.H, a.W, a.jump_rel, P, ns)) return -1;
     const double n[3] = {R[0] * ns[0] + R[1] * ns[1] + R[2] * ns[2], R[3] * ns[0] + R[4] * ns[1] + R[5] * ns[2],
                          R[6] * ns[0] + R[7] * ns[1] + R[8] * ns[2]};
-    const double p[3] = {R[0] * P[0] + R[1] * P[1] + R[2] * P[2] + t[0], R[3] * P[0] + R[4] * P[1] + R[5] * P[2] + t[1],
-                         R[6] * P[0] + R[7] * P[1] + R[8] * P[2] + t[2]};
+    double p[3];
+    pose_carry(R, t, P[0], P[1], P[2], p);
     // the voxel of p: the insert's rule on p rounded to float32
     const float xf = (float)p[0], yf = (float)p[1], zf = (float)p[2];
-    if (xf - xf != 0.0f || yf - yf != 0.0f || zf - zf != 0.0f) return -1;
+    if (!point_finite(xf, yf, zf)) return -1;
     unsigned long long f[3];
     unsigned g;
     if (!map_axis(xf, a.voxel, f[0], g) || !map_axis(yf, a.voxel, f[1], g) || !map_axis(zf, a.voxel, f[2], g)) return -1;
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(ELO_BLOCK) void mapfit_eval_kernel(const MapFitEval
     const int b = blockIdx.y;
     const long cells = (long)a.H * a.W;
     double R[9], t[3];
-    bool live = map_pose(pose + (long)b * 7, R, t);                     // (uniform over the workgroup)
+    bool live = pose_load(pose + (long)b * 7, R, t);                    // (uniform over the workgroup)
     live = live && t[0] - t[0] == 0.0 && t[1] - t[1] == 0.0 && t[2] - t[2] == 0.0;
     const float *x = a.xyz + (long)b * cells * 3;
     float acc[FIT_SUMS];
@@ -167,26 +162,13 @@ __global__ __launch_bounds__(ELO_BLOCK) void mapfit_eval_kernel(const MapFitEval
     fit_store_row(acc, count, part, a.parts + ((long)b * gridDim.x + blockIdx.x) * FIT_ROW);
 }
 
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
 }  // namespace
 }  // namespace elo
 
 using namespace elo;
 
-extern "C" int elo_map_fit_parts(int H, int W)
-{
-    if (!fit_sizes_ok(1, H, W)) return -1;
-    return (int)(((long)H * W + MAPFIT_TILE - 1) / MAPFIT_TILE);
-}
-
-// [partial rows (batch, parts, FIT_ROW) | status (batch)]
-extern "C" long elo_map_fit_scratch_words(int batch, int H, int W)
-{
-    if (!fit_sizes_ok(batch, H, W)) return -1;
-    return (long)batch * elo_map_fit_parts(H, W) * FIT_ROW + batch;
-}
+extern "C" int elo_map_fit_parts(int H, int W) { return fit_parts(H, W, MAPFIT_TILE); }
+extern "C" long elo_map_fit_scratch_words(int batch, int H, int W) { return fit_scratch_words(batch, H, W, MAPFIT_TILE); }
 
 extern "C" int elo_map_fit(const elo_map_fit_args *a, elo_stream_t stream)
 {
@@ -197,30 +179,22 @@ extern "C" int elo_map_fit(const elo_map_fit_args *a, elo_stream_t stream)
     ELO_REQUIRE(map_table_ok(a->voxel, a->log2_capacity), who, "voxel is positive and finite, log2_capacity ELO_MAP_MIN_LOG2 .. ELO_MAP_MAX_LOG2");
     ELO_REQUIRE(a->iters >= 0, who, "negative iters");
     ELO_REQUIRE(a->gate > 0.0f && a->gate <= a->voxel, who, "gate must be positive and at most the voxel");
-    ELO_REQUIRE(a->huber > 0.0f && a->huber - a->huber == 0.0f, who, "huber must be positive and finite");
+    ELO_REQUIRE(positive_finite(a->huber), who, "huber must be positive and finite");
     ELO_REQUIRE(a->jump_rel >= 0.0f && a->damping >= 0.0f && a->damping - a->damping == 0.0f, who, "jump_rel / damping must be >= 0");
     ELO_REQUIRE(a->min_points >= 1, who, "min_points is >= 1");
     ELO_REQUIRE(a->keys && a->acc && a->xyz && a->pose_in, who, "null table, image or pose");
     ELO_REQUIRE(a->pose_out && a->info && a->grad && a->stats && a->scratch, who, "null output or scratch pointer");
     ELO_REQUIRE(a->pose_out != a->pose_in, who, "pose_out aliases pose_in");
-    ELO_REQUIRE(aligned8(a->keys) && aligned8(a->acc) && aligned8(a->pose_in) && aligned8(a->pose_out) && aligned8(a->match), who,
+    ELO_REQUIRE(aligned(a->keys, 8) && aligned(a->acc, 8) && aligned(a->pose_in, 8) && aligned(a->pose_out, 8) && aligned(a->match, 8), who,
                 "keys, acc, pose_in, pose_out and match must be 8-byte aligned");
     if (a->batch == 0) return ELO_OK;
     hipStream_t s = (hipStream_t)stream;
-    const int parts = elo_map_fit_parts(a->H, a->W);
+    const int parts = fit_parts(a->H, a->W, MAPFIT_TILE);
     const MapFitEval ev = {a->H, a->W, (double)a->voxel, (double)a->gate, (double)a->huber, (double)a->jump_rel,
                            (1ull << a->log2_capacity) - 1ull, (unsigned long long)a->min_points, a->keys, a->acc, a->xyz, a->match,
                            a->scratch};
-    FitSolve<FitPoseWorld> so = {parts, a->scratch, a->scratch + (long)a->batch * parts * FIT_ROW, a->pose_in, a->pose_in, a->pose_out,
-                                 a->info, a->grad, a->stats, a->min_count, (double)a->damping, 1, 0};
     const dim3 grid((unsigned)parts, (unsigned)a->batch);
-    for (int it = 0; it <= a->iters; ++it) {
-        const double *pose = it == 0 ? a->pose_in : a->pose_out;
+    return fit_run<FitPoseWorld>(a, parts, s, who, [&](const double *pose) {
         hipLaunchKernelGGL(mapfit_eval_kernel, grid, dim3(ELO_BLOCK), 0, s, ev, pose);
-        so.pose = pose;
-        so.first = it == 0;
-        so.report = it == a->iters;
-        hipLaunchKernelGGL(fit_solve_kernel<FitPoseWorld>, dim3((unsigned)a->batch), dim3(FIT_SOLVE_BLOCK), 0, s, so);
-    }
-    return check_launch(who);
+    });
 }

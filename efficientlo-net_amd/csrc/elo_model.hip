@@ -9,6 +9,7 @@
 // per target cell recomputes the winner's point from its index by the very same instructions (splat stores no points) and writes
 // both outputs in full.  No floating-point atomic: the minimum of a set of integers does not depend on the order of arrival.
 #include "elo_project_device.h"
+#include "elo_pose_device.h"
 
 namespace elo {
 namespace {
@@ -28,31 +29,16 @@ struct ModelRender {
     int vec;                        // 1: H*W is a multiple of 4 and src is 16-byte aligned -- a strip is three aligned float4
 };
 
-// R(q), q normalised here, in double from the row's floats; false: the quaternion has no direction (zero or non-finite norm)
-__device__ __forceinline__ bool model_pose(const float *row, double (&R)[9], double (&t)[3])
-{
-    double q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
-    const double n = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-    if (!(n > 0.0) || n - n != 0.0) return false;
-    q0 /= n; q1 /= n; q2 /= n; q3 /= n;
-    R[0] = 1.0 - 2.0 * (q2 * q2 + q3 * q3); R[1] = 2.0 * (q1 * q2 - q0 * q3);       R[2] = 2.0 * (q1 * q3 + q0 * q2);
-    R[3] = 2.0 * (q1 * q2 + q0 * q3);       R[4] = 1.0 - 2.0 * (q1 * q1 + q3 * q3); R[5] = 2.0 * (q2 * q3 - q0 * q1);
-    R[6] = 2.0 * (q1 * q3 - q0 * q2);       R[7] = 2.0 * (q2 * q3 + q0 * q1);       R[8] = 1.0 - 2.0 * (q1 * q1 + q2 * q2);
-    t[0] = row[4]; t[1] = row[5]; t[2] = row[6];
-    return true;
-}
-
 // p' = R p + t in double, every component rounded to float32 once, and its float32 range; false: the point is dropped (an empty
 // cell, a non-finite or all-zero p', a range that is not positive and finite).  Splat and resolve both come through here.
 __device__ __forceinline__ bool model_carry(const double (&R)[9], const double (&t)[3], float ax, float ay, float az, float &x, float &y,
                                             float &z, float &rf)
 {
-    if (ax == 0.0f && ay == 0.0f && az == 0.0f) return false;
-    x = (float)(R[0] * ax + R[1] * ay + R[2] * az + t[0]);
-    y = (float)(R[3] * ax + R[4] * ay + R[5] * az + t[1]);
-    z = (float)(R[6] * ax + R[7] * ay + R[8] * az + t[2]);
-    if (x - x != 0.0f || y - y != 0.0f || z - z != 0.0f) return false;
-    if (x == 0.0f && y == 0.0f && z == 0.0f) return false;
+    if (cell_empty(ax, ay, az)) return false;
+    pose_carry_f32(R, t, ax, ay, az, x, y, z);
+    if (x - x != 0.0f || y - y != 0.0f || z - z != 0.0f) return false;      // (!point_finite, spelled out: through the call the
+                                                                            //  splat and resolve kernels allocate other registers)
+    if (cell_empty(x, y, z)) return false;
     rf = sqrtf(x * x + y * y + z * z);                                  // the projections' own sequence (bin_point_by, elo_features.hip)
     return rf > 0.0f && rf - rf == 0.0f;
 }
@@ -71,7 +57,7 @@ __device__ __forceinline__ void model_splat_block(const ModelRender &a, const Ro
     const long i0 = ((long)tile * ELO_BLOCK + threadIdx.x) * MODEL_STRIP;
     if (i0 >= cells) return;
     double R[9], t[3];
-    if (!model_pose(a.pose + (long)bk * 7, R, t)) return;                               // the whole source is skipped
+    if (!pose_load(a.pose + (long)bk * 7, R, t)) return;                              // the whole source is skipped
     const float *s = a.src + ((long)bk * cells + i0) * 3;
     float v[3 * MODEL_STRIP];
     if (a.vec) {                                                                        // (cells % 4 == 0: the strip is inside the image)
@@ -123,21 +109,13 @@ __global__ __launch_bounds__(ELO_BLOCK) void model_resolve_kernel(const ModelRen
         const long bk = (long)b * a.K + k;
         const float *p = a.src + (bk * cells + (i - k * cells)) * 3;
         double R[9], t[3];
-        if (model_pose(a.pose + bk * 7, R, t) && model_carry(R, t, p[0], p[1], p[2], x, y, z, rf)) idx = (int)i;
+        if (pose_load(a.pose + bk * 7, R, t) && model_carry(R, t, p[0], p[1], p[2], x, y, z, rf)) idx = (int)i;
         else x = y = z = 0.0f;                                                          // (not reached: the key came from this point)
     }
     out_xyz[(long)g * 3 + 0] = x;
     out_xyz[(long)g * 3 + 1] = y;
     out_xyz[(long)g * 3 + 2] = z;
     out_src[g] = idx;
-}
-
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
-bool model_sizes_ok(int batch, int H, int W)
-{
-    return batch >= 0 && H >= 1 && W >= 1 && (long)H * W <= (1l << 31) - 1 && (long)batch * H * W <= (1l << 31) - 1;
 }
 
 }  // namespace
@@ -148,7 +126,7 @@ using namespace elo;
 // one 64-bit key per target cell
 extern "C" long elo_model_render_scratch_words(int batch, int H, int W)
 {
-    if (!model_sizes_ok(batch, H, W)) return -1;
+    if (!image_sizes_ok(batch, H, W, 1)) return -1;
     return 2l * batch * H * W;
 }
 
@@ -157,25 +135,23 @@ extern "C" int elo_model_render(const elo_model_render_args *a, elo_stream_t str
     const char *who = "elo_model_render";
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->K >= 1 && a->K <= ELO_MODEL_MAX_SCANS, who, "K is 1 .. ELO_MODEL_MAX_SCANS");
-    ELO_REQUIRE(model_sizes_ok(a->batch, a->H, a->W), who, "bad sizes");
+    ELO_REQUIRE(image_sizes_ok(a->batch, a->H, a->W, 1), who, "bad sizes");
     ELO_REQUIRE((long)a->K * a->H * a->W <= (1l << 31) - 1, who, "K * H * W beyond 2^31");
     ELO_REQUIRE(!a->beam_elev || a->H <= ELO_MAX_BEAMS, who, "more beams than ELO_MAX_BEAMS");
     ELO_REQUIRE(a->az_res > 0.0f && (a->beam_elev || a->vert_res > 0.0f), who, "bad projection constants");
     ELO_REQUIRE(a->src && a->pose, who, "null image or pose");
     ELO_REQUIRE(a->out_xyz && a->out_src && a->scratch, who, "null output or scratch pointer");
-    ELO_REQUIRE(((uintptr_t)a->scratch & 7) == 0, who, "scratch must be 8-byte aligned");
+    ELO_REQUIRE(aligned(a->scratch, 8), who, "scratch must be 8-byte aligned");
     const long cells = (long)a->H * a->W;
-    {
-        const uintptr_t s0 = (uintptr_t)a->src, s1 = s0 + (size_t)a->batch * a->K * cells * 12;
-        const uintptr_t o0 = (uintptr_t)a->out_xyz, o1 = o0 + (size_t)a->batch * cells * 12;
-        ELO_REQUIRE(a->batch == 0 ? o0 != s0 : (o1 <= s0 || s1 <= o0), who, "out_xyz aliases src");
-    }
+    ELO_REQUIRE(a->batch == 0 ? a->out_xyz != a->src                                     // (an empty batch: only the very same address)
+                              : !ranges_meet(a->src, (size_t)a->batch * a->K * cells * 12, a->out_xyz, (size_t)a->batch * cells * 12),
+                who, "out_xyz aliases src");
     if (a->batch == 0) return ELO_OK;
     hipStream_t s = (hipStream_t)stream;
     const unsigned total = (unsigned)(a->batch * cells);
     const unsigned tiles = (unsigned)((cells + MODEL_TILE - 1) / MODEL_TILE);
     const ModelRender r = {a->K, a->H, a->W, a->az_res, a->src, a->pose, reinterpret_cast<unsigned long long *>(a->scratch), tiles,
-                           (cells % MODEL_STRIP == 0 && ((uintptr_t)a->src & 15) == 0) ? 1 : 0};
+                           (cells % MODEL_STRIP == 0 && aligned(a->src, 16)) ? 1 : 0};
     const unsigned quads = (2u * total + 3u) / 4u, want = (quads + ELO_BLOCK - 1) / ELO_BLOCK;
     hipLaunchKernelGGL(model_clear_kernel, dim3(want < MODEL_CLEAR_BLOCKS ? want : MODEL_CLEAR_BLOCKS), dim3(ELO_BLOCK), 0, s,
                        a->scratch, 2u * total);

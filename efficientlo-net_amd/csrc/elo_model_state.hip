@@ -8,7 +8,7 @@
 // model_update_kernel: one workgroup, thread j owns row j of the poses: P_j <- T^-1 o P_j in double, the entered row <- the
 // identity, every component rounded to float32 once into the copy the render reads, then thread 0 writes the state -- the only
 // store to it anywhere, behind a barrier that follows every read of it.  No atomic.
-#include "elo_common.h"
+#include "elo_pose_device.h"
 
 namespace elo {
 namespace {
@@ -78,13 +78,12 @@ __global__ __launch_bounds__(STATE_UPDATE_BLOCK) void model_update_kernel(double
             const double m = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
             p[0] = q0 / m; p[1] = q1 / m; p[2] = q2 / m; p[3] = q3 / m;
             // R(q_T)^T (t_j - t_T)
-            const double R0 = 1.0 - 2.0 * (y * y + z * z), R1 = 2.0 * (x * y - w * z), R2 = 2.0 * (x * z + w * y);
-            const double R3 = 2.0 * (x * y + w * z), R4 = 1.0 - 2.0 * (x * x + z * z), R5 = 2.0 * (y * z - w * x);
-            const double R6 = 2.0 * (x * z - w * y), R7 = 2.0 * (y * z + w * x), R8 = 1.0 - 2.0 * (x * x + y * y);
+            double R[9];
+            pose_rotation(w, x, y, z, R);
             const double v0 = row[4] - (double)T[4], v1 = row[5] - (double)T[5], v2 = row[6] - (double)T[6];
-            p[4] = R0 * v0 + R3 * v1 + R6 * v2;
-            p[5] = R1 * v0 + R4 * v1 + R7 * v2;
-            p[6] = R2 * v0 + R5 * v1 + R8 * v2;
+            p[4] = R[0] * v0 + R[3] * v1 + R[6] * v2;
+            p[5] = R[1] * v0 + R[4] * v1 + R[7] * v2;
+            p[6] = R[2] * v0 + R[5] * v1 + R[8] * v2;
         }
         for (int i = 0; i < 7; ++i) {
             row[i] = p[i];
@@ -98,24 +97,9 @@ __global__ __launch_bounds__(STATE_UPDATE_BLOCK) void model_update_kernel(double
     }
 }
 
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
-// the pose fit's bounds on one image (fit_sizes_ok, elo_posefit.hip) and the render's on the ring it reads (elo_model.hip)
-bool state_sizes_ok(int K, int H, int W)
-{
-    return H >= 3 && W >= 1 && (long)H * W <= (1l << 31) - 1 && (long)K * H * W <= (1l << 31) - 1;
-}
-
-bool overlaps(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 void launch_enter(float *ring, const float *image, const int *state, int K, long cells, int begin, hipStream_t s)
 {
-    const int vec = (cells % 4 == 0 && (((uintptr_t)ring | (uintptr_t)image) & 15) == 0) ? 1 : 0;
+    const int vec = (cells % 4 == 0 && aligned(ring, 16) && aligned(image, 16)) ? 1 : 0;
     const unsigned long n = vec ? (unsigned long)cells * 3 / 4 : (unsigned long)cells * 3;
     const unsigned long want = (n + ELO_BLOCK - 1) / ELO_BLOCK;
     hipLaunchKernelGGL(model_enter_kernel, dim3((unsigned)(want < STATE_COPY_BLOCKS ? want : STATE_COPY_BLOCKS)), dim3(ELO_BLOCK), 0, s,
@@ -133,10 +117,10 @@ extern "C" int elo_model_begin(const elo_model_begin_args *a, elo_stream_t strea
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->K >= 1 && a->K <= ELO_MODEL_MAX_SCANS, who, "K is 1 .. ELO_MODEL_MAX_SCANS");
     ELO_REQUIRE(a->H >= 3, who, "a fit's normal needs three rows: H >= 3");
-    ELO_REQUIRE(state_sizes_ok(a->K, a->H, a->W), who, "bad sizes");
+    ELO_REQUIRE(image_sizes_ok(a->K, a->H, a->W, 3), who, "bad sizes");    // one image as a fit takes it, the K of the ring as the render does
     ELO_REQUIRE(a->ring && a->state && a->first, who, "null ring, state or image");
     const long cells = (long)a->H * a->W;
-    ELO_REQUIRE(!overlaps(a->ring, (size_t)a->K * cells * 12, a->first, (size_t)cells * 12), who, "first overlaps ring");
+    ELO_REQUIRE(!ranges_meet(a->ring, (size_t)a->K * cells * 12, a->first, (size_t)cells * 12), who, "first overlaps ring");
     launch_enter(a->ring, a->first, a->state, a->K, cells, 1, (hipStream_t)stream);
     return check_launch(who);
 }
@@ -147,12 +131,12 @@ extern "C" int elo_model_advance(const elo_model_advance_args *a, elo_stream_t s
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(a->K >= 1 && a->K <= ELO_MODEL_MAX_SCANS, who, "K is 1 .. ELO_MODEL_MAX_SCANS");
     ELO_REQUIRE(a->H >= 3, who, "a fit's normal needs three rows: H >= 3");
-    ELO_REQUIRE(state_sizes_ok(a->K, a->H, a->W), who, "bad sizes");
+    ELO_REQUIRE(image_sizes_ok(a->K, a->H, a->W, 3), who, "bad sizes");    // one image as a fit takes it, the K of the ring as the render does
     ELO_REQUIRE(a->ring && a->state && a->scan, who, "null ring, state or image");
     ELO_REQUIRE(a->poses64 && a->poses32 && a->T, who, "null poses or T");
-    ELO_REQUIRE(((uintptr_t)a->poses64 & 7) == 0, who, "poses64 must be 8-byte aligned");
+    ELO_REQUIRE(aligned(a->poses64, 8), who, "poses64 must be 8-byte aligned");
     const long cells = (long)a->H * a->W;
-    ELO_REQUIRE(!overlaps(a->ring, (size_t)a->K * cells * 12, a->scan, (size_t)cells * 12), who, "scan overlaps ring");
+    ELO_REQUIRE(!ranges_meet(a->ring, (size_t)a->K * cells * 12, a->scan, (size_t)cells * 12), who, "scan overlaps ring");
     hipStream_t s = (hipStream_t)stream;
     launch_enter(a->ring, a->scan, a->state, a->K, cells, 0, s);
     hipLaunchKernelGGL(model_update_kernel, dim3(1), dim3(STATE_UPDATE_BLOCK), 0, s, a->poses64, a->poses32, a->state, a->T, a->K);

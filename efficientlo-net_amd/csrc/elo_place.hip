@@ -19,7 +19,7 @@
 // workgroups a CU at most.  The best shift by (dist, shift) is a shuffle reduction in the first wave.
 // place_rank_kernel: a workgroup per query, k passes of an argmin by (dist, entry) over the entries that lie above the last
 // winner: no sort, no ties left to chance.
-#include "elo_map_device.h"
+#include "elo_pose_device.h"
 
 namespace elo {
 namespace {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(ELO_BLOCK) void place_descriptor_kernel(const Place
         const int h = (int)(i / run), w = w0 + (int)(i - (long)h * run);
         const float *p = img + ((long)h * W + w) * 3;
         const float x = p[0], y = p[1], z = p[2];
-        if (map_cell_empty(x, y, z) || !map_point_finite(x, y, z)) continue;
+        if (cell_empty(x, y, z) || !point_finite(x, y, z)) continue;
         const double r2 = (double)x * (double)x + (double)y * (double)y;
         if (r2 < a.min_range2 || r2 >= edge2[a.rings]) continue;
         int ring = 0;
@@ -195,9 +195,6 @@ inline bool place_shape_ok(int rings, int sectors)
     return rings >= 1 && rings <= PLACE_MAX_R && sectors >= 1 && sectors <= PLACE_MAX_S;
 }
 
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
 }  // namespace
 }  // namespace elo
 
@@ -209,14 +206,14 @@ extern "C" int elo_scan_descriptor(const elo_scan_descriptor_args *a, elo_stream
     ELO_REQUIRE(a, who, "null argument block");
     ELO_REQUIRE(place_shape_ok(a->rings, a->sectors), who, "rings is 1 .. ELO_PLACE_MAX_RINGS, sectors 1 .. ELO_PLACE_MAX_SECTORS");
     ELO_REQUIRE(a->batch >= 0 && a->H >= 1 && a->W >= a->sectors, who, "bad sizes: batch >= 0, H >= 1, W >= sectors");
-    ELO_REQUIRE((long)a->H * a->W <= (1l << 31) - 1 && (long)a->batch * a->H * a->W <= (1l << 31) - 1, who, "batch * H * W beyond 2^31");
+    ELO_REQUIRE(image_sizes_ok(a->batch, a->H, a->W, 1), who, "batch * H * W beyond 2^31");
     ELO_REQUIRE(a->batch <= 65535, who, "batch beyond 65535");
-    ELO_REQUIRE(a->z_step > 0.0 && a->z_step - a->z_step == 0.0 && a->z_min - a->z_min == 0.0, who,
+    ELO_REQUIRE(positive_finite(a->z_step) && a->z_min - a->z_min == 0.0, who,
                 "z_step is positive and finite, z_min finite");
     ELO_REQUIRE(a->min_range2 >= 0.0, who, "min_range2 is >= 0");
     double below = 0.0;
     for (int j = 1; j <= a->rings; ++j) {
-        ELO_REQUIRE(a->edge2[j] > below && a->edge2[j] - a->edge2[j] == 0.0, who, "edge2[1 .. rings] is positive, finite and ascending");
+        ELO_REQUIRE(a->edge2[j] > below && positive_finite(a->edge2[j]), who, "edge2[1 .. rings] is positive, finite and ascending");
         below = a->edge2[j];
     }
     ELO_REQUIRE(a->xyz && a->desc, who, "null pointer");
@@ -236,7 +233,7 @@ extern "C" int elo_descriptor_search(const elo_descriptor_search_args *a, elo_st
     ELO_REQUIRE(a->k >= 1 && a->k <= ELO_PLACE_MAX_K, who, "k is 1 .. ELO_PLACE_MAX_K");
     ELO_REQUIRE(a->query && a->db && a->entry && a->shift && a->dist, who, "null pointer");
     ELO_REQUIRE(a->m == 0 || (a->best_shift && a->best_dist), who, "null pointer");
-    ELO_REQUIRE(aligned8(a->dist) && aligned8(a->best_dist), who, "dist and best_dist must be 8-byte aligned");
+    ELO_REQUIRE(aligned(a->dist, 8) && aligned(a->best_dist, 8), who, "dist and best_dist must be 8-byte aligned");
     if (a->n == 0) return ELO_OK;
     const PlaceSearch s = {a->n, a->m, a->rings, a->sectors, a->k, a->query, a->db, a->entry, a->shift, a->dist, a->best_shift, a->best_dist};
     hipStream_t st = (hipStream_t)stream;

@@ -30,21 +30,17 @@ __device__ __forceinline__ void fit_term(const FitEval &a, const Rows &rows, con
                                          const double (&t)[3], float (&acc)[FIT_SUMS], unsigned &count)
 {
     const float ax = x1[0], ay = x1[1], az = x1[2];
-    if (ax == 0.0f && ay == 0.0f && az == 0.0f) return;
-    const double p[3] = {R[0] * ax + R[1] * ay + R[2] * az + t[0], R[3] * ax + R[4] * ay + R[5] * az + t[1],
-                         R[6] * ax + R[7] * ay + R[8] * az + t[2]};
+    if (cell_empty(ax, ay, az)) return;
+    double p[3];
+    pose_carry(R, t, ax, ay, az, p);
     // the cell of p: the projections' own float32 rule on p rounded to float32 (bin_point_by, elo_features.hip)
     const float x = (float)p[0], y = (float)p[1], z = (float)p[2];
     const float rf = sqrtf(x * x + y * y + z * z);
     if (!(rf > 0.0f) || rf - rf != 0.0f) return;                        // the origin has no direction; a non-finite pose has no cell
     const int m = rows.cell(atan2f(y, x), z, rf, a.H, a.W, a.az_res);   // clipped to the image by the rule
-    const int h = m / a.W, w = m - h * a.W;
-    if (h == 0 || h == a.H - 1) return;                                 // no normal in the edge rows
-    const int wl = w == 0 ? a.W - 1 : w - 1, wr = w == a.W - 1 ? 0 : w + 1;     // the seam
-    const float *c = x2 + (long)m * 3, *l = x2 + ((long)h * a.W + wl) * 3, *r = x2 + ((long)h * a.W + wr) * 3;
-    const float *u = x2 + (long)(m - a.W) * 3, *d = x2 + (long)(m + a.W) * 3;
+    const int h = m / a.W;
     double P2[3], n[3];
-    if (!fit_normal(c, l, r, u, d, a.jump_rel, P2, n)) return;
+    if (!fit_normal(x2, h, m - h * a.W, a.H, a.W, a.jump_rel, P2, n)) return;
     const double dv[3] = {p[0] - P2[0], p[1] - P2[1], p[2] - P2[2]};
     if (!(sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) <= a.gate)) return;
     const double res = n[0] * dv[0] + n[1] * dv[1] + n[2] * dv[2];
@@ -58,7 +54,8 @@ __device__ __forceinline__ void fit_eval_block(const FitEval &a, const float *po
     const int b = blockIdx.y;
     const long cells = (long)a.H * a.W;
     double R[9], t[3], q[4];
-    pose_double(pose + b * 7, R, t, q);
+    pose_row_or_identity(pose + b * 7, q, t);
+    pose_rotation(q[0], q[1], q[2], q[3], R);
     const float *x1 = a.xyz1 + (long)b * cells * 3, *x2 = a.xyz2 + (long)b * cells * 3;
     float acc[FIT_SUMS];
     for (int k = 0; k < FIT_SUMS; ++k) acc[k] = 0.0f;
@@ -86,26 +83,13 @@ __global__ __launch_bounds__(ELO_BLOCK) void fit_eval_beams_kernel(const FitEval
     fit_eval_block(a, pose, RowsByBeams{mid, half}, part);
 }
 
-#define ELO_REQUIRE(cond, who, what) \
-    do { if (!(cond)) return fail(ELO_ERR_ARG, "%s: %s", who, what); } while (0)
-
 }  // namespace
 }  // namespace elo
 
 using namespace elo;
 
-extern "C" int elo_pose_fit_parts(int H, int W)
-{
-    if (!fit_sizes_ok(1, H, W)) return -1;
-    return (int)(((long)H * W + FIT_TILE - 1) / FIT_TILE);
-}
-
-// [partial rows (batch, parts, FIT_ROW) | status (batch)]
-extern "C" long elo_pose_fit_scratch_words(int batch, int H, int W)
-{
-    if (!fit_sizes_ok(batch, H, W)) return -1;
-    return (long)batch * elo_pose_fit_parts(H, W) * FIT_ROW + batch;
-}
+extern "C" int elo_pose_fit_parts(int H, int W) { return fit_parts(H, W, FIT_TILE); }
+extern "C" long elo_pose_fit_scratch_words(int batch, int H, int W) { return fit_scratch_words(batch, H, W, FIT_TILE); }
 
 extern "C" int elo_pose_fit(const elo_pose_fit_args *a, elo_stream_t stream)
 {
@@ -114,8 +98,8 @@ extern "C" int elo_pose_fit(const elo_pose_fit_args *a, elo_stream_t stream)
     ELO_REQUIRE(a->H >= 3, who, "a normal needs three rows: H >= 3");
     ELO_REQUIRE(fit_sizes_ok(a->batch, a->H, a->W), who, "bad sizes");
     ELO_REQUIRE(a->iters >= 0, who, "negative iters");
-    ELO_REQUIRE(a->gate > 0.0f && a->gate - a->gate == 0.0f, who, "gate must be positive and finite");
-    ELO_REQUIRE(a->huber > 0.0f && a->huber - a->huber == 0.0f, who, "huber must be positive and finite");
+    ELO_REQUIRE(positive_finite(a->gate), who, "gate must be positive and finite");
+    ELO_REQUIRE(positive_finite(a->huber), who, "huber must be positive and finite");
     ELO_REQUIRE(a->jump_rel >= 0.0f && a->damping >= 0.0f && a->damping - a->damping == 0.0f, who, "jump_rel / damping must be >= 0");
     ELO_REQUIRE(!a->beam_elev || a->H <= ELO_MAX_BEAMS, who, "more beams than ELO_MAX_BEAMS");
     ELO_REQUIRE(a->az_res > 0.0f && (a->beam_elev || a->vert_res > 0.0f), who, "bad projection constants");
@@ -124,22 +108,14 @@ extern "C" int elo_pose_fit(const elo_pose_fit_args *a, elo_stream_t stream)
     ELO_REQUIRE(a->pose_out != a->pose_in, who, "pose_out aliases pose_in");
     if (a->batch == 0) return ELO_OK;
     hipStream_t s = (hipStream_t)stream;
-    const int parts = elo_pose_fit_parts(a->H, a->W);
+    const int parts = fit_parts(a->H, a->W, FIT_TILE);
     const FitEval ev = {a->H, a->W, a->az_res, a->xyz1, a->xyz2, (double)a->gate, (double)a->huber, (double)a->jump_rel, a->scratch};
-    FitSolve<FitPoseRel> so = {parts, a->scratch, a->scratch + (long)a->batch * parts * FIT_ROW, a->pose_in, a->pose_in, a->pose_out,
-                   a->info, a->grad, a->stats, a->min_count, (double)a->damping, 1, 0};
     const int half = a->beam_elev ? beam_search_half(a->H) : 0;
     const dim3 grid((unsigned)parts, (unsigned)a->batch);
-    for (int it = 0; it <= a->iters; ++it) {
-        const float *pose = it == 0 ? a->pose_in : a->pose_out;
+    return fit_run<FitPoseRel>(a, parts, s, who, [&](const float *pose) {
         if (a->beam_elev)
             hipLaunchKernelGGL(fit_eval_beams_kernel, grid, dim3(ELO_BLOCK), 0, s, ev, pose, a->beam_elev, half);
         else
             hipLaunchKernelGGL(fit_eval_kernel, grid, dim3(ELO_BLOCK), 0, s, ev, pose, a->vert_res, a->vert_off);
-        so.pose = pose;
-        so.first = it == 0;
-        so.report = it == a->iters;
-        hipLaunchKernelGGL(fit_solve_kernel<FitPoseRel>, dim3((unsigned)a->batch), dim3(FIT_SOLVE_BLOCK), 0, s, so);
-    }
-    return check_launch(who);
+    });
 }

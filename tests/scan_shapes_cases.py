@@ -168,7 +168,7 @@ def wall_case():
 def dead_rows_case():
     """(x1 (3,8,64,3) filtered, x2, good poses (3,7) float32, dead poses, consts, [share dropped]): three images of the 8 x 64 scene;
     image 2's good pose is the identity rotation with its start translation.  Dead: image 0's translation holds a NaN, image 2's
-    quaternion is zero -- the identity, by pose_double.  The filter ran at the good poses."""
+    quaternion is zero -- the identity, by pose_row_or_identity.  The filter ran at the good poses."""
     f1, f2 = R.scene(3, 8, 64)
     c = R.constants(8, 64)
     good = R.start_poses(3)
