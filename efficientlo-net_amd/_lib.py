@@ -108,6 +108,41 @@ def grouping_form(query, args):
     return grouping_form_name(query, rc)
 
 
+# ... and the weight gradient's: ELO_WGRAD_FORM(CI, CO, xv, gv, waves, gy, gz), the 42 compiled kernels by name
+WGRAD_LOADS = ("s", "v")                                       # one channel per tile / CI (CO) consecutive channels per lane
+WGRAD_FORMS = tuple("ci%dco%d/x%sg%s" % (ci, co, WGRAD_LOADS[xv], WGRAD_LOADS[gv]) for ci in (1, 2, 3, 4) for co in (1, 2, 4)
+                    for xv in (0, 1) if not (xv and ci == 3) for gv in (0, 1))
+
+
+def wgrad_form_fields(value):
+    """ELO_WGRAD_FORM unpacked: dict(CI, CO, xv, gv, waves, gy, gz)."""
+    return dict(CI=(value & 3) + 1, CO=1 << (value >> 2 & 3), xv=value >> 4 & 1, gv=value >> 5 & 1, waves=(value >> 6 & 3) + 1,
+                gz=value >> 8 & 4095, gy=value >> 20)
+
+
+def wgrad_form_name(value):
+    """ELO_WGRAD_FORM as '<kernel>@<gy>x<gz>w<waves>' with the kernel a name of WGRAD_FORMS: 'ci4co4/xvgv@1x1w1'."""
+    f = wgrad_form_fields(value)
+    return "ci%dco%d/x%sg%s@%dx%dw%d" % (f["CI"], f["CO"], WGRAD_LOADS[f["xv"]], WGRAD_LOADS[f["gv"]], f["gy"], f["gz"], f["waves"])
+
+
+def wgrad_form(args):
+    """What elo_dense_weight_grad_form answers for a WeightGradArgs block, as wgrad_form_name spells it; raises where
+    elo_dense_weight_grad would refuse the block.  Host only: nothing is launched."""
+    rc = lib().elo_dense_weight_grad_form(ctypes.byref(args))
+    if rc < 0:
+        check(rc)
+    return wgrad_form_name(rc)
+
+
+def bn_parts(rows_per_group, C):
+    """elo_bn_parts: the partial rows of the reductions of elo_bn_stats / elo_bn_backward; raises where they would refuse the sizes."""
+    rc = lib().elo_bn_parts(rows_per_group, C)
+    if rc < 0:
+        check(rc)
+    return rc
+
+
 SoftmaxValidArgs = _struct("elo_softmax_valid_args", [
     ("batch", _i), ("npoints", _i), ("C", _i), ("feature", _vp), ("weight", _vp), ("xyz", _vp), ("out", _vp),
     ("scratch", _vp), ("stats", _vp)])
@@ -326,6 +361,8 @@ SYMBOLS = [
     ("elo_bn_apply", ctypes.c_int, [ctypes.POINTER(BnApplyArgs), _vp]),
     ("elo_bn_backward", ctypes.c_int, [ctypes.POINTER(BnBackwardArgs), _vp]),
     ("elo_dense_weight_grad", ctypes.c_int, [ctypes.POINTER(WeightGradArgs), _vp]),
+    ("elo_dense_weight_grad_form", ctypes.c_int, [ctypes.POINTER(WeightGradArgs)]),
+    ("elo_bn_parts", ctypes.c_int, [ctypes.c_long, ctypes.c_int]),
     ("elo_dense_rows", ctypes.c_int, [ctypes.POINTER(DenseRowsArgs), _vp]),
     ("elo_dense_rows_supported", ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int]),
     ("elo_dense_rows_scratch_floats", ctypes.c_long, [ctypes.c_int, ctypes.c_int]),

@@ -457,6 +457,12 @@ using namespace elo;
 
 extern "C" long elo_bn_scratch_floats(int C, int groups) { return 2l * C * ELO_BN_MAX_PARTS * (groups > 1 ? groups : 1); }
 
+extern "C" int elo_bn_parts(long rows_per_group, int C)
+{
+    if (int rc = check_bn("elo_bn_parts", rows_per_group, C, {})) return rc;
+    return grid_for(rows_per_group, C);
+}
+
 // rows per group (groups <= 1: one group), or -1
 static long group_rows(const char *who, long rows, int groups)
 {
@@ -531,30 +537,58 @@ extern "C" int elo_weight_grad_slices(long rows, int Cin, int Cout)
     return (int)(s < 1 ? 1 : s);
 }
 
-extern "C" int elo_dense_weight_grad(const elo_weight_grad_args *a, elo_stream_t stream)
+// what elo_dense_weight_grad launches for an argument block, or why it refuses it: the ONE place that decides (the launcher and the
+// elo_dense_weight_grad_form query both ask here)
+namespace {
+struct WeightGradPlan { int CI, CO, gy, gz, wpb, slices; bool xv, gv; };
+
+int weight_grad_plan(const elo_weight_grad_args *a, const char *who, WeightGradPlan &p)
 {
-    const char *who = "elo_dense_weight_grad";
     if (!a) return fail(ELO_ERR_ARG, "%s: null argument block", who);
     if (a->rows <= 0 || a->Cin <= 0 || a->Cout <= 0) return fail(ELO_ERR_ARG, "%s: bad sizes", who);
     if (!a->x || !a->g || !a->dW || !a->scratch) return fail(ELO_ERR_ARG, "%s: null tensor pointer", who);
     if (a->rows * (long)(a->Cin > a->Cout ? a->Cin : a->Cout) >= (1l << 31)) return fail(ELO_ERR_LIMIT, "%s: rows * width >= 2^31 (32-bit element offsets)", who);
     const int cit = (a->Cin + 15) / 16, cot = (a->Cout + 15) / 16;
-    const int slices = elo_weight_grad_slices(a->rows, a->Cin, a->Cout);
-    float *bpart = a->db ? a->scratch + (size_t)slices * a->Cin * a->Cout : nullptr;
-    hipStream_t s = (hipStream_t)stream;
+    p.slices = elo_weight_grad_slices(a->rows, a->Cin, a->Cout);
     // blocks of dW: all column tiles of a <= 64-wide output (1, 2 or 4); row tiles: the count in 1..4 that pads the input
     // width least, larger on a tie or when the padding stays <= 25 % (138 channels = 9 tiles: 3 x 3; 80 = 5 tiles: 2 x 3)
-    const int CO = cot >= 4 ? 4 : cot >= 2 ? 2 : 1;
-    int CI = 1;
+    p.CO = cot >= 4 ? 4 : cot >= 2 ? 2 : 1;
+    p.CI = 1;
     for (int c = 2; c <= 4; ++c) {
         const int padded = (cit + c - 1) / c * c;
-        if (padded <= (cit + CI - 1) / CI * CI || padded * 4 <= cit * 5) CI = c;
+        if (padded <= (cit + p.CI - 1) / p.CI * p.CI || padded * 4 <= cit * 5) p.CI = c;
     }
-    const int gy = (cit + CI - 1) / CI, gz = (cot + CO - 1) / CO, nb = gy * gz, wpb = nb < TB / 64 ? nb : TB / 64;
-    const dim3 grid((unsigned)slices, (unsigned)((nb + wpb - 1) / wpb));
+    p.gy = (cit + p.CI - 1) / p.CI;
+    p.gz = (cot + p.CO - 1) / p.CO;
+    // (the block grid as ELO_WGRAD_FORM packs it; beyond it the launch's own y extent, 65535 workgroups, is exceeded as well)
+    if (p.gy > 2047 || p.gz > 4095 || (long)p.gy * p.gz > 4l * 65535)
+        return fail(ELO_ERR_LIMIT, "%s: %d x %d blocks of dW (at most 2047 x 4095, 262140 in all)", who, p.gy, p.gz);
+    const int nb = p.gy * p.gz;
+    p.wpb = nb < TB / 64 ? nb : TB / 64;
     // vector loads: the tile count is a vector width (1, 2, 4), every block of the grid is whole, rows stay 16-byte aligned
-    const bool xv = CI != 3 && a->Cin % (16 * CI) == 0 && ((uintptr_t)a->x & 15) == 0;
-    const bool gv = a->Cout % (16 * CO) == 0 && ((uintptr_t)a->g & 15) == 0;
+    p.xv = p.CI != 3 && a->Cin % (16 * p.CI) == 0 && ((uintptr_t)a->x & 15) == 0;
+    p.gv = a->Cout % (16 * p.CO) == 0 && ((uintptr_t)a->g & 15) == 0;
+    return ELO_OK;
+}
+}  // namespace
+
+extern "C" int elo_dense_weight_grad_form(const elo_weight_grad_args *a)
+{
+    WeightGradPlan p;
+    if (int rc = weight_grad_plan(a, "elo_dense_weight_grad_form", p)) return rc;
+    return ELO_WGRAD_FORM(p.CI, p.CO, p.xv ? 1 : 0, p.gv ? 1 : 0, p.wpb, p.gy, p.gz);
+}
+
+extern "C" int elo_dense_weight_grad(const elo_weight_grad_args *a, elo_stream_t stream)
+{
+    const char *who = "elo_dense_weight_grad";
+    WeightGradPlan p;
+    if (int rc = weight_grad_plan(a, who, p)) return rc;
+    const int slices = p.slices, CI = p.CI, CO = p.CO, gy = p.gy, gz = p.gz, wpb = p.wpb, nb = gy * gz;
+    const bool xv = p.xv, gv = p.gv;
+    float *bpart = a->db ? a->scratch + (size_t)slices * a->Cin * a->Cout : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)slices, (unsigned)((nb + wpb - 1) / wpb));
 #define ELO_WG4(CI_, CO_, XV_, GV_)                                                                                           \
     hipLaunchKernelGGL((weight_grad_kernel<CI_, CO_, XV_, GV_>), grid, dim3(64 * wpb), 0, s, a->x, a->g, a->rows, a->Cin, a->Cout, gy, gz, \
                        a->scratch, bpart)

@@ -1190,6 +1190,33 @@ typedef struct elo_weight_grad_args {
 int elo_weight_grad_slices(long rows, int Cin, int Cout);
 int elo_dense_weight_grad(const elo_weight_grad_args *a, elo_stream_t stream);
 
+/* WHICH KERNELS the entry points above launch (host-only queries: nothing is launched, no tensor pointer is dereferenced -- only the
+ * pointers' VALUES are read, for null and for their alignment).  Each launcher calls the same function, so the answer is what a launch
+ * takes.  All forms of an entry point compute the same function.
+ * elo_dense_weight_grad_form(a): ELO_WGRAD_FORM(CI, CO, xv, gv, waves, gy, gz), or the negative elo_status with which
+ *   elo_dense_weight_grad would refuse the block (ELO_ERR_ARG: a NULL block or tensor pointer other than db, a size <= 0; ELO_ERR_LIMIT:
+ *   rows * max(Cin, Cout) >= 2^31, or more than 2047 x 4095 -- 262140 in all -- blocks of dW).
+ *     CI x CO: the 16 x 16 tiles of dW one wave owns (a block).  CO = 4 from 4 column tiles on, 2 from 2, else 1; CI = the count in
+ *       1..4 that pads the ceil(Cin / 16) row tiles least, the larger on a tie or while the padding stays <= 25 %.
+ *     xv / gv: x / g is loaded as CI / CO consecutive channels per lane in one instruction (Cin % (16 CI) == 0 resp. Cout % (16 CO) == 0,
+ *       the tensor 16-byte aligned, CI != 3), else one channel per tile.  Same products in the same order: the same bits.
+ *     gy x gz: the grid of blocks; waves: per workgroup, min(gy * gz, 4) -- the workgroups are (slices, ceil(gy * gz / waves)).
+ *   One of 42 compiled kernels: CI in 1..4, CO in {1, 2, 4}, xv (never with CI = 3), gv.
+ * elo_bn_parts(rows_per_group, C): the partial rows (workgroups per group) of the reductions of elo_bn_stats and elo_bn_backward:
+ *   ceil(ceil(rows_per_group / (1024 / C)) / 8), at least 1, at most ELO_BN_MAX_PARTS; or the negative elo_status with which those
+ *   refuse the sizes (ELO_ERR_ARG: no rows; ELO_ERR_LIMIT: C not a power of two in 4..256). */
+#define ELO_WGRAD_FORM(CI, CO, xv, gv, waves, gy, gz) \
+    (((CI) - 1) | ((CO) >> 1) << 2 | (xv) << 4 | (gv) << 5 | ((waves) - 1) << 6 | (gz) << 8 | (gy) << 20)
+#define ELO_WGRAD_CI(form) (((form) & 3) + 1)
+#define ELO_WGRAD_CO(form) (1 << ((form) >> 2 & 3))
+#define ELO_WGRAD_XV(form) ((form) >> 4 & 1)
+#define ELO_WGRAD_GV(form) ((form) >> 5 & 1)
+#define ELO_WGRAD_WAVES(form) (((form) >> 6 & 3) + 1)
+#define ELO_WGRAD_GZ(form) ((form) >> 8 & 4095)
+#define ELO_WGRAD_GY(form) ((form) >> 20)
+int elo_dense_weight_grad_form(const elo_weight_grad_args *a);
+int elo_bn_parts(long rows_per_group, int C);
+
 /* out = x W (+ bias) over the rows of a training layer (utils/tf_util.py:120-185: conv2d 1x1 and its adjoint dx = dz W^T with
  * transposed = 1), fp32 on v_mfma_f32_16x16x4_f32: one pass over x, W staged once per workgroup in LDS.  Any Cin; Cout <= 192
  * and ceil(Cin/16) * ceil(Cout/16) <= 160 (elo_dense_rows_supported).  scratch != NULL: ALSO the batch-norm moments of out, from the
